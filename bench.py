@@ -2,8 +2,19 @@
 """DISTS / A-DISTS frame-pairs/s on MI355X (BASELINE.json metric), one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p|256|adists1080p|adists256|video10k]
-                  [--precision f16|f32s|f32|bf16] [--only]
+                  [--precision f16|f32s|f32|bf16] [--dump-outputs DIR] [--full [--only] [--no-cpu-baseline]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it sets up (the `auto` calibration included), warms up, times the K
+steps with a host clock that ends in a device synchronise, writes the outputs when asked and prints a compact line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, ...).  `--dump-outputs DIR` writes
+what the timed path computed in its last step -- the per-pair scores a caller of DISTS.forward / ADISTS.forward
+receives -- as DIR/scores.npy (float32; every rank's last step, in rank order; video10k: the whole video's scores).
+The frames are generated on the device from fixed seeds, so the same arguments give the same inputs from run to run.
+Everything else described below (the per-kernel event ring inside the timed region and the `roofline` /
+`roofline_hbm` / `kernel_ms_per_step` figures built from it, A-DISTS' second one-stream pass, the companion workloads
+and the CPU baseline) runs only with `--full`; `--only` and `--no-cpu-baseline` then drop the companions / the CPU
+baseline from it.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts that torch.distributed.run
 command itself as a CHILD process (before anything touches the GPU), relays rank 0's JSON line and exits with the
@@ -22,14 +33,14 @@ says what ran in `dtype`,
 shard across ranks with no data-path collective; the only exchange is ONE all-gather of the per-frame scores
 after the last step (inside the timed region) -- weak scaling, K steps of 8 pairs on every GPU.
 
-At N=1 the same JSON line also carries, under "workloads", the rest of the metric ("1080p & 256^2", DISTS
+With `--full` at N=1 the same JSON line also carries, under "workloads", the rest of the metric ("1080p & 256^2", DISTS
 and A-DISTS) measured the same way in the same process: 1080p in f16 (the opt-in fast mode: one MFMA per product; NOT
 what `auto` admits for every weight set), in f32m / f32m2 and in f32s (float32 activations, split-f16 products: the
 reference's own precision class, what `auto` runs when nothing faster is admitted), the shipped default ON THE OTHER TWO
 PINNED WEIGHT SETS (`1080p/auto@gain1.3`: the ImageNet-like activation magnitude, `1080p/auto@gain1.6`: the stress set --
 whatever rung each calibrates to, with its calibration report), exact `f32` (the only mode with the reference's 24-bit
 products; peak 157.3 TF), 256x256 B=32 (configs[1]) in f16 / f32m / f32s, and A-DISTS at 1080p B=8 (configs[4], f32s).
-`config.default_by_weight_set` puts the three defaults side by side.  Every entry has its own
+`config.default_by_weight_set` puts the three defaults side by side.  With `--full` every entry has its own
 `roofline` (the MFMA conv stack: algorithmic FLOPs of layers 1..12 / the HIP-event time of those launches, measured
 inside the timed region on the launch stream; `peak` is always the guide's dense 2.5 PFLOP/s f16 figure, and for
 f32m / f32s both the algorithmic and the issued-MFMA fraction are given) and `roofline_hbm` (the HBM-bound L2-pool +
@@ -41,7 +52,7 @@ when the library that ran is not the profiled build.
 `--workload video10k` is BASELINE.json configs[3]: a 10 000-frame 1080p video whose frames are generated on
 the device per batch from seed = frame index, sharded over the ranks (strong scaling), one all-gather.
 
-`cpu_baseline` times the CPU oracle (the reference's arithmetic, bit-identical to it in the authoring
+`cpu_baseline` (`--full`) times the CPU oracle (the reference's arithmetic, bit-identical to it in the authoring
 container) on a bounded sample of the headline workload on this box's host cores.
 """
 import argparse
@@ -287,8 +298,10 @@ def synth_frames(b, h, w, dev, seed):
     return x, y
 
 
-def run_workload(key, precision, steps, warmup, dev, world, rank, batch=0, vgg=VGG):
-    """K timed steps of one workload on this rank; returns (dt max-over-ranks, scores, ktimes, prec, B, H, W, src)."""
+def run_workload(key, precision, steps, warmup, dev, world, rank, batch=0, vgg=VGG, timing=False):
+    """K timed steps of one workload on this rank; returns (dt of this rank, ktimes, prec, B, H, W, src, last) with
+    `last` the scores of the last timed step of every rank, in rank order.  `timing` (--full) records the per-kernel
+    event ring inside the timed region (ktimes; else None)."""
     wl = WORKLOADS[key]
     B, H, W = batch or wl["B"], wl["H"], wl["W"]
     model, prec, src = make_model(wl["metric"], precision, dev, H, W, vgg)
@@ -308,17 +321,21 @@ def run_workload(key, precision, steps, warmup, dev, world, rank, batch=0, vgg=V
         if world > 1:  # warm the collective too
             sharding.gather_scores(scores, world * scores.numel())
         sync()
-        ops.timing_enable(not os.environ.get("NQA_BENCH_NO_EVENTS"))  # (development: what the event pairs cost)
+        if timing:
+            ops.timing_enable(not os.environ.get("NQA_BENCH_NO_EVENTS"))  # (development: what the event pairs cost)
         t0 = time.perf_counter()
         for k in range(steps):
             scores[k * B:(k + 1) * B] = model(x, y)
         all_scores = sharding.gather_scores(scores, world * scores.numel()) if world > 1 else scores
         sync()
         dt = time.perf_counter() - t0
-    ktimes = ops.timing_collect()
-    ops.timing_enable(False)
+    ktimes = None
+    if timing:
+        ktimes = ops.timing_collect()
+        ops.timing_enable(False)
     assert torch.isfinite(all_scores).all()
-    if wl["metric"] == "A-DISTS" and os.environ.get("NQA_ADISTS_STREAMS", "2") != "1":
+    last = all_scores.view(world, steps, B)[:, -1].reshape(-1).cpu()
+    if timing and wl["metric"] == "A-DISTS" and os.environ.get("NQA_ADISTS_STREAMS", "2") != "1":
         # A-DISTS runs a batch as two half-batches on two HIP streams: launches that share the chip have HIP-event
         # durations that are not additive (each runs slower for the company, or they do not overlap at all -- both
         # were seen).  `value` is the shipped two-stream form, timed above; the per-kernel times behind `roofline` come
@@ -337,12 +354,13 @@ def run_workload(key, precision, steps, warmup, dev, world, rank, batch=0, vgg=V
         finally:
             del os.environ["NQA_ADISTS_STREAMS"]
     del x, y
-    return dt, ktimes, prec, B, H, W, src
+    return dt, ktimes, prec, B, H, W, src, last
 
 
-def run_video(n_frames, precision, warmup, dev, world, rank, batch):
+def run_video(n_frames, precision, warmup, dev, world, rank, batch, timing=False):
     """configs[3]: frames [0, n_frames) of a 1080p video, generated on the device per batch from seed = frame
-    index (no rank ever holds the video), contiguous frame ranges per rank, ONE all-gather of the scores."""
+    index (no rank ever holds the video), contiguous frame ranges per rank, ONE all-gather of the scores.
+    Returns (dt, ktimes or None, prec, H, W, src, video columns, the (n_frames,) scores)."""
     wl = WORKLOADS["video10k"]
     H, W = wl["H"], wl["W"]
     net, prec, src = make_model("DISTS", precision, dev, H, W)
@@ -359,7 +377,8 @@ def run_video(n_frames, precision, warmup, dev, world, rank, batch):
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
-        ops.timing_enable(True)
+        if timing:
+            ops.timing_enable(True)
         t0 = time.perf_counter()
         scores = sharding.score_frames_sharded(score_batch, n_frames, batch, dev)
         torch.cuda.synchronize(dev)
@@ -367,11 +386,22 @@ def run_video(n_frames, precision, warmup, dev, world, rank, batch):
             dist.barrier()
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
-    ktimes = ops.timing_collect()
-    ops.timing_enable(False)
+    ktimes = None
+    if timing:
+        ktimes = ops.timing_collect()
+        ops.timing_enable(False)
     assert scores.numel() == n_frames and torch.isfinite(scores).all()
-    cols = video.video_columns("DISTS", scores.cpu().numpy())
-    return dt, ktimes, prec, H, W, src, {k: float(v) for k, v in cols.items()}
+    scores = scores.cpu()
+    cols = video.video_columns("DISTS", scores.numpy())
+    return dt, ktimes, prec, H, W, src, {k: float(v) for k, v in cols.items()}, scores
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (the scores are float32 on the device already)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().cpu().numpy().astype(np.float32))
 
 
 def self_launch(n, argv):
@@ -440,7 +470,7 @@ def run_stub(steps, warmup, world, rank):
         dist.barrier()
     dt = time.perf_counter() - t0
     assert all_scores.numel() == world * steps * B and torch.isfinite(all_scores).all()
-    return dt, B
+    return dt, B, all_scores.view(world, steps, B)[:, -1].reshape(-1)
 
 
 def main():
@@ -452,13 +482,19 @@ def main():
                     help="1080p (default, BASELINE configs[2]) | 256 | adists1080p | adists256 | video10k")
     ap.add_argument("--precision", default=None, help="default: DISTS auto (calibrated f16 / f32m / f32s), A-DISTS f32s; "
                                                       "or one of f16, f32m, f32s, f32, bf16")
-    ap.add_argument("--only", action="store_true", help="skip the companion workloads of the N=1 line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the per-kernel "
+                    "event ring and rooflines, the companion workloads of the N=1 line and the CPU baseline")
+    ap.add_argument("--only", action="store_true", help="with --full: skip the companion workloads of the N=1 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float32)")
     ap.add_argument("--batch", type=int, default=0, help="override pairs per GPU per step (experiments only)")
     ap.add_argument("--vgg", default=VGG, help="VGG-16 weights of the headline line: a checkpoint path or a stand-in spec "
                     "synth:<seed>[:<gain>] (profiling the default at another weight magnitude; the companions name their own)")
     ap.add_argument("--frames", type=int, default=10000, help="frames of the video10k workload")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # typed as `python bench.py --gpus N`: become the launcher (no GPU call has been made in this process)
@@ -498,9 +534,11 @@ def main():
         return max(per), per
 
     if stub:
-        dt, B = run_stub(args.steps, args.warmup, world, rank)
+        dt, B, last = run_stub(args.steps, args.warmup, world, rank)
         dt, per = rank_times(dt)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, scores=last)
             print(json.dumps({"metric": "stub frame-pairs/s (launch-path test only, no HIP kernel ran)",
                               "value": round(world * B * args.steps / dt, 2), "unit": "frame-pairs/s", "n_gpus": world,
                               "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -511,16 +549,19 @@ def main():
             dist.destroy_process_group()
         return
 
-    traffic = load_traffic()
+    traffic = load_traffic() if args.full else {}
     wl = WORKLOADS[args.workload]
+    timing_note = ("hipEvent pairs around every kernel launch are recorded inside the timed region" if args.full else
+                   "host clock around the timed steps, ending in a device synchronise; no per-kernel events (--full)")
 
     if args.workload == "video10k":
         batch = args.batch or wl["B"]
-        dt, ktimes, prec, H, W, src, cols = run_video(args.frames, args.precision, args.warmup, dev, world, rank, batch)
+        dt, ktimes, prec, H, W, src, cols, scores = run_video(args.frames, args.precision, args.warmup, dev, world, rank,
+                                                              batch, timing=args.full)
         dt, per = rank_times(dt)
         if rank == 0:
-            roof, hbm, kms = rooflines(ktimes, H, W, batch, prec, traffic_for(traffic, f"1080p/{prec}"))
-            # this rank's launches cover its own shard only: per-launch figures stay valid, per-step ones are per batch
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, scores=scores)
             per_rank = -(-args.frames // world)
             nsteps = max(1, -(-per_rank // batch))
             out = {"metric": "DISTS frame-pairs/s", "value": round(args.frames / dt, 2), "unit": "frame-pairs/s",
@@ -532,20 +573,23 @@ def main():
                               "height": H, "width": W, "vgg_weights": src,
                               "sharding": f"contiguous frame ranges over {world} ranks, one all-gather of scores"},
                    "per_rank_pairs_per_s": [round(-(-args.frames // world) / t, 2) for t in per],
-                   "video_columns": cols, "roofline": roof, "kernel_ms_per_step": kms, "roofline_hbm": hbm}
+                   "video_columns": cols}
+            if args.full:
+                # this rank's launches cover its own shard only: per-launch figures stay valid, per-step ones are per batch
+                roof, hbm, kms = rooflines(ktimes, H, W, batch, prec, traffic_for(traffic, f"1080p/{prec}"))
+                out.update({"roofline": roof, "kernel_ms_per_step": kms, "roofline_hbm": hbm})
             print(json.dumps(out), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
 
-    dt, ktimes, prec, B, H, W, src = run_workload(args.workload, args.precision, args.steps, args.warmup, dev, world,
-                                                  rank, args.batch, vgg=args.vgg)
+    dt, ktimes, prec, B, H, W, src, last = run_workload(args.workload, args.precision, args.steps, args.warmup, dev,
+                                                        world, rank, args.batch, vgg=args.vgg, timing=args.full)
     dt, per = rank_times(dt)
     out = None
     if rank == 0:
-        roof, hbm, kms = rooflines(ktimes, H, W, B, prec, traffic_for(traffic, f"{args.workload}/{prec}"), steps=args.steps)
-        if wl["metric"] == "A-DISTS":
-            roof["note"] += ONE_STREAM_NOTE
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, scores=last)
         out = {
             "metric": wl["metric"] + " frame-pairs/s",
             "value": round(world * B * args.steps / dt, 2),
@@ -564,15 +608,19 @@ def main():
                        "precision": (args.precision or "auto (shipped default)") + " -> " + prec
                                     + ("" if args.precision else " on the gain-1.0 stand-in weights; the same default runs f32m on the "
                                        "ImageNet-magnitude set (gain 1.3) and f32s on the stress set (gain 1.6): see "
-                                       "config.default_by_weight_set and workloads 1080p/auto@gain1.3, @gain1.6"),
+                                       "config.default_by_weight_set and workloads 1080p/auto@gain1.3, @gain1.6"
+                                       + ("" if args.full else " of the --full line")),
                        "auto_calibration": dict(AUTO_REPORT) if not args.precision and wl["metric"] == "DISTS" else None,
-                       "timing": "hipEvent pairs around every kernel launch are recorded inside the timed region"},
+                       "timing": timing_note},
             "per_rank_pairs_per_s": [round(B * args.steps / t, 2) for t in per],
-            "roofline": roof,
-            "kernel_ms_per_step": kms,
-            "roofline_hbm": hbm,
         }
-    if world == 1 and not args.only and args.workload == "1080p" and not args.batch:
+        if args.full:
+            roof, hbm, kms = rooflines(ktimes, H, W, B, prec, traffic_for(traffic, f"{args.workload}/{prec}"),
+                                       steps=args.steps)
+            if wl["metric"] == "A-DISTS":
+                roof["note"] += ONE_STREAM_NOTE
+            out.update({"roofline": roof, "kernel_ms_per_step": kms, "roofline_hbm": hbm})
+    if args.full and world == 1 and not args.only and args.workload == "1080p" and not args.batch:
         comp = {}
         defaults = {"gain 1.0 (synth:1234, the headline)": {"mode": prec, "pairs_per_s": out["value"],
                                                             "conv_frac_of_2.5PF": roof["frac"]}}
@@ -581,7 +629,8 @@ def main():
             vgg = entry[2] if len(entry) > 2 else VGG
             if (key, cprec, vgg) == (args.workload, prec, VGG):
                 continue  # that is the headline
-            cdt, ckt, cp, cb, ch, cw, csrc = run_workload(key, cprec, args.steps, args.warmup, dev, 1, 0, vgg=vgg)
+            cdt, ckt, cp, cb, ch, cw, csrc, _ = run_workload(key, cprec, args.steps, args.warmup, dev, 1, 0, vgg=vgg,
+                                                             timing=True)
             croof, chbm, ckms = rooflines(ckt, ch, cw, cb, cp, traffic_for(traffic, f"{key}/{cp}"), steps=args.steps)
             if WORKLOADS[key]["metric"] == "A-DISTS":
                 croof["note"] += ONE_STREAM_NOTE
@@ -604,7 +653,7 @@ def main():
         # (gain 1.3 is the ImageNet magnitude); the headline `value` is the first of these
         out["config"]["default_by_weight_set"] = defaults
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(H, W, adists=wl["metric"] == "A-DISTS")
         print(json.dumps(out), flush=True)
     if world > 1:

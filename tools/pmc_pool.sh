@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/pmc_pool; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT -- python3 $R/bench.py --workload 1080p --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/err.txt
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT -- python3 $R/bench.py --full --workload 1080p --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/err.txt
 python3 - <<PY
 import csv,glob
 for f in glob.glob("$OUT/*/*_counter_collection.csv"):

@@ -7,7 +7,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run_trace() {  # tag, bench args...
   local tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- python3 $R/bench.py "$@" --only --no-cpu-baseline > $OUT/bench_$tag.json 2> $OUT/trace_$tag.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- python3 $R/bench.py "$@" --full --only --no-cpu-baseline > $OUT/bench_$tag.json 2> $OUT/trace_$tag.err
   echo "trace $tag done" >> $R/gpurun_out/prof_r2.progress
 }
 run_trace 1080p_f16 --steps 10 --warmup 3

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/trace_b1; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --batch ${1:-1} --steps 50 --warmup 5 --no-cpu-baseline > $OUT/out.txt 2> $OUT/err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --full --batch ${1:-1} --steps 50 --warmup 5 --no-cpu-baseline > $OUT/out.txt 2> $OUT/err.txt
 python3 - <<PY
 import csv,glob
 f=glob.glob("$OUT/*/*_kernel_stats.csv")
