@@ -31,6 +31,10 @@
  *     4 bytes per element like float; the tapped maps (conv layers 1, 3, 6, 9, 12 = relu1_2 ..
  *     relu5_3) are plain float.  nqa_split16_encode / _decode convert;
  *   - VGG weights are handed over once as a packed blob (nqa_pack_vgg_weights).
+ *
+ * Gradients: the score's dependence on its inputs has two backward families below -- the pyramid backward
+ * (DISTS.forward(require_grad=True), nqa_conv3x3_split ... nqa_conv1_1_backward) and the statistics backward onto
+ * caller-provided feature maps (forward_from_feats under autograd, nqa_dists_stats_nchw_backward).
  */
 #ifndef NQA_H
 #define NQA_H
@@ -153,6 +157,22 @@ size_t nqa_stats_scratch_bytes(int B, const int C[NQA_NUM_TAPS], const int Hk[NQ
 int nqa_dists_stats_nchw(const float *const fx[NQA_NUM_TAPS], const float *const fy[NQA_NUM_TAPS], int B,
                          const int C[NQA_NUM_TAPS], const int Hk[NQA_NUM_TAPS], const int Wk[NQA_NUM_TAPS],
                          void *scratch, size_t scratch_bytes, float *s1, float *s2, void *stream);
+
+/* Backward of nqa_dists_stats_nchw: forward_from_feats under autograd (the training loss of the reference's
+ * no-reference models, nerf_qa/model_nr_v8.py:258-265).  Given g_s1 = dL/dS1 and g_s2 = dL/dS2 (dev float32 (B, ctot),
+ * ctot = sum C[k]), writes gx[k] = dL/dfx[k] and gy[k] = dL/dfy[k] (dev float32 NCHW, the shapes of fx[k]); either of
+ * gx[k], gy[k] may be null, and nothing is computed or written for that map.  Per (pair, channel) plane of N pixels:
+ *   gx = g1 dS1/dmx / N + 2 g2 dS2/dv / N (x - mx) + g2 dS2/dcov / N (y - my), gy the same with x and y swapped,
+ * the coefficients from the forward's fp64 sums and the affine map evaluated in fp64, rounded to float once.
+ * fwd_scratch / fwd_bytes: the scratch that the MATCHING nqa_dists_stats_nchw call (same maps, B, C, Hk, Wk) filled,
+ * left unchanged since; coef: dev, nqa_stats_backward_bytes(B, C) bytes of per-plane coefficients (overwritten).
+ * Two launches, both counted as NQA_K_STATS by the timing ring; no atomics (bitwise repeatable). */
+size_t nqa_stats_backward_bytes(int B, const int C[NQA_NUM_TAPS]);
+int nqa_dists_stats_nchw_backward(const float *const fx[NQA_NUM_TAPS], const float *const fy[NQA_NUM_TAPS], int B,
+                                  const int C[NQA_NUM_TAPS], const int Hk[NQA_NUM_TAPS], const int Wk[NQA_NUM_TAPS],
+                                  const void *fwd_scratch, size_t fwd_bytes, const float *g_s1, const float *g_s2,
+                                  void *coef, size_t coef_bytes, float *const gx[NQA_NUM_TAPS],
+                                  float *const gy[NQA_NUM_TAPS], void *stream);
 
 /* alpha/beta weighted sum -> score, DISTS_pt.py:127-129,135,142,144:
  * w = sum(alpha)+sum(beta); score_b = 1 - sum_c alpha_c/w S1_bc - sum_c beta_c/w S2_bc.

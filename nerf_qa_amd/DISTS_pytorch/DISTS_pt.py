@@ -592,8 +592,13 @@ class DISTS(torch.nn.Module):
 
     def forward_from_feats(self, feats0, feats1, batch_average=False):
         if torch.is_grad_enabled() and any(f.requires_grad for f in list(feats0) + list(feats1)):
-            raise NotImplementedError("forward_from_feats on grad-carrying features (the NR decoder, "
-                                      "model_nr_v8.py:258-265) is outside this build's scope")
+            # the NR models' training loss (model_nr_v8.py:258-265): the same statistics kernel, with a HIP backward
+            # onto the maps (nerf_qa_amd/autograd.py); the weighted sum stays torch so alpha and beta get theirs too
+            if len(feats0) != 6 or len(feats1) != 6:
+                raise ValueError("expected six feature maps per image")
+            from ..autograd import FeatsSimilarities
+            s1, s2 = FeatsSimilarities.apply(*feats0, *feats1)
+            return self._weighted(s1, s2, batch_average)
         s1, s2 = ops.dists_stats_nchw(feats0, feats1)
         return self._weighted(s1, s2, batch_average)
 

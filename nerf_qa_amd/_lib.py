@@ -48,6 +48,10 @@ _SIGNATURES = {
     "nqa_stats_scratch_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "nqa_dists_stats_nchw": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   _vp, _sz, _vp, _vp, _vp]),
+    "nqa_stats_backward_bytes": (_sz, [_i, C.POINTER(_i)]),
+    "nqa_dists_stats_nchw_backward": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i),
+                                           C.POINTER(_i), _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp),
+                                           _vp]),
     "nqa_dists_score": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "nqa_conv_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nqa_dists_fused_taps": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),

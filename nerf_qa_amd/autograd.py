@@ -192,3 +192,29 @@ class DistsSimilarities(torch.autograd.Function):
         x, y = ctx.saved_tensors
         gx, gy = dists_backward(ctx.module, x, y, g1.contiguous(), g2.contiguous())
         return (gx if ctx.needs_input_grad[0] else None), (gy if ctx.needs_input_grad[1] else None), None
+
+
+class FeatsSimilarities(torch.autograd.Function):
+    """(feats0[0..5], feats1[0..5]) -> (S1, S2), each (B, sum C), differentiable in all twelve maps: forward_from_feats
+    under autograd (DISTS_pt.py:181-202; the training loss of the reference's no-reference models, model_nr_v8.py:258-265).
+    Values from the same statistics kernel as the no-grad call; backward = two launches of csrc/nqa_stats_backward.hip
+    on the forward's fp64 sums, for the maps that need a gradient only.  Each gradient comes back in its map's dtype and
+    shape."""
+
+    @staticmethod
+    def forward(ctx, *feats):
+        f = [ops._f32c(t) for t in feats]
+        s1, s2, scratch = ops.dists_stats_nchw(f[:6], f[6:], keep_scratch=True)
+        ctx.save_for_backward(*f)
+        ctx.scratch = scratch
+        ctx.dtypes = [t.dtype for t in feats]
+        return s1, s2
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        f = ctx.saved_tensors
+        need = list(ctx.needs_input_grad)
+        if not any(need):
+            return (None,) * 12
+        gx, gy = ops.dists_stats_nchw_backward(f[:6], f[6:], ctx.scratch, g1, g2, need[:6], need[6:])
+        return tuple(None if g is None else g.to(dt) for g, dt in zip(gx + gy, ctx.dtypes))

@@ -849,6 +849,55 @@ int nqa_dists_stats_nchw(const float *const fx[NQA_NUM_TAPS], const float *const
   return finalize(part, p.d, B, s1, s2, st);
 }
 
+// ---- backward of nqa_dists_stats_nchw (forward_from_feats under autograd) ----
+size_t nqa_stats_backward_bytes(int B, const int C[NQA_NUM_TAPS]) {
+  if (B <= 0 || !C) return 0;
+  long ctot = 0;
+  for (int k = 0; k < 6; ++k) {
+    if (C[k] <= 0) return 0;
+    ctot += C[k];
+  }
+  return align_up((size_t)B * ctot * 6 * sizeof(double), 256);
+}
+
+int nqa_dists_stats_nchw_backward(const float *const fx[NQA_NUM_TAPS], const float *const fy[NQA_NUM_TAPS], int B,
+                                  const int C[NQA_NUM_TAPS], const int Hk[NQA_NUM_TAPS], const int Wk[NQA_NUM_TAPS],
+                                  const void *fwd_scratch, size_t fwd_bytes, const float *g_s1, const float *g_s2,
+                                  void *coef, size_t coef_bytes, float *const gx[NQA_NUM_TAPS],
+                                  float *const gy[NQA_NUM_TAPS], void *stream) {
+  if (!fx || !fy || !C || !Hk || !Wk || !fwd_scratch || !g_s1 || !g_s2 || !coef || !gx || !gy || B <= 0) {
+    set_error("dists_stats_nchw_backward: bad argument (null pointer or B <= 0)");
+    return NQA_E_ARG;
+  }
+  int HW[6];
+  for (int k = 0; k < 6; ++k) {
+    if (!fx[k] || !fy[k] || C[k] <= 0 || Hk[k] <= 0 || Wk[k] <= 0) {
+      set_error("dists_stats_nchw_backward: bad feature %d", k);
+      return NQA_E_ARG;
+    }
+    if ((long)Hk[k] * Wk[k] > (1L << 30)) {  // (the gradient kernel's in-plane offsets are 32-bit)
+      set_error("dists_stats_nchw_backward: feature %d has %ld > 2^30 pixels per plane", k, (long)Hk[k] * Wk[k]);
+      return NQA_E_SHAPE;
+    }
+    HW[k] = Hk[k] * Wk[k];
+  }
+  const StatsPlan p = stats_plan(B, C, HW, nullptr, 6, NQA_PREC_F32);
+  if (fwd_bytes < p.doubles * 8) {
+    set_error("dists_stats_nchw_backward: forward scratch %zu < %zu bytes", fwd_bytes, p.doubles * 8);
+    return NQA_E_WORKSPACE;
+  }
+  const size_t need = nqa_stats_backward_bytes(B, C);
+  if (coef_bytes < need) {
+    set_error("dists_stats_nchw_backward: coefficient buffer %zu < %zu bytes", coef_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *cf = static_cast<double *>(coef);
+  int rc;
+  if ((rc = stats_coef(static_cast<const double *>(fwd_scratch), p.d, B, g_s1, g_s2, cf, st))) return rc;
+  return stats_grad(fx, fy, B, C, HW, cf, gx, gy, st);
+}
+
 // ---- conv + L2-pool + statistics as a single operator (tests, tools; the DISTS path calls the launcher directly) ----
 static __global__ void part_reduce_kernel(const double *__restrict__ part, int nblk, int C, double *__restrict__ sums, long total) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (b, c, s)

@@ -200,6 +200,39 @@ struct StageDesc {
   int ctot;
 };
 
+// Moments of one (pair b, global channel gc) from a stage's per-block partial sums, folded by one wave (lane = 0..63:
+// lanes stride over the blocks, then a shuffle tree; the total is valid in lane 0): mx, my, vx, vy, cov in fp64.
+// Returns the stage k and its channel c.  (finalize_kernel and the statistics' backward share it, so the backward
+// differentiates exactly the numbers the forward formed.)
+struct PlaneMoments {
+  int k, c;
+  double mx, my, vx, vy, cov, inv;
+};
+__device__ inline PlaneMoments plane_moments(const double *__restrict__ part, const StageDesc &d, int b, int gc, int lane) {
+  PlaneMoments m;
+  int k = 0;
+  while (k + 1 < d.nstage && gc >= d.coff[k + 1]) ++k;
+  const int c = gc - d.coff[k];
+  const double *p = part + d.part_off[k] + ((size_t)b * d.nblk[k] * d.c[k] + c) * 5;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int blk = lane; blk < d.nblk[k]; blk += 64) {
+#pragma unroll
+    for (int q = 0; q < 5; ++q) s[q] += p[(size_t)blk * d.c[k] * 5 + q];
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q)
+    for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
+  m.k = k;
+  m.c = c;
+  m.inv = 1.0 / (double)d.hw[k];
+  m.mx = s[0] * m.inv;
+  m.my = s[1] * m.inv;
+  m.vx = s[2] * m.inv - m.mx * m.mx;
+  m.vy = s[3] * m.inv - m.my * m.my;
+  m.cov = s[4] * m.inv - m.mx * m.my;
+  return m;
+}
+
 size_t max_act_elems(int H, int W);  // largest activation map of the pyramid, elements per image (nqa_api.hip)
 
 // ---- host launchers shared between translation units ---------------------------------
@@ -239,6 +272,15 @@ int pool_stats(const void *feat, int B, int H, int W, int C, int prec, void *poo
 int stats_nhwc(const void *feat, int B, int HW, int C, int prec, double *part, hipStream_t st);
 int stats_nchw(const float *fx, const float *fy, int B, int C, int HW, double *part, hipStream_t st);
 int finalize(const double *part, const StageDesc &d, int B, float *s1, float *s2, hipStream_t st);
+// ---- backward of the NCHW statistics (nqa_stats_backward.hip; forward_from_feats under autograd) ----
+// per-plane fp64 coefficients {mx, my, a, b, ox, oy} from the forward's partials and dL/dS1, dL/dS2 (B, ctot);
+// tap k's planes (b, c) at record B * coff[k] + b * C[k] + c
+int stats_coef(const double *part, const StageDesc &d, int B, const float *g_s1, const float *g_s2, double *coef,
+               hipStream_t st);
+// gx[k] / gy[k] (either may be null) from the maps and those coefficients, all six taps in one launch
+int stats_grad(const float *const fx[NQA_NUM_TAPS], const float *const fy[NQA_NUM_TAPS], int B, const int C[NQA_NUM_TAPS],
+               const int HW[NQA_NUM_TAPS], const double *coef, float *const gx[NQA_NUM_TAPS], float *const gy[NQA_NUM_TAPS],
+               hipStream_t st);
 int score(const float *s1, const float *s2, const float *alpha, const float *beta, int B, float *out, hipStream_t st);
 int nhwc_to_nchw(const void *in, int n, int HW, int C, int prec, float *out, hipStream_t st);
 // ---- conv + L2-pool + statistics in one kernel (nqa_conv_pool.hip; the DISTS path's tap 2) ----

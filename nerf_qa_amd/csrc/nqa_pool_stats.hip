@@ -357,23 +357,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double *__restrict_
   const int lane = threadIdx.x & 63;
   const int gc = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (gc >= d.ctot) return;
-  int k = 0;
-  while (k + 1 < d.nstage && gc >= d.coff[k + 1]) ++k;
-  const int c = gc - d.coff[k];
-  const double *p = part + d.part_off[k] + ((size_t)b * d.nblk[k] * d.c[k] + c) * 5;
-  double s[5] = {0, 0, 0, 0, 0};
-  for (int blk = lane; blk < d.nblk[k]; blk += 64) {
-#pragma unroll
-    for (int q = 0; q < 5; ++q) s[q] += p[(size_t)blk * d.c[k] * 5 + q];
-  }
-#pragma unroll
-  for (int q = 0; q < 5; ++q)
-    for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off, 64);
+  const PlaneMoments m = plane_moments(part, d, b, gc, lane);
   if (lane) return;
-  const double inv = 1.0 / (double)d.hw[k];
-  const double mx = s[0] * inv, my = s[1] * inv;
-  const double vx = s[2] * inv - mx * mx, vy = s[3] * inv - my * my;
-  const double cov = s[4] * inv - mx * my;
+  const double mx = m.mx, my = m.my, vx = m.vx, vy = m.vy, cov = m.cov;
   const double c1 = 1e-6, c2 = 1e-6;
   s1[(size_t)b * d.ctot + gc] = (float)((2.0 * mx * my + c1) / (mx * mx + my * my + c1));
   s2[(size_t)b * d.ctot + gc] = (float)((2.0 * cov + c2) / (vx + vy + c2));

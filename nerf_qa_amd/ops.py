@@ -265,8 +265,8 @@ def dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, 
     return s1, s2
 
 
-def dists_stats_nchw(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor]):
-    """(S1, S2) from two lists of six float32 NCHW feature maps (forward_from_feats)."""
+def _feats_args(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor]):
+    """Two lists of six NCHW maps -> (device, float32 contiguous maps 0 and 1, B, the C / H / W / pointer arrays)."""
     if len(feats0) != 6 or len(feats1) != 6:
         raise ValueError("expected six feature maps per image")
     dev = _need_cuda(*feats0, *feats1)
@@ -279,16 +279,50 @@ def dists_stats_nchw(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tens
     cs = (C.c_int * 6)(*[f.shape[1] for f in f0])
     hs = (C.c_int * 6)(*[f.shape[2] for f in f0])
     wsz = (C.c_int * 6)(*[f.shape[3] for f in f0])
+    p0 = (C.c_void_p * 6)(*[ptr(f) for f in f0])
+    p1 = (C.c_void_p * 6)(*[ptr(f) for f in f1])
+    return dev, f0, f1, b, cs, hs, wsz, p0, p1
+
+
+def dists_stats_nchw(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor], keep_scratch: bool = False):
+    """(S1, S2) from two lists of six float32 NCHW feature maps (forward_from_feats).
+
+    keep_scratch=True returns (S1, S2, scratch): the forward's per-block fp64 sums, which dists_stats_nchw_backward
+    reads (pass it unchanged, with the same maps)."""
+    dev, f0, f1, b, cs, hs, wsz, p0, p1 = _feats_args(feats0, feats1)
     ctot = sum(f.shape[1] for f in f0)
     s1 = torch.empty((b, ctot), dtype=torch.float32, device=dev)
     s2 = torch.empty((b, ctot), dtype=torch.float32, device=dev)
     nbytes = lib().nqa_stats_scratch_bytes(b, cs, hs, wsz)
     scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-    p0 = (C.c_void_p * 6)(*[ptr(f) for f in f0])
-    p1 = (C.c_void_p * 6)(*[ptr(f) for f in f1])
     _call(dev, lib().nqa_dists_stats_nchw, p0, p1, b, cs, hs, wsz, ptr(scratch), scratch.numel(), ptr(s1), ptr(s2),
                                      stream_ptr(dev))
+    if keep_scratch:
+        return s1, s2, scratch
     return s1, s2
+
+
+def dists_stats_nchw_backward(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor], scratch: torch.Tensor,
+                              g_s1: torch.Tensor, g_s2: torch.Tensor, need0: Sequence[bool], need1: Sequence[bool]):
+    """(g0, g1): lists of six float32 NCHW gradients dL/dfeats0[k], dL/dfeats1[k] given dL/dS1, dL/dS2 (B, ctot), or
+    None where need0[k] / need1[k] is False (nothing is computed for those).  scratch: what
+    dists_stats_nchw(feats0, feats1, keep_scratch=True) returned, unchanged."""
+    if len(need0) != 6 or len(need1) != 6:
+        raise ValueError("expected six flags per list")
+    dev, f0, f1, b, cs, hs, wsz, p0, p1 = _feats_args(feats0, feats1)
+    _need_cuda(f0[0], scratch, g_s1, g_s2)
+    ctot = sum(f.shape[1] for f in f0)
+    g_s1, g_s2 = _f32c(g_s1), _f32c(g_s2)
+    if tuple(g_s1.shape) != (b, ctot) or tuple(g_s2.shape) != (b, ctot):
+        raise ValueError(f"expected gradients of shape {(b, ctot)}, got {tuple(g_s1.shape)} / {tuple(g_s2.shape)}")
+    g0 = [torch.empty_like(f) if n else None for f, n in zip(f0, need0)]
+    g1 = [torch.empty_like(f) if n else None for f, n in zip(f1, need1)]
+    coef = torch.empty(max(lib().nqa_stats_backward_bytes(b, cs), 256), dtype=torch.uint8, device=dev)
+    q0 = (C.c_void_p * 6)(*[None if g is None else ptr(g) for g in g0])
+    q1 = (C.c_void_p * 6)(*[None if g is None else ptr(g) for g in g1])
+    _call(dev, lib().nqa_dists_stats_nchw_backward, p0, p1, b, cs, hs, wsz, ptr(scratch), scratch.numel(), ptr(g_s1),
+          ptr(g_s2), ptr(coef), coef.numel(), q0, q1, stream_ptr(dev))
+    return g0, g1
 
 
 def dists_score(s1: torch.Tensor, s2: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
