@@ -200,6 +200,18 @@ int nqa_adists_forward(const float *x_nchw, const float *y_nchw, int B, int H, i
 int nqa_adists_forward_map(const float *x_nchw, const float *y_nchw, int B, int H, int W, const void *packed_w,
                            int prec, void *workspace, size_t workspace_bytes, float *d, float *map, void *stream);
 
+/* A-DISTS and DISTS of the same pairs from ONE pyramid.  nqa_adists_forward already fills, for its channel norms and
+ * global-branch moments, the fp64 per-(pair, channel) sums of all six taps -- the very sums nqa_dists_forward folds into
+ * S1 / S2, from the same statistics kernels.  This call runs nqa_adists_forward's launches unchanged (d, and map when
+ * non-null, are bit-identical to nqa_adists_forward / nqa_adists_forward_map) plus one finalisation launch on those sums
+ * (counted as NQA_K_STATS): s1, s2 dev float32 (B,1475) receive what nqa_dists_forward writes for (x, y) in `prec`, up
+ * to the order of the fp64 partial sums of taps 1-2 where nqa_dists_forward fuses them into a conv kernel.  Workspace
+ * nqa_adists_workspace_bytes(B, H, W, prec); map may be null.  Arguments are checked as in nqa_adists_forward, and s1 /
+ * s2 must not be null. */
+int nqa_adists_dists_forward(const float *x_nchw, const float *y_nchw, int B, int H, int W, const void *packed_w,
+                             int prec, void *workspace, size_t workspace_bytes, float *d, float *s1, float *s2,
+                             float *map, void *stream);
+
 /* ---- input preparation on the device (decoded uint8 frame -> metric input) ------------ */
 
 /* transforms.ToTensor / `torch.from_numpy(frame).permute(2,0,1).float() / 255.0` (prep.py:89,

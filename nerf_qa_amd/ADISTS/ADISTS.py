@@ -127,7 +127,12 @@ class ADISTS(torch.nn.Module):
         d["_packed"], d["_ws"], d["_side"] = {}, ops.Workspace(), {}
 
     def _score(self, x, y, prec):
-        """D (B,) of a batch.  Large frames in batches of TWO_STREAM_MIN_PAIRS or more run as two half-batches on two
+        """D (B,) of a batch (see _batched)."""
+        return self._batched(x, y, prec, lambda a, b, packed: ops.adists_forward(a, b, packed, prec, self._ws))
+
+    def _batched(self, x, y, prec, call):
+        """call(x, y, packed) -> a tensor or a tuple of tensors with one row per pair (_score: D; pair.score_pair: D, S1,
+        S2), for the whole batch.  Large frames in batches of TWO_STREAM_MIN_PAIRS or more run as two half-batches on two
         HIP streams: the VALU-bound window pass of one half rides beside the MFMA-bound conv stack of the other (+2-3 %
         at 1080p, profiles/r03_adists_two_streams.txt; pairs are independent, so the scores are those of one call).
         NQA_ADISTS_STREAMS=1 switches it off."""
@@ -136,7 +141,7 @@ class ADISTS(torch.nn.Module):
         two = (dev.type == "cuda" and b >= TWO_STREAM_MIN_PAIRS and x.shape[-2] * x.shape[-1] >= TWO_STREAM_MIN_PIXELS
                and os.environ.get("NQA_ADISTS_STREAMS", "2") != "1")
         if not two:
-            return ops.adists_forward(x, y, packed, prec, self._ws)
+            return call(x, y, packed)
         side = self._side.get(str(dev))
         if side is None:
             side = self._side[str(dev)] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
@@ -146,10 +151,12 @@ class ADISTS(torch.nn.Module):
         for st, (lo, hi) in zip(side, ((0, half), (half, b))):
             st.wait_stream(main)  # the frames (and the packed weights) were produced on the caller's stream
             with torch.cuda.stream(st):
-                outs.append(ops.adists_forward(x[lo:hi], y[lo:hi], packed, prec, self._ws))  # (scratch is per stream)
+                outs.append(call(x[lo:hi], y[lo:hi], packed))  # (scratch is per stream)
         for st in side:
             main.wait_stream(st)
-        return torch.cat(outs)
+        if torch.is_tensor(outs[0]):
+            return torch.cat(outs)
+        return tuple(torch.cat(parts) for parts in zip(*outs))
 
     def _loss_with_grad(self, x, y):
         """1 - mean(D) WITH its gradient towards x and y (ADISTS.py:139-141, 195).  The tapped maps come from

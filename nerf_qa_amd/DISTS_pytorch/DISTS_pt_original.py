@@ -59,8 +59,8 @@ class DISTS(_BaseDISTS):
         wsum = a.sum() + b.sum()
         return a / wsum, b / wsum
 
-    def forward(self, x, y, require_grad=False, batch_average=False):
-        s1, s2 = self._similarities(x, y, require_grad)
+    def _weighted(self, s1, s2, batch_average):
+        """score from S1, S2 with this variant's weighting (:111-134); forward and pair.score_pair share it."""
         flags = str(config().dists_weight_norm).split("+")
         alpha = torch.relu(self.alpha) if "relu" in flags else self.alpha
         beta = torch.relu(self.beta) if "relu" in flags else self.beta
@@ -78,6 +78,10 @@ class DISTS(_BaseDISTS):
             o += c
         score = 1 - (dist1 + dist2).squeeze()
         return score.mean() if batch_average else score
+
+    def forward(self, x, y, require_grad=False, batch_average=False):
+        s1, s2 = self._similarities(x, y, require_grad)
+        return self._weighted(s1, s2, batch_average)
 
 
 def prepare_image(image, resize=True):

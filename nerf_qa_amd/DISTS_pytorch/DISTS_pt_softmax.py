@@ -39,8 +39,8 @@ class DISTS(_BaseDISTS):
         w = torch.softmax(torch.cat([self.alpha.detach(), self.beta.detach()], dim=1).float(), dim=1).reshape(-1)
         return w[:self.alpha.numel()], w[self.alpha.numel():]
 
-    def forward(self, x, y, require_grad=False, batch_average=False, warp=None, certainty=None):
-        s1, s2 = self._similarities(x, y, require_grad)
+    def _weighted(self, s1, s2, batch_average):
+        """score from S1, S2 with the softmax weighting (:117-134); forward and pair.score_pair share it."""
         w = torch.softmax(torch.cat([self.alpha, self.beta], dim=1), dim=1)
         alpha, beta = torch.split(w, self.alpha.shape[1], dim=1)
         alpha, beta = alpha.view(1, -1), beta.view(1, -1)
@@ -54,3 +54,7 @@ class DISTS(_BaseDISTS):
             o += c
         score = 1 - (dist1 + dist2).squeeze()
         return score.mean() if batch_average else score
+
+    def forward(self, x, y, require_grad=False, batch_average=False, warp=None, certainty=None):
+        s1, s2 = self._similarities(x, y, require_grad)
+        return self._weighted(s1, s2, batch_average)

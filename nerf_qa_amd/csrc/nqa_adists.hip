@@ -1146,7 +1146,8 @@ size_t nqa_adists_workspace_bytes(int B, int H, int W, int prec) {
 }  // extern "C"
 
 static int adists_run(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
-                      size_t ws_bytes, float *d_out, float *map_out, void *stream) {
+                      size_t ws_bytes, float *d_out, float *map_out, void *stream, float *s1_out = nullptr,
+                      float *s2_out = nullptr) {
   if (!x || !y || !packed || !ws || !d_out) {
     set_error("adists_forward: null pointer");
     return NQA_E_ARG;
@@ -1213,6 +1214,9 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
       }
     }
   }
+  // ---- DISTS' S1 / S2 from the same sums (nqa_adists_dists_forward only).  `part` is complete here and nothing
+  // below writes it: adists_prep_kernel reads it, hsum reuses rows of q, the chain's `ones` lives in bufB ----
+  if (s1_out && (rc = finalize(part, p.sd, B, s1_out, s2_out, st))) return rc;
   // ---- per-channel scalars, stage-0 images as NHWC4, entropies, channel weights ----
   {
     dim3 grid(cdiv(ctot, 256), B);
@@ -1352,6 +1356,16 @@ int nqa_adists_forward_map(const float *x, const float *y, int B, int H, int W, 
     return NQA_E_ARG;
   }
   return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, map_out, stream);
+}
+
+int nqa_adists_dists_forward(const float *x, const float *y, int B, int H, int W, const void *packed, int prec,
+                             void *ws, size_t ws_bytes, float *d_out, float *s1, float *s2, float *map_out,
+                             void *stream) {
+  if (!s1 || !s2) {
+    set_error("adists_dists_forward: null similarity pointer");
+    return NQA_E_ARG;
+  }
+  return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, map_out, stream, s1, s2);
 }
 
 }  // extern "C"

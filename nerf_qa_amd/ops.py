@@ -392,6 +392,32 @@ def adists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec,
     return d
 
 
+def adists_dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, ws: Workspace | None = None,
+                         with_map: bool = False):
+    """(D (B,), S1 (B,1475), S2 (B,1475)[, map (B,H,W)]) from ONE pyramid: adists_forward's D (and map), bit for bit, plus
+    the similarities dists_forward computes for the same pairs in `prec`, folded from the sums A-DISTS forms anyway
+    (include/nqa.h, nqa_adists_dists_forward)."""
+    p = prec_id(prec)
+    dev = _need_cuda(x, y, packed)
+    x, y = _f32c(x), _f32c(y)
+    if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"expected two (B,3,H,W) tensors of equal shape, got {tuple(x.shape)} / {tuple(y.shape)}")
+    b, _, h, w = x.shape
+    mb = _max_pairs(lambda n: lib().nqa_adists_workspace_bytes(n, h, w, p), b)
+    if mb < b:
+        parts = [adists_dists_forward(x[i:i + mb], y[i:i + mb], packed, prec, ws, with_map) for i in range(0, b, mb)]
+        return tuple(torch.cat([q[j] for q in parts]) for j in range(4 if with_map else 3))
+    d = torch.empty((b,), dtype=torch.float32, device=dev)
+    s1 = torch.empty((b, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    s2 = torch.empty((b, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    m = torch.empty((b, h, w), dtype=torch.float32, device=dev) if with_map else None
+    nbytes = lib().nqa_adists_workspace_bytes(b, h, w, p)
+    buf = (ws or Workspace()).get(nbytes, dev)
+    _call(dev, lib().nqa_adists_dists_forward, ptr(x), ptr(y), b, h, w, ptr(packed), p, ptr(buf), buf.numel(), ptr(d),
+          ptr(s1), ptr(s2), ptr(m) if with_map else None, stream_ptr(dev))
+    return (d, s1, s2, m) if with_map else (d, s1, s2)
+
+
 # ---- input preparation (SURVEY.md section 8 f2) ---------------------------------------------------
 def u8hwc_to_f32nchw(frames: torch.Tensor, pil_roundtrip: bool = False) -> torch.Tensor:
     """ToTensor on the device: uint8 (n,H,W,3) -> float32 (n,3,H,W) / 255 (prep.py:89, data.py:80)."""

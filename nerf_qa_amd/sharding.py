@@ -21,35 +21,41 @@ def shard_range(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, min(n_frames, lo + per)
 
 
-def gather_scores(local: torch.Tensor, n_frames: int, group=None) -> torch.Tensor:
-    """All-gather the per-rank score vectors into the full (n_frames,) vector on every rank."""
+def gather_scores(local: torch.Tensor, n_frames: int, group=None, columns: int = 1) -> torch.Tensor:
+    """All-gather the per-rank score vectors into the full (n_frames,) vector on every rank.  columns > 1: `local` is a
+    (frames, columns) table (several metrics of the same frames, video.score_video(shared_pyramid=True)) and the result
+    is the full (n_frames, columns) table, still from ONE collective."""
     if not (dist.is_available() and dist.is_initialized()):
-        assert local.numel() == n_frames
+        assert local.numel() == n_frames * columns
         return local
     world = dist.get_world_size(group)
     per = -(-n_frames // world)
-    pad = torch.zeros(per, dtype=torch.float32, device=local.device)
-    pad[: local.numel()] = local.float()
-    out = torch.empty(world * per, dtype=torch.float32, device=local.device)
+    pad = torch.zeros(per * columns, dtype=torch.float32, device=local.device)
+    pad[: local.numel()] = local.float().reshape(-1)
+    out = torch.empty(world * per * columns, dtype=torch.float32, device=local.device)
     dist.all_gather_into_tensor(out, pad, group=group)
-    return out[:n_frames]
+    if columns == 1:
+        return out[:n_frames]
+    return out.view(world * per, columns)[:n_frames]
 
 
 def score_frames_sharded(score_batch: Callable[[int, int], torch.Tensor], n_frames: int, batch: int,
-                         device, group=None) -> torch.Tensor:
+                         device, group=None, columns: int = 1) -> torch.Tensor:
     """Score frames [0, n_frames) across the process group.
 
     score_batch(lo, hi) returns the (hi-lo,) scores of frames lo..hi-1 on `device`
     (it loads / generates those frames itself).  Returns the full score vector on every rank.
+    columns > 1: score_batch returns a (hi-lo, columns) table and so does this function, (n_frames, columns).
     """
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     lo, hi = shard_range(n_frames, rank, world)
     parts = []
+    shape = (-1,) if columns == 1 else (-1, columns)
     for s in range(lo, hi, batch):
-        parts.append(score_batch(s, min(hi, s + batch)).reshape(-1).float())
-    local = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=device)
-    return gather_scores(local, n_frames, group)
+        parts.append(score_batch(s, min(hi, s + batch)).reshape(shape).float())
+    local = torch.cat(parts) if parts else torch.zeros((0,) + shape[1:], dtype=torch.float32, device=device)
+    return gather_scores(local, n_frames, group, columns)
 
 
 def agree_precision(model, h: int, w: int, device, group=None) -> str:

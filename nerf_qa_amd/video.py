@@ -65,7 +65,8 @@ def synthetic_frames(indices, h: int, w: int, device):
 def score_video(ref: torch.Tensor, render: torch.Tensor, dists_model: Optional[torch.nn.Module] = None,
                 adists_model: Optional[torch.nn.Module] = None, batch_size: int = 8, group=None,
                 policy: Optional[str] = None, keep_aspect_ratio: bool = False, suffix: str = "",
-                with_frame_bias: bool = True, return_frame_scores: bool = False) -> Dict[str, object]:
+                with_frame_bias: bool = True, return_frame_scores: bool = False,
+                shared_pyramid: bool = False) -> Dict[str, object]:
     """Score one video given as two (N,3,H,W) float32 tensors on the GPU, or -- with `policy` -- as two
     decoded uint8 (N,H,W,3) frame stacks on the GPU that are prepared per batch on the device
     (prep.prepare_frames: "interp256" = prep.py:89-95, "pil256" = prepare_image, ...).
@@ -76,13 +77,22 @@ def score_video(ref: torch.Tensor, render: torch.Tensor, dists_model: Optional[t
     Returns the reference's columns for this video: `A-DISTS`/`DISTS` (+`suffix`) with _std/_min/_max,
     and when `with_frame_bias` (test2_prep.py's first pass, suffix "") `frame_count`,
     `frame_bias_adists`, `frame_bias_dists`.
+
+    shared_pyramid=True (both models required) scores every batch with pair.score_pair: the two metrics share one VGG
+    pyramid instead of running it once each, frames given with a `policy` are prepared once per batch instead of once
+    per metric, and a sharded video still costs one all-gather (of a two-column table).  The pair runs in A-DISTS'
+    precision, a function of the frame size alone, so nothing has to be agreed between ranks.  The A-DISTS columns are
+    those of the default mode bit for bit; the DISTS columns are those of DISTS(precision=<that precision>).
     """
     if ref.shape != render.shape:
         raise ValueError("ref and render differ in shape")
+    if shared_pyramid and (dists_model is None or adists_model is None):
+        raise ValueError("score_video(shared_pyramid=True) scores DISTS and A-DISTS from one pyramid: "
+                         "pass both dists_model and adists_model")
     n = ref.shape[0]
     out: Dict[str, object] = {}
 
-    def run(model_call: Callable[[torch.Tensor, torch.Tensor], torch.Tensor]) -> np.ndarray:
+    def run(model_call: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], columns: int = 1) -> np.ndarray:
         def batch(lo, hi):
             a, b = ref[lo:hi], render[lo:hi]
             if policy is not None:
@@ -90,21 +100,32 @@ def score_video(ref: torch.Tensor, render: torch.Tensor, dists_model: Optional[t
                 b = prep.prepare_frames(b, policy, keep_aspect_ratio=keep_aspect_ratio)
             return model_call(a, b)
 
-        scores = sharding.score_frames_sharded(batch, n, batch_size, ref.device, group)
+        scores = sharding.score_frames_sharded(batch, n, batch_size, ref.device, group, columns)
         return scores.cpu().numpy()
 
     frames = {}
-    if dists_model is not None and getattr(dists_model, "precision", None) == "auto" and policy is None:
+    if shared_pyramid:
+        from .pair import score_pair
+
+        def both(a, b):
+            ds, ad = score_pair(dists_model, adists_model, a, b, batch_average=False, as_loss=False)
+            return torch.stack([ad.reshape(-1).float(), ds.reshape(-1).float()], dim=1)
+
+        table = run(both, columns=2)
+        frames["A-DISTS"], frames["DISTS"] = np.ascontiguousarray(table[:, 0]), np.ascontiguousarray(table[:, 1])
+    elif dists_model is not None and getattr(dists_model, "precision", None) == "auto" and policy is None:
         # one precision mode per video: under a process group rank 0's calibration verdict is broadcast BEFORE the
         # shards are scored (ranks whose shard is empty never enter forward(), so the collective cannot live there);
         # with no process group this is the plain precision_for.  (With `policy` the prepared size is only known per
         # batch; callers who shard prepared-on-the-fly videos call sharding.agree_precision with that size themselves.)
         sharding.agree_precision(dists_model, int(ref.shape[-2]), int(ref.shape[-1]), ref.device, group)
-    if adists_model is not None:
+    if adists_model is not None and not shared_pyramid:
         frames["A-DISTS"] = run(lambda a, b: adists_model(a, b, as_loss=False))
+    if "A-DISTS" in frames:
         out.update(video_columns("A-DISTS", frames["A-DISTS"], suffix))
-    if dists_model is not None:
+    if dists_model is not None and not shared_pyramid:
         frames["DISTS"] = run(lambda a, b: dists_model(a, b, batch_average=False))
+    if "DISTS" in frames:
         out.update(video_columns("DISTS", frames["DISTS"], suffix))
     if with_frame_bias:
         out["frame_count"] = -(-n // batch_size)  # len(DataLoader): batches, as the reference counts them
