@@ -297,7 +297,8 @@ int nqa_timing_collect(int launches[NQA_K_COUNT], double ms[NQA_K_COUNT]);
  *                            format, zero bias -- e.g. a layer's flipped, transposed weights for its data gradient;
  *   nqa_conv3x3_split        that layer: split16 NHWC in, FLOAT NHWC out, ReLU optional;
  *   nqa_relu_mask_split16    g * (act > 0) as split16 records (act: a float tapped map, or split16);
- *   nqa_l2pool_backward      g_tap += d(L2-pool)/d(tap) applied to g_pooled (DISTS_pt.py:22-25), pooled = the forward's split16 map;
+ *   nqa_l2pool_backward      g_tap += d(L2-pool)/d(tap) applied to g_pooled (DISTS_pt.py:22-25); pooled_split16 is accepted and NOT read -- the
+ *                            pooled value is formed from the tap in float (split16 loses it below 2^-14);
  *   nqa_conv1_1_backward     g * (relu1_1 > 0) (float NHWC, 64 channels) -> gradient of the RAW image, float NCHW (n,3,H,W),
  *                            the (x - mean) / std of DISTS_pt.py:92 included; w = conv1_1's float32 OIHW weights on the device. */
 size_t nqa_packed_conv_split_bytes(int cout, int cin);

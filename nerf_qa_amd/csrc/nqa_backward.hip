@@ -43,10 +43,33 @@ __global__ __launch_bounds__(256) void relu_mask_split16_kernel(const float *__r
 }
 
 // g_x[iy, ix, c] += x[iy, ix, c] * sum over the (up to four) pooled pixels o whose 3x3 window holds (iy, ix) of
-// w(o; iy, ix) * g_y[o, c] / y[o, c],  w = hanning3x3 / 16, y = the pooled map (split16 records, as the forward wrote it)
-__global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__restrict__ x, const char *__restrict__ y,
-                                                              const float *__restrict__ gy, int H, int W, int C, int Ho,
-                                                              int Wo, long total, float *__restrict__ gx) {
+// w(o; iy, ix) * g_y[o, c] / y[o, c],  w = hanning3x3 / 16, y = the pooled value.  y is formed HERE from x in float: the
+// forward's pooled map is split16, whose lo half is a subnormal half (absolute step 2^-24) for values below 2^-3 -- a
+// pooled value of 5e-4 read from it is off by up to 2^-14 (6e-5 of the gradient; 1.3 % at the sqrt(1e-12) floor).
+__device__ static inline void l2pool_value4(const float *__restrict__ x, int n, int H, int W, int C, int oy, int ox, int c,
+                                            float (&y)[4]) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int sy = 2 * oy - 1 + ky;
+    if ((unsigned)sy >= (unsigned)H) continue;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int sx = 2 * ox - 1 + kx;
+      if ((unsigned)sx >= (unsigned)W) continue;
+      const float wgt = (ky == 1 ? 0.5f : 0.25f) * (kx == 1 ? 0.5f : 0.25f);
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(x + (((long)n * H + sy) * W + sx) * C + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = fmaf(wgt * v[e], v[e], s[e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) y[e] = sqrtf(s[e] + 1e-12f);
+}
+
+__global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__restrict__ x, const float *__restrict__ gy,
+                                                              int H, int W, int C, int Ho, int Wo, long total,
+                                                              float *__restrict__ gx) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int G = C / 4;
@@ -71,9 +94,10 @@ __global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__res
       const float wgt = wy * ((ix & 1) ? 0.25f : 0.5f);
       const long o = ((long)n * Ho + oy) * Wo + ox;
       const f32x4 gv = *reinterpret_cast<const f32x4 *>(gy + o * C + c);
-      const char *rec = y + o * (long)C * 4;
+      float yv[4];
+      l2pool_value4(x, n, H, W, C, oy, ox, c, yv);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] += wgt * gv[e] / split16_value(rec, c + e);
+      for (int e = 0; e < 4; ++e) acc[e] += wgt * gv[e] / yv[e];
     }
   }
   const long xi = (((long)n * H + iy) * W + ix) * C + c;
@@ -127,12 +151,11 @@ int relu_mask_split16(const float *g, const void *act, int act_split, long npix,
   return check_launch("relu_mask_split16");
 }
 
-int l2pool_backward(const float *x, const void *y_split16, const float *gy, int n, int H, int W, int C, float *gx,
-                    hipStream_t st) {
+int l2pool_backward(const float *x, const void * /*y_split16: not read, see the kernel*/, const float *gy, int n, int H,
+                    int W, int C, float *gx, hipStream_t st) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const long total = (long)n * H * W * (C / 4);
-  l2pool_backward_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(x, static_cast<const char *>(y_split16), gy,
-                                                                                H, W, C, Ho, Wo, total, gx);
+  l2pool_backward_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(x, gy, H, W, C, Ho, Wo, total, gx);
   return check_launch("l2pool_backward");
 }
 

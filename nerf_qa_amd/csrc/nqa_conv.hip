@@ -186,7 +186,11 @@ __host__ __device__ inline int lds_swz(int r) {
 // consecutive stages per kernel row -- [hi: 3 taps][lo: 3 taps] -- that contract the SAME activation rows into the
 // same accumulators; nothing but the stage index -> (chunk, kernel row) map changes, and the epilogue multiplies by the
 // layer's exact power-of-two 1/scale (the weights are packed times 2^k so that lo is a normal half).
-template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16, int NTERM = 1>
+// LOACC (f32s only; the data-gradient convolutions of nqa_backward.hip): the two cross terms al*bh and ah*bl, 2^-11 of the
+// main one, go to an accumulator of their own and are added once at the end.  The main accumulator is then rounded once
+// per k-step instead of three times -- its rounding is what a 4608-term float sum loses (2.0e-6 of the largest output at
+// 512 input channels with one accumulator; the operands themselves are good for 8e-7).
+template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16, int NTERM = 1, bool LOACC = false>
 __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
     const typename P::T *__restrict__ in, const char *__restrict__ wpk, const float *__restrict__ bias,
     typename P::T *__restrict__ out, int H, int W, int Cin, int Cout, int tiles_x, int out_split, float floor_v) {
@@ -304,6 +308,16 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
     for (int j = 0; j < WM_T; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  static_assert(!LOACC || (P::SPLIT && !M16), "LOACC: the split-f16 products only");
+  f32x16 acc_lo[LOACC ? WN_T : 1][LOACC ? WM_T : 1];
+  if constexpr (LOACC) {
+#pragma unroll
+    for (int i = 0; i < WN_T; ++i)
+#pragma unroll
+      for (int j = 0; j < WM_T; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc_lo[i][j][r] = 0.f;
+  }
   // M16: the wave's WN_T x WM_T tiles of 32x32 as 2WN_T x 2WM_T tiles of 16x16 (4 accumulators each);
   // lane = (l15: row of the A fragment / column of the B fragment, c4: 16-byte k-chunk of the row)
   const int l15 = lane & 15, c4 = lane >> 4;
@@ -439,10 +453,11 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
 #pragma unroll
           for (int i = 0; i < WN_T; ++i)
 #pragma unroll
-            for (int j = 0; j < WM_T; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                  __builtin_bit_cast(f16x8, term == 0 ? al[i] : ah[i]),
-                  __builtin_bit_cast(f16x8, term == 1 ? bl[j] : bh[j]), acc[i][j], 0, 0, 0);
+            for (int j = 0; j < WM_T; ++j) {
+              f32x16 &c = (LOACC && term < 2) ? acc_lo[LOACC ? i : 0][LOACC ? j : 0] : acc[i][j];
+              c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, term == 0 ? al[i] : ah[i]),
+                                                         __builtin_bit_cast(f16x8, term == 1 ? bl[j] : bh[j]), c, 0, 0, 0);
+            }
       };
       u32x4 ahA[WN_T], alA[WN_T], bhA[WM_T], blA[WM_T], ahB[WN_T], alB[WN_T], bhB[WM_T], blB[WM_T];
       load_split(0, ahA, alA, bhA, blA);
@@ -483,6 +498,12 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
   }
 #endif
 
+  if constexpr (LOACC) {
+#pragma unroll
+    for (int i = 0; i < WN_T; ++i)
+#pragma unroll
+      for (int j = 0; j < WM_T; ++j) acc[i][j] += acc_lo[i][j];
+  }
   // ---- epilogue: bias + ReLU, staged through LDS so the tile leaves as whole pixel records ----
   // acc[i][j][r]: channel = 8*(r>>2) + 4*h + (r&3) of row tile i, pixel = lane&31 of column tile j:
   // a lane owns 4 consecutive channels of one pixel, i.e. 8- or 16-byte pieces a whole record
@@ -2397,14 +2418,15 @@ static int launch_conv1_1(const float *x, int n, int H, int W, const char *packe
   return check_launch("conv1_1");
 }
 
-template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16 = (sizeof(typename P::T) == 2), int NTERM = 1>
+template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16 = (sizeof(typename P::T) == 2), int NTERM = 1,
+          bool LOACC = false>
 static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, const char *wpk, const float *bias,
                         void *out, int out_split, hipStream_t st, float floor_v = 0.f) {
   typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
   static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
   std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
   if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) {
       set_error("conv3x3_igemm: cannot raise the dynamic LDS limit to %d bytes", G::LDS_BYTES);
       return NQA_E_LAUNCH;
@@ -2414,7 +2436,7 @@ static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, 
   const int tiles_x = cdiv(W, TW), tiles_y = cdiv(H, G::TH);
   dim3 grid(tiles_x * tiles_y, n, cout / G::BN);
   TimedLaunch t(NQA_K_CONV, st);
-  conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM><<<grid, G::THREADS, G::LDS_BYTES, st>>>(
+  conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC><<<grid, G::THREADS, G::LDS_BYTES, st>>>(
       reinterpret_cast<const typename P::T *>(in), wpk, bias, reinterpret_cast<typename P::T *>(out), H, W, cin, cout,
       tiles_x, out_split, floor_v);
   return check_launch("conv3x3_igemm");
@@ -2810,11 +2832,11 @@ int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout
   const float fl = relu ? 0.f : -INFINITY;
   const bool narrow = W <= 16;
   if (cout % 128 == 0) {
-    return narrow ? launch_igemm<PrecF32S, 2, 2, 2, 2, 16>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
-                  : launch_igemm<PrecF32S, 2, 2, 2, 2, 32>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
+    return narrow ? launch_igemm<PrecF32S, 2, 2, 2, 2, 16, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
+                  : launch_igemm<PrecF32S, 2, 2, 2, 2, 32, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
   }
-  return narrow ? launch_igemm<PrecF32S, 1, 4, 2, 2, 16, false>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
-                : launch_igemm<PrecF32S, 1, 4, 2, 2, 32, false>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
+  return narrow ? launch_igemm<PrecF32S, 1, 4, 2, 2, 16, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
+                : launch_igemm<PrecF32S, 1, 4, 2, 2, 32, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
 }
 
 int conv1_1_blob(const float *x, int n, int H, int W, const void *packed, int blob_prec, int kprec, void *out,

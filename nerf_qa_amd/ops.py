@@ -530,7 +530,8 @@ def relu_mask_split16(g: torch.Tensor, act: torch.Tensor, act_is_split16: bool) 
 
 
 def l2pool_backward(tap: torch.Tensor, pooled_split16: torch.Tensor, g_pooled: torch.Tensor, g_tap: torch.Tensor) -> None:
-    """g_tap += d(L2-pool)/d(tap) applied to g_pooled; tap, g_tap float (n,H,W,C); pooled_split16, g_pooled (n,Ho,Wo,C)."""
+    """g_tap += d(L2-pool)/d(tap) applied to g_pooled; tap, g_tap float (n,H,W,C); pooled_split16, g_pooled (n,Ho,Wo,C).
+    The kernel forms the pooled value from `tap` in float; `pooled_split16` is only checked for its shape."""
     dev = _need_cuda(tap, pooled_split16, g_pooled, g_tap)
     n, h, w, c = tap.shape
     assert g_tap.shape == tap.shape and g_tap.is_contiguous() and tap.is_contiguous() and tap.dtype == torch.float32

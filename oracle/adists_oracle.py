@@ -58,7 +58,7 @@ def compute_prob(feats, window_size: int = WINDOW):
     for k in range(len(feats) - 1, -1, -1):
         f = feats[k]
         if windowed(f.shape[2], f.shape[3], window_size):
-            win = window_2d(f.shape[1], window_size)
+            win = window_2d(f.shape[1], window_size).to(f.dtype)
             m = _wconv(f, win)
             v = _wconv(f ** 2, win) - m ** 2
             h, w = m.shape[2], m.shape[3]
@@ -108,12 +108,12 @@ def adists_from_feats(feats_x, feats_y, window_size: int = WINDOW, as_loss: bool
     wl = channel_weights(feats_x)
     d = 0
     bsz, _, big_h, big_w = feats_x[0].shape
-    d_map_full = torch.zeros([bsz, big_h, big_w])
+    d_map_full = torch.zeros([bsz, big_h, big_w], dtype=feats_x[0].dtype)
     for k in range(len(CHNS) - 1, -1, -1):
         fx = F.normalize(feats_x[k], dim=(2, 3))
         fy = F.normalize(feats_y[k], dim=(2, 3))
         if windowed(fx.shape[2], fx.shape[3], window_size):
-            win = window_2d(CHNS[k], window_size)
+            win = window_2d(CHNS[k], window_size).to(fx.dtype)
             xm = _wconv(fx, win)
             ym = _wconv(fy, win)
             xv = _wconv(fx ** 2, win) - xm ** 2

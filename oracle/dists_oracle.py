@@ -37,7 +37,7 @@ def hanning_filter() -> torch.Tensor:
 def l2pool(x: torch.Tensor) -> torch.Tensor:
     """sqrt(depthwise3x3_s2_p1(x^2) + 1e-12).  DISTS_pt.py:22-25 (= ADISTS.py:28-31)."""
     c = x.shape[1]
-    filt = hanning_filter()[None, None].repeat(c, 1, 1, 1)
+    filt = hanning_filter().to(x.dtype)[None, None].repeat(c, 1, 1, 1)
     out = F.conv2d(x ** 2, filt, stride=2, padding=1, groups=c)
     return (out + 1e-12).sqrt()
 
@@ -49,8 +49,8 @@ def vgg_pyramid(x: torch.Tensor, convs) -> list:
     image is tap 0; the network input is (x-mean)/std, zero-padded *after*
     normalisation; each later stage starts with an L2-pool.
     """
-    mean = torch.tensor(IMAGENET_MEAN).view(1, -1, 1, 1)
-    std = torch.tensor(IMAGENET_STD).view(1, -1, 1, 1)
+    mean = torch.tensor(IMAGENET_MEAN, dtype=x.dtype).view(1, -1, 1, 1)  # every constant follows the input's dtype,
+    std = torch.tensor(IMAGENET_STD, dtype=x.dtype).view(1, -1, 1, 1)    # so a float64 call runs in float64 throughout
     h = (x - mean) / std
     feats = [x]
     li = 0
@@ -95,8 +95,8 @@ def dists_score(s1, s2, alpha, beta, batch_average=False):
     b = beta.reshape(-1)
     w_sum = a.sum() + b.sum()
     an, bn = a / w_sum, b / w_sum
-    d1 = torch.zeros(s1.shape[0])
-    d2 = torch.zeros(s1.shape[0])
+    d1 = torch.zeros(s1.shape[0], dtype=s1.dtype)
+    d2 = torch.zeros(s1.shape[0], dtype=s1.dtype)
     o = 0
     for c in CHNS:
         d1 = d1 + (an[o:o + c] * s1[:, o:o + c]).sum(1)
