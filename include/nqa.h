@@ -312,6 +312,41 @@ int nqa_l2pool_backward(const float *tap_nhwc, const void *pooled_split16, const
 int nqa_conv1_1_backward(const float *gm_nhwc, const float *w_oihw_dev, int n, int H, int W, float *g_image_nchw,
                          void *stream);
 
+/* ---- DISTS as a loss: the same backward enqueued without one device -> host read (nerf_qa_amd/autograd.py,
+ * pyramid_backward_device / dists_backward).  The chain above is linear in the gradient, and its split16 operands have a
+ * half's range, so the gradient is renormalised by an exact power of two before every layer; here the exponents live
+ * in device memory, PER IMAGE, so the images of a batch never influence one another.
+ *
+ *   nqa_dists_stats_nhwc_backward   the statistics' gradient on the pyramid's own layout: tx, ty dev float NHWC
+ *       (B, H, W, C) taps of the two images, g_s1 / g_s2 dev float, pair b's C values at g + b * g_stride (e.g. the
+ *       tap's columns of the (B, 1475) upstream: g_stride 1475).  Writes gx = dL/dtx and gy = dL/dty (either may be null:
+ *       nothing is computed for it), each times the tap's own ReLU mask (t > 0).  The arithmetic contract of
+ *       nqa_dists_stats_nchw_backward: fp64 sums and coefficients, the affine map centred and combined in fp64, rounded to
+ *       float once, one writer per element, no atomics.  C a power of two in 16..1024, maps 16-byte aligned, H * W <= 2^30.
+ *       Three launches, counted as NQA_K_STATS.
+ *   nqa_grad_exponent               k[i] = the exponent with max|g_i| * 2^k[i] in [128, 256) for image i of g (n images of
+ *       per_image floats each, per_image % 4 == 0), 0 where that maximum is 0 or not finite; k_total[i] += k[i] when
+ *       k_total is not null.  Two launches (NQA_K_POOL).
+ *   nqa_relu_mask_split16_scaled    nqa_relu_mask_split16 of g * 2^k[image];
+ *   nqa_l2pool_backward_scaled      out = g_tap * 2^k_total[image] + d(L2-pool)/d(tap) applied to g_pooled (g_tap: the tap's
+ *       own gradient, brought into the chain's running scale; out may be g_tap);
+ *   nqa_conv1_1_backward_scaled     nqa_conv1_1_backward of g * 2^k[image] * (relu1_1 > 0), times 2^-k_total[image];
+ *       relu1_1_split16: nqa_conv1_1's NQA_PREC_F32S output, or null for no mask.
+ * Power-of-two scaling is exact: each scaled form equals its plain form on operands scaled beforehand, bit for bit. */
+size_t nqa_dists_stats_nhwc_backward_bytes(int B, int H, int W, int C);
+int nqa_dists_stats_nhwc_backward(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C, const float *g_s1,
+                                  const float *g_s2, long g_stride, void *workspace, size_t workspace_bytes, float *gx_nhwc,
+                                  float *gy_nhwc, void *stream);
+size_t nqa_grad_exponent_bytes(int n, long per_image);
+int nqa_grad_exponent(const float *g, int n, long per_image, void *workspace, size_t workspace_bytes, int *k, int *k_total,
+                      void *stream);
+int nqa_relu_mask_split16_scaled(const float *g_nhwc, const void *act_nhwc, int act_is_split16, int n,
+                                 long pixels_per_image, int C, const int *k, void *out_split16, void *stream);
+int nqa_l2pool_backward_scaled(const float *tap_nhwc, const float *g_pooled_nhwc, const float *g_tap_nhwc, const int *k_total,
+                               int n, int H, int W, int C, float *out_nhwc, void *stream);
+int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16, const float *w_oihw_dev, const int *k,
+                                const int *k_total, int n, int H, int W, float *g_image_nchw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

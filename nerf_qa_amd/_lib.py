@@ -72,6 +72,13 @@ _SIGNATURES = {
     "nqa_relu_mask_split16": (_i, [_vp, _vp, _i, C.c_long, _i, _vp, _vp]),
     "nqa_l2pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "nqa_conv1_1_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "nqa_dists_stats_nhwc_backward_bytes": (_sz, [_i, _i, _i, _i]),
+    "nqa_dists_stats_nhwc_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_grad_exponent_bytes": (_sz, [_i, C.c_long]),
+    "nqa_grad_exponent": (_i, [_vp, _i, C.c_long, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_relu_mask_split16_scaled": (_i, [_vp, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
+    "nqa_l2pool_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "nqa_conv1_1_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "nqa_set_conv_variant": (_i, [_i]),
     "nqa_timing_enable": (_i, [_i]),
     "nqa_timing_collect": (_i, [C.POINTER(_i), C.POINTER(C.c_double)]),

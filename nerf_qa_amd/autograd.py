@@ -9,6 +9,12 @@ conv1_1's gradient onto the three image planes.  The per-channel statistics' gra
 map of the two taps with per-(pair, channel) coefficients; those few numbers are evaluated in float64 on the device.
 The alpha/beta weighted sum stays the torch expression of DISTS_pt.py, so autograd chains d(score)/d(S1, S2) into
 this Function and reaches alpha and beta on its own.  No VGG weight receives a gradient (they are frozen, :51-52).
+
+Used as a LOSS (a render x against a fixed frame y, inside an optimisation loop) the backward is dists_backward's loss
+path: only the images that need a gradient are walked back, the statistics' gradient and the chain's power-of-two
+renormalisation are HIP (csrc/nqa_loss_backward.hip, the scaled kernels of csrc/nqa_backward.hip) with per-image exponents
+in device memory, and nothing is read back to the host.  pyramid_backward and _stats_grad are the first form: the
+reference the tests pin, A-DISTS' head, and the baseline of tools/gpu_loss_step_bench.py.
 """
 from __future__ import annotations
 
@@ -133,8 +139,66 @@ def pyramid_backward(module, acts, taps, pooled, g_taps):
 
 
 @torch.no_grad()
-def dists_backward(module, x, y, g1, g2):
-    """(dL/dx, dL/dy) given dL/dS1, dL/dS2 (each (B, 1475)) for the pairs (x, y), float32 (B,3,H,W) on the GPU."""
+def pyramid_taps(module, imgs):
+    """The five float NHWC taps of `imgs` by pyramid_keep's own launches, keeping nothing else: what the statistics need of
+    an image that takes no gradient.  (The same kernels as pyramid_keep on purpose: the fused forward of ops.vgg_pyramid
+    runs stage 1 in another kernel and agrees with these to a summation order only, and the gradient of a pair must
+    not depend on whether its partner asked for one.)"""
+    prec = "f32s"
+    packed = module._packed_weights(imgs.device, prec)
+    inp = ops.conv1_1(imgs, packed, prec)
+    taps = []
+    for l in range(1, 13):
+        inp = ops.conv3x3_relu(inp, l, packed, prec)
+        if l in ops.TAP_LAYERS:
+            taps.append(inp)
+            if l != 12:
+                inp = ops.l2pool(inp, prec)
+    return taps
+
+
+@torch.no_grad()
+def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False):
+    """pyramid_backward with the renormalisation on the device: the exponents are taken per IMAGE by a reduction kernel
+    and read by the scaled forms of the chain's kernels (csrc/nqa_loss_backward.hip, nqa_backward.hip), so nothing comes
+    back to the host between the first and the last launch -- the step can be enqueued ahead, and the gradient of an
+    image does not depend on what else is in the batch.  With one image the exponents are the host path's and the result
+    is pyramid_backward's bit for bit.  masked=True: g_taps already carry their taps' ReLU masks (g * (t > 0))."""
+    blobs, w0 = _backward_blobs(module, taps[0].device)
+    if not masked:  # BEFORE the first exponent is taken (see pyramid_backward)
+        g_taps = [g * (t > 0) for g, t in zip(g_taps, taps)]
+    n, dev = taps[0].shape[0], taps[0].device
+    k = torch.empty(n, dtype=torch.int32, device=dev)   # the exponent of the step, per image
+    K = torch.zeros(n, dtype=torch.int32, device=dev)   # the running total
+    g = g_taps[4].contiguous()
+    ops.grad_exponent(g, k, K)
+    for l in range(12, 0, -1):
+        gm = ops.relu_mask_split16_scaled(g, acts[l], l not in ops.TAP_LAYERS, k)
+        g = ops.conv3x3_split(gm, blobs[l], ops.CONV_CIN[l], relu=False)
+        if l in (2, 4, 7, 10):
+            s = ops.CONV_STAGE[l]
+            g = ops.l2pool_backward_scaled(taps[s - 1], g, g_taps[s - 1], K)  # the tap's own gradient * 2^K + pool gradient
+        ops.grad_exponent(g, k, K)
+    return ops.conv1_1_backward_scaled(g, acts[0], w0, k, K)  # d(ReLU) of relu1_1 and 2^-K inside
+
+
+def _image_stats_grad(x, y, g1, g2, need):
+    """The statistics' gradient of tap 0, the raw NCHW images, through the NCHW kernels of forward_from_feats: the image
+    goes in as map 0 of six, the other five are single zero pixels with zero upstream gradients."""
+    b, dev = x.shape[0], x.device
+    dummy = [torch.zeros((b, 1, 1, 1), dtype=torch.float32, device=dev)] * 5
+    pad = torch.zeros((b, 5), dtype=torch.float32, device=dev)
+    fx, fy = [x] + dummy, [y] + dummy
+    _, _, scratch = ops.dists_stats_nchw(fx, fy, keep_scratch=True)
+    gx, gy = ops.dists_stats_nchw_backward(fx, fy, scratch, torch.cat([g1[:, :3], pad], 1), torch.cat([g2[:, :3], pad], 1),
+                                           [need[0]] + [False] * 5, [need[1]] + [False] * 5)
+    return gx[0], gy[0]
+
+
+@torch.no_grad()
+def _dists_backward_host(module, x, y, g1, g2):
+    """The first form of dists_backward, kept callable as the baseline of tools/gpu_loss_step_bench.py: both images
+    through the chain, the statistics' gradient in torch, the renormalisation read back to the host per layer."""
     b = x.shape[0]
     xy = torch.cat([x, y]).float().contiguous()
     acts, taps, pooled = pyramid_keep(module, xy)
@@ -151,10 +215,57 @@ def dists_backward(module, x, y, g1, g2):
     return gimg[:b] + gx0, gimg[b:] + gy0
 
 
+@torch.no_grad()
+def dists_backward(module, x, y, g1, g2, need=(True, True), host_scaled=False):
+    """(dL/dx, dL/dy) given dL/dS1, dL/dS2 (each (B, 1475)) for the pairs (x, y), float32 (B,3,H,W) on the GPU; None for
+    the side `need` does not ask for.
+
+    Only the images that need a gradient are run through pyramid_keep and the backward chain; the other one (the fixed
+    ground-truth frame of a loss) gives its taps to the statistics and nothing else: half the activations, none of its
+    twelve data-gradient convolutions.  The statistics' gradient is csrc/nqa_loss_backward.hip's (fp64 sums and
+    coefficients, the taps' ReLU masks folded in), the chain is pyramid_backward_device: no host read anywhere, and every
+    pair's gradient is independent of the rest of the batch.  host_scaled=True runs the first form instead (both sides,
+    torch statistics, host-side renormalisation)."""
+    need = (bool(need[0]), bool(need[1]))
+    if host_scaled:
+        gx, gy = _dists_backward_host(module, x, y, g1, g2)
+        return (gx if need[0] else None), (gy if need[1] else None)
+    if not (need[0] or need[1]):
+        return None, None
+    b = x.shape[0]
+    x, y = x.float().contiguous(), y.float().contiguous()
+    g1, g2 = ops._f32c(g1), ops._f32c(g2)
+    if need[0] and need[1]:
+        acts, taps, pooled = pyramid_keep(module, torch.cat([x, y]))
+        tx, ty = [t[:b] for t in taps], [t[b:] for t in taps]
+    elif need[0]:
+        acts, taps, pooled = pyramid_keep(module, x)
+        tx, ty = taps, pyramid_taps(module, y)
+    else:
+        acts, taps, pooled = pyramid_keep(module, y)
+        tx, ty = pyramid_taps(module, x), taps
+    # ---- gradients of the statistics with respect to the taps of the images in the chain, ReLU masks included ----
+    off = 3
+    g_taps = []
+    for t, fx, fy in zip(taps, tx, ty):
+        c = t.shape[-1]
+        g = torch.empty_like(t)  # laid out as `taps`: x's images, then y's, whichever are in the chain
+        out_x = g[:b] if need[0] else None
+        out_y = g[-b:] if need[1] else None
+        ops.dists_stats_nhwc_backward(fx, fy, g1, g2, off, need[0], need[1], out_x, out_y)
+        g_taps.append(g)
+        off += c
+    gx0, gy0 = _image_stats_grad(x, y, g1, g2, need)  # tap 0 = the raw image (NCHW)
+    gimg = pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=True)
+    if need[0] and need[1]:
+        return gimg[:b] + gx0, gimg[b:] + gy0
+    return (gimg + gx0, None) if need[0] else (None, gimg + gy0)
+
+
 class PyramidTaps(torch.autograd.Function):
     """images (n,3,H,W) -> the five tapped maps relu1_2 .. relu5_3 as float NCHW tensors, differentiable in the images
     (ADISTS.forward(as_loss=True) runs forward_once WITH autograd, ADISTS.py:139-141; the frozen VGG weights get no
-    gradient).  Values from the fused f32s forward; backward = pyramid_keep + pyramid_backward."""
+    gradient).  Values from the fused f32s forward; backward = pyramid_keep + pyramid_backward_device."""
 
     @staticmethod
     def forward(ctx, imgs, module):
@@ -173,7 +284,7 @@ class PyramidTaps(torch.autograd.Function):
         acts, taps, pooled = pyramid_keep(ctx.module, imgs)
         g_taps = [(torch.zeros_like(t) if g is None else g.detach().float().permute(0, 2, 3, 1).contiguous())
                   for g, t in zip(grads, taps)]
-        return pyramid_backward(ctx.module, acts, taps, pooled, g_taps), None
+        return pyramid_backward_device(ctx.module, acts, taps, pooled, g_taps), None
 
 
 class DistsSimilarities(torch.autograd.Function):
@@ -190,8 +301,8 @@ class DistsSimilarities(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g1, g2):
         x, y = ctx.saved_tensors
-        gx, gy = dists_backward(ctx.module, x, y, g1.contiguous(), g2.contiguous())
-        return (gx if ctx.needs_input_grad[0] else None), (gy if ctx.needs_input_grad[1] else None), None
+        gx, gy = dists_backward(ctx.module, x, y, g1.contiguous(), g2.contiguous(), need=ctx.needs_input_grad[:2])
+        return gx, gy, None
 
 
 class FeatsSimilarities(torch.autograd.Function):

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
 SOURCES = ["nqa_api.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
-           "nqa_backward.hip", "nqa_stats_backward.hip"]
+           "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]  # the remarks are parsed below: no hand-scheduled kernel may spill
@@ -23,7 +23,9 @@ RESOURCES_BUILD = os.path.join(HERE, "build", "kernel_resources.json")  # what t
 NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_regw_kernel", "conv3x3_regw128_kernel", "conv3x3_regw128_pool_kernel", "conv1_pool_kernel", "conv1_regw_kernel",
               "conv1_fused_kernel", "conv1_tile_kernel", "conv1_split_kernel", "conv1_regw_split_kernel", "conv3x3_regw_split_kernel", "pool_stats_kernel",
               "adists_window_lds_kernel", "adists_window_planar_kernel", "l2pool_kernel", "stats_nhwc_kernel",
-              "stats_coef_kernel", "stats_grad_kernel")
+              "stats_coef_kernel", "stats_grad_kernel", "loss_stats_sums_kernel", "loss_stats_coef_kernel", "loss_stats_grad_kernel",
+              "absmax_partial_kernel", "exponent_finish_kernel", "relu_mask_split16_kernel", "l2pool_backward_kernel",
+              "conv1_1_backward_kernel")
 
 
 def parse_resource_remarks(text: str) -> dict:

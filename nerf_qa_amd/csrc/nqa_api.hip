@@ -1069,4 +1069,98 @@ int nqa_conv1_1_backward(const float *gm_nhwc, const float *w_oihw_dev, int n, i
   return conv1_1_backward(gm_nhwc, w_oihw_dev, n, H, W, g_image_nchw, static_cast<hipStream_t>(stream));
 }
 
+// ---- DISTS as a loss (nqa_loss_backward.hip and the scaled forms of nqa_backward.hip) -------------------------------
+static bool loss_bad_c(int C) { return C < 16 || C > 1024 || C % 16 || 256 % (C / 4); }
+
+size_t nqa_dists_stats_nhwc_backward_bytes(int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0 || loss_bad_c(C) || (long)H * W > (1L << 30)) return 0;
+  return align_up(loss_stats_backward_doubles(B, H * W, C) * sizeof(double), 256);
+}
+
+int nqa_dists_stats_nhwc_backward(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C, const float *g_s1,
+                                  const float *g_s2, long g_stride, void *workspace, size_t workspace_bytes, float *gx_nhwc,
+                                  float *gy_nhwc, void *stream) {
+  if (!tx_nhwc || !ty_nhwc || !g_s1 || !g_s2 || !workspace || (!gx_nhwc && !gy_nhwc) || B <= 0 || B > 65535 || H <= 0 ||
+      W <= 0 || g_stride < C) {
+    set_error("dists_stats_nhwc_backward: bad argument (null pointer, no gradient to write, B %d outside 1..65535, "
+              "%d x %d, or g_stride %ld < C %d)", B, H, W, g_stride, C);
+    return NQA_E_ARG;
+  }
+  if (loss_bad_c(C)) {
+    set_error("dists_stats_nhwc_backward: C %d must be a power of two in 16..1024", C);
+    return NQA_E_SHAPE;
+  }
+  if ((long)H * W > (1L << 30)) {
+    set_error("dists_stats_nhwc_backward: %ld > 2^30 pixels per image", (long)H * W);
+    return NQA_E_SHAPE;
+  }
+  if (((uintptr_t)tx_nhwc | (uintptr_t)ty_nhwc | (uintptr_t)gx_nhwc | (uintptr_t)gy_nhwc) & 15) {
+    set_error("dists_stats_nhwc_backward: the maps must be 16-byte aligned");
+    return NQA_E_ARG;
+  }
+  const size_t need = nqa_dists_stats_nhwc_backward_bytes(B, H, W, C);
+  if (workspace_bytes < need) {
+    set_error("dists_stats_nhwc_backward: workspace %zu < %zu bytes", workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return loss_stats_backward(tx_nhwc, ty_nhwc, B, H * W, C, g_s1, g_s2, g_stride, static_cast<double *>(workspace), gx_nhwc,
+                             gy_nhwc, static_cast<hipStream_t>(stream));
+}
+
+size_t nqa_grad_exponent_bytes(int n, long per_image) {
+  if (n <= 0 || per_image <= 0 || per_image % 4) return 0;
+  return align_up((size_t)n * grad_exponent_nblk(per_image) * sizeof(unsigned), 256);
+}
+
+int nqa_grad_exponent(const float *g, int n, long per_image, void *workspace, size_t workspace_bytes, int *k, int *k_total,
+                      void *stream) {
+  if (!g || !workspace || !k || n <= 0 || n > 65535 || per_image <= 0) {
+    set_error("grad_exponent: bad argument (null pointer, n %d outside 1..65535 or per_image %ld <= 0)", n, per_image);
+    return NQA_E_ARG;
+  }
+  if (per_image % 4 || ((uintptr_t)g & 15)) {
+    set_error("grad_exponent: per_image %ld must be a multiple of 4 and g 16-byte aligned", per_image);
+    return NQA_E_SHAPE;
+  }
+  const size_t need = nqa_grad_exponent_bytes(n, per_image);
+  if (workspace_bytes < need) {
+    set_error("grad_exponent: workspace %zu < %zu bytes", workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return grad_exponent(g, n, per_image, static_cast<unsigned *>(workspace), k, k_total, static_cast<hipStream_t>(stream));
+}
+
+int nqa_relu_mask_split16_scaled(const float *g_nhwc, const void *act_nhwc, int act_is_split16, int n,
+                                 long pixels_per_image, int C, const int *k, void *out_split16, void *stream) {
+  if (!g_nhwc || !act_nhwc || !k || !out_split16 || n <= 0 || pixels_per_image <= 0 || C <= 0 || C % 16) {
+    set_error("relu_mask_split16_scaled: bad argument (null pointer, n %d, %ld pixels, C %d must be a positive multiple of 16)",
+              n, pixels_per_image, C);
+    return NQA_E_ARG;
+  }
+  return relu_mask_split16_scaled(g_nhwc, act_nhwc, act_is_split16, n, pixels_per_image, C, k, out_split16,
+                                  static_cast<hipStream_t>(stream));
+}
+
+int nqa_l2pool_backward_scaled(const float *tap_nhwc, const float *g_pooled_nhwc, const float *g_tap_nhwc, const int *k_total,
+                               int n, int H, int W, int C, float *out_nhwc, void *stream) {
+  if (!tap_nhwc || !g_pooled_nhwc || !g_tap_nhwc || !k_total || !out_nhwc || C <= 0 || C % 16) {
+    set_error("l2pool_backward_scaled: bad argument");
+    return NQA_E_ARG;
+  }
+  if (bad_dims("l2pool_backward_scaled", n, H, W, NQA_PREC_F32, 0)) return NQA_E_ARG;
+  return l2pool_backward_scaled(tap_nhwc, g_pooled_nhwc, g_tap_nhwc, k_total, n, H, W, C, out_nhwc,
+                                static_cast<hipStream_t>(stream));
+}
+
+int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16, const float *w_oihw_dev, const int *k,
+                                const int *k_total, int n, int H, int W, float *g_image_nchw, void *stream) {
+  if (!g_nhwc || !w_oihw_dev || !k || !k_total || !g_image_nchw) {
+    set_error("conv1_1_backward_scaled: null pointer");
+    return NQA_E_ARG;
+  }
+  if (bad_dims("conv1_1_backward_scaled", n, H, W, NQA_PREC_F32, 0)) return NQA_E_ARG;
+  return conv1_1_backward_scaled(g_nhwc, relu1_1_split16, w_oihw_dev, k, k_total, n, H, W, g_image_nchw,
+                                 static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

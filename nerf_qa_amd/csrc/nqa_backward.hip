@@ -20,14 +20,23 @@ __device__ static inline float split16_value(const char *pixel, int c) {  // cha
 }
 
 // out = split16(g * (act > 0)); one thread per (pixel, 4 channels).  act is float (a tapped map) or split16.
+// SCALED: g is multiplied by 2^kexp[image] first (an exact power of two read from device memory: the renormalisation of
+// the loss path, which the host-scaled chain applies as a separate pass over g).
+template <bool SCALED>
 __global__ __launch_bounds__(256) void relu_mask_split16_kernel(const float *__restrict__ g, const void *__restrict__ act,
-                                                                int act_split, long npix, int C, char *__restrict__ out) {
+                                                                int act_split, long npix, int C, long pix_per_image,
+                                                                const int *__restrict__ kexp, char *__restrict__ out) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int G = C / 4;
   if (idx >= npix * G) return;
   const long p = idx / G;
   const int c = (int)(idx - p * G) * 4;
-  const f32x4 gv = *reinterpret_cast<const f32x4 *>(g + p * C + c);
+  f32x4 gv = *reinterpret_cast<const f32x4 *>(g + p * C + c);
+  if constexpr (SCALED) {
+    const int k = kexp[p / pix_per_image];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gv[e] = ldexpf(gv[e], k);
+  }
   float a[4];
   if (act_split) {
     const char *rec = static_cast<const char *>(act) + p * (long)C * 4;
@@ -67,9 +76,13 @@ __device__ static inline void l2pool_value4(const float *__restrict__ x, int n, 
   for (int e = 0; e < 4; ++e) y[e] = sqrtf(s[e] + 1e-12f);
 }
 
+// SCALED: gx_out = gx_in * 2^ktot[image] + pool gradient (gx_in: the tap's own gradient, brought into the running scale
+// of the chain here); otherwise gx_in == gx_out and the pool gradient is added in place.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__restrict__ x, const float *__restrict__ gy,
                                                               int H, int W, int C, int Ho, int Wo, long total,
-                                                              float *__restrict__ gx) {
+                                                              const float *gx_in, const int *__restrict__ ktot,
+                                                              float *gx) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int G = C / 4;
@@ -102,7 +115,12 @@ __global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__res
   }
   const long xi = (((long)n * H + iy) * W + ix) * C + c;
   const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + xi);
-  f32x4 o = *reinterpret_cast<const f32x4 *>(gx + xi);
+  f32x4 o = *reinterpret_cast<const f32x4 *>(gx_in + xi);
+  if constexpr (SCALED) {
+    const int k = ktot[n];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = ldexpf(o[e], k);
+  }
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] += xv[e] * acc[e];
   *reinterpret_cast<f32x4 *>(gx + xi) = o;
@@ -111,8 +129,13 @@ __global__ __launch_bounds__(256) void l2pool_backward_kernel(const float *__res
 // d(conv1_1)/d(normalised image): gimg[n, c, y, x] = sum_{ky,kx,co} gm[n, y+1-ky, x+1-kx, co] * w[co, c, ky, kx], then
 // divided by std[c] (the input normalisation (x - mean) / std, DISTS_pt.py:92).  gm = g * (relu1_1 > 0), float NHWC.
 // One wave per output pixel: lane = output channel co of gm, 27 products per lane, wave sums.
+// SCALED: gm is the UNMASKED gradient; it is multiplied by 2^kexp[image] and masked with relu1_1 > 0 (act0: split16
+// records, or null for no mask) as it is read, and 2^-ktot[image] is taken out of the result.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void conv1_1_backward_kernel(const float *__restrict__ gm, const float *__restrict__ w,
-                                                               int H, int W, long npix, float *__restrict__ gimg) {
+                                                               int H, int W, long npix, const char *__restrict__ act0,
+                                                               const int *__restrict__ kexp, const int *__restrict__ ktot,
+                                                               float *__restrict__ gimg) {
   const int lane = threadIdx.x & 63;
   const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pix >= npix) return;
@@ -129,7 +152,12 @@ __global__ __launch_bounds__(256) void conv1_1_backward_kernel(const float *__re
     for (int kx = 0; kx < 3; ++kx) {
       const int sx = x + 1 - kx;
       if ((unsigned)sx >= (unsigned)W) continue;
-      const float gv = gm[(((long)n * H + sy) * W + sx) * 64 + lane];
+      const long src = ((long)n * H + sy) * W + sx;
+      float gv = gm[src * 64 + lane];
+      if constexpr (SCALED) {
+        gv = ldexpf(gv, kexp[n]);
+        if (act0 && !(split16_value(act0 + src * 256, lane) > 0.f)) gv = 0.f;
+      }
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc[c] = fmaf(gv, w[((lane * 3 + c) * 3 + ky) * 3 + kx], acc[c]);
     }
@@ -140,29 +168,63 @@ __global__ __launch_bounds__(256) void conv1_1_backward_kernel(const float *__re
   if (lane == 0) {
     const float sd[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) gimg[((long)n * 3 + c) * HW + r] = acc[c] / sd[c];
+    for (int c = 0; c < 3; ++c) {
+      float o = acc[c] / sd[c];
+      if constexpr (SCALED) o = ldexpf(o, -ktot[n]);
+      gimg[((long)n * 3 + c) * HW + r] = o;
+    }
   }
 }
 
 int relu_mask_split16(const float *g, const void *act, int act_split, long npix, int C, void *out, hipStream_t st) {
   const long total = npix * (C / 4);
-  relu_mask_split16_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(g, act, act_split, npix, C,
-                                                                                  static_cast<char *>(out));
+  relu_mask_split16_kernel<false><<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(
+      g, act, act_split, npix, C, npix, nullptr, static_cast<char *>(out));
   return check_launch("relu_mask_split16");
+}
+
+int relu_mask_split16_scaled(const float *g, const void *act, int act_split, int n, long pix_per_image, int C,
+                             const int *kexp, void *out, hipStream_t st) {
+  const long npix = (long)n * pix_per_image, total = npix * (C / 4);
+  TimedLaunch t(NQA_K_POOL, st);
+  relu_mask_split16_kernel<true><<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(
+      g, act, act_split, npix, C, pix_per_image, kexp, static_cast<char *>(out));
+  return check_launch("relu_mask_split16_scaled");
 }
 
 int l2pool_backward(const float *x, const void * /*y_split16: not read, see the kernel*/, const float *gy, int n, int H,
                     int W, int C, float *gx, hipStream_t st) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const long total = (long)n * H * W * (C / 4);
-  l2pool_backward_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(x, gy, H, W, C, Ho, Wo, total, gx);
+  l2pool_backward_kernel<false><<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(x, gy, H, W, C, Ho, Wo, total, gx,
+                                                                                       nullptr, gx);
   return check_launch("l2pool_backward");
+}
+
+int l2pool_backward_scaled(const float *x, const float *gy, const float *g_tap, const int *ktot, int n, int H, int W,
+                           int C, float *out, hipStream_t st) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const long total = (long)n * H * W * (C / 4);
+  TimedLaunch t(NQA_K_POOL, st);
+  l2pool_backward_kernel<true><<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(x, gy, H, W, C, Ho, Wo, total, g_tap,
+                                                                                      ktot, out);
+  return check_launch("l2pool_backward_scaled");
 }
 
 int conv1_1_backward(const float *gm, const float *w_oihw, int n, int H, int W, float *gimg, hipStream_t st) {
   const long npix = (long)n * H * W;
-  conv1_1_backward_kernel<<<dim3((unsigned)((npix + 3) / 4)), 256, 0, st>>>(gm, w_oihw, H, W, npix, gimg);
+  conv1_1_backward_kernel<false><<<dim3((unsigned)((npix + 3) / 4)), 256, 0, st>>>(gm, w_oihw, H, W, npix, nullptr,
+                                                                                   nullptr, nullptr, gimg);
   return check_launch("conv1_1_backward");
+}
+
+int conv1_1_backward_scaled(const float *g, const void *act0_split16, const float *w_oihw, const int *kexp,
+                            const int *ktot, int n, int H, int W, float *gimg, hipStream_t st) {
+  const long npix = (long)n * H * W;
+  TimedLaunch t(NQA_K_POOL, st);
+  conv1_1_backward_kernel<true><<<dim3((unsigned)((npix + 3) / 4)), 256, 0, st>>>(
+      g, w_oihw, H, W, npix, static_cast<const char *>(act0_split16), kexp, ktot, gimg);
+  return check_launch("conv1_1_backward_scaled");
 }
 
 }  // namespace nqa

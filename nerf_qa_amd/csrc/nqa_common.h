@@ -259,6 +259,20 @@ int relu_mask_split16(const float *g, const void *act, int act_split, long npix,
 int l2pool_backward(const float *x, const void *y_split16, const float *gy, int n, int H, int W, int C, float *gx,
                     hipStream_t st);
 int conv1_1_backward(const float *gm, const float *w_oihw, int n, int H, int W, float *gimg, hipStream_t st);
+// the same three with the chain's power-of-two renormalisation read from device memory (per image: kexp the exponent
+// of the step, ktot the running total), nqa_backward.hip
+int relu_mask_split16_scaled(const float *g, const void *act, int act_split, int n, long pix_per_image, int C,
+                             const int *kexp, void *out, hipStream_t st);
+int l2pool_backward_scaled(const float *x, const float *gy, const float *g_tap, const int *ktot, int n, int H, int W,
+                           int C, float *out, hipStream_t st);
+int conv1_1_backward_scaled(const float *g, const void *act0_split16, const float *w_oihw, const int *kexp,
+                            const int *ktot, int n, int H, int W, float *gimg, hipStream_t st);
+// ---- the loss path (nqa_loss_backward.hip): statistics' gradient on NHWC taps, renormalisation exponents ----
+size_t loss_stats_backward_doubles(int B, int HW, int C);
+int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,
+                        long g_stride, double *ws, float *gx, float *gy, hipStream_t st);
+int grad_exponent_nblk(long per_image);
+int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
 int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off,
                           int relu, void *out, hipStream_t st);
 int l2pool_to_split16(const void *in_f16, int n, int H, int W, int C, void *out_split16, hipStream_t st);

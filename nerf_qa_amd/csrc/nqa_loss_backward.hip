@@ -1,0 +1,249 @@
+// DISTS as a LOSS (DISTS.forward(x, y, require_grad=True) inside an optimisation, nerf_qa/DISTS_pytorch/DISTS_pt.py:105-108)
+// for gfx950: what the loss path of nerf_qa_amd/autograd.py needs beyond the chain kernels of nqa_backward.hip.
+//
+//   loss_stats_sums_kernel   the five fp64 sums behind DISTS_pt.py:131-139 of a pair of float NHWC taps, per block
+//   loss_stats_coef_kernel   one wave per (pair, channel): folds them (plane_moments, the forward's own fold) into the
+//                            six fp64 numbers {mx, my, a, b, ox, oy} of nqa_stats_backward.hip
+//   loss_stats_grad_kernel   gx = (x > 0) * (ox + a (x - mx) + b (y - my)), gy likewise with x and y swapped: the affine
+//                            map centred and combined in fp64 and rounded to float once, the tap's own ReLU folded in
+//   absmax_partial_kernel    per (image, block) the largest |g| as its bit pattern (which orders like the value)
+//   exponent_finish_kernel   per image: k with max|g| 2^k in [128, 256) (0 for a zero or non-finite maximum), and the
+//                            running total of the chain
+//
+// The statistics' gradient is the NHWC counterpart of stats_coef_kernel + stats_grad_kernel and keeps their arithmetic
+// contract; the exponents replace the host's float(t.abs().max()) of autograd.pyramid_backward, so a loss step enqueues
+// without a single device -> host read.  All of it is HBM-streaming code: 16-byte accesses per lane, one writer per
+// output element, no atomics (bitwise repeatable), and no image of a batch ever meets another in one accumulation.
+#include "nqa_common.h"
+
+namespace nqa {
+
+#define NQA_COEF 6  // coefficient record of one (pair, channel) plane: {mx, my, a, b, ox, oy} (nqa_stats_backward.hip)
+
+// Thread layout shared by the sums and the gradient kernel: G = C / 4 channel groups of 16 bytes, PL = 256 / G pixels
+// side by side; thread (pl, g) walks the pixels p_begin + pl, + PL, ... of the block's range with its four channels.
+
+// grid (nblk, B).  part[((b * nblk + blk) * C + c) * 5 + s], s = {sum x, sum y, sum x^2, sum y^2, sum xy}.
+__global__ __launch_bounds__(256) void loss_stats_sums_kernel(const float *__restrict__ tx, const float *__restrict__ ty,
+                                                              int HW, int C, int ppb, double *__restrict__ part) {
+  __shared__ double red[256 * 4];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
+  const int G = C / 4, PL = 256 / G;
+  const int g = tid % G, pl = tid / G;
+  const int p_begin = blk * ppb;
+  const int p_end = min(HW, p_begin + ppb);
+  const float *px = tx + (size_t)b * HW * C + g * 4;
+  const float *py = ty + (size_t)b * HW * C + g * 4;
+  double s[5][4];
+#pragma unroll
+  for (int q = 0; q < 5; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[q][e] = 0.0;
+#pragma unroll 4
+  for (int p = p_begin + pl; p < p_end; p += PL) {
+    const f32x4 xv = *reinterpret_cast<const f32x4 *>(px + (size_t)p * C);
+    const f32x4 yv = *reinterpret_cast<const f32x4 *>(py + (size_t)p * C);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double x = (double)xv[e], y = (double)yv[e];
+      s[0][e] += x;
+      s[1][e] += y;
+      s[2][e] = fma(x, x, s[2][e]);
+      s[3][e] = fma(y, y, s[3][e]);
+      s[4][e] = fma(x, y, s[4][e]);
+    }
+  }
+  // fold the PL pixel lanes of each channel group, in a fixed order
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[tid * 4 + e] = s[q][e];
+    __syncthreads();
+    if (pl == 0) {
+      for (int j = 1; j < PL; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[q][e] += red[(j * G + g) * 4 + e];
+    }
+    __syncthreads();
+  }
+  if (pl == 0) {
+    double *o = part + (((size_t)b * nblk + blk) * C + g * 4) * 5;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int q = 0; q < 5; ++q) o[e * 5 + q] = s[q][e];
+  }
+}
+
+// grid (cdiv(C, 4), B), 256 threads = 4 waves = 4 channels.  g_s1 / g_s2 point at the tap's first column of pair 0;
+// pair b's row starts g_stride floats further.  coef: plane b * C + c.
+__global__ __launch_bounds__(256) void loss_stats_coef_kernel(const double *__restrict__ part, StageDesc d,
+                                                              const float *__restrict__ g_s1, const float *__restrict__ g_s2,
+                                                              long g_stride, double *__restrict__ coef) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= d.ctot) return;
+  const PlaneMoments m = plane_moments(part, d, b, c, lane);
+  if (lane) return;
+  const double inv = m.inv, mx = m.mx, my = m.my, vx = m.vx, vy = m.vy, cov = m.cov;
+  const double c1 = 1e-6, c2 = 1e-6;
+  const double n1 = 2.0 * mx * my + c1, d1 = mx * mx + my * my + c1;
+  const double ds1_dmx = (2.0 * my * d1 - 2.0 * mx * n1) / (d1 * d1);
+  const double ds1_dmy = (2.0 * mx * d1 - 2.0 * my * n1) / (d1 * d1);
+  const double n2 = 2.0 * cov + c2, d2 = vx + vy + c2;
+  const double ds2_dcov = 2.0 / d2, ds2_dv = -n2 / (d2 * d2);
+  const double g1 = g_s1[(size_t)b * g_stride + c], g2 = g_s2[(size_t)b * g_stride + c];
+  double *o = coef + ((size_t)b * d.ctot + c) * NQA_COEF;
+  o[0] = mx;
+  o[1] = my;
+  o[2] = 2.0 * g2 * ds2_dv * inv;
+  o[3] = g2 * ds2_dcov * inv;
+  o[4] = g1 * ds1_dmx * inv;
+  o[5] = g1 * ds1_dmy * inv;
+}
+
+// grid (nblk, B).  gx / gy: either may be null (nothing is computed for it).
+__global__ __launch_bounds__(256) void loss_stats_grad_kernel(const float *__restrict__ tx, const float *__restrict__ ty,
+                                                              int HW, int C, int ppb, const double *__restrict__ coef,
+                                                              float *__restrict__ gx, float *__restrict__ gy) {
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y, blk = blockIdx.x;
+  const int G = C / 4, PL = 256 / G;
+  const int g = tid % G, pl = tid / G;
+  const int p_begin = blk * ppb;
+  const int p_end = min(HW, p_begin + ppb);
+  double mx[4], my[4], ca[4], cb[4], ox[4], oy[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double *q = coef + ((size_t)b * C + g * 4 + e) * NQA_COEF;
+    mx[e] = q[0];
+    my[e] = q[1];
+    ca[e] = q[2];
+    cb[e] = q[3];
+    ox[e] = q[4];
+    oy[e] = q[5];
+  }
+  const size_t base = (size_t)b * HW * C + g * 4;
+#pragma unroll 4
+  for (int p = p_begin + pl; p < p_end; p += PL) {
+    const size_t at = base + (size_t)p * C;
+    const f32x4 xv = *reinterpret_cast<const f32x4 *>(tx + at);
+    const f32x4 yv = *reinterpret_cast<const f32x4 *>(ty + at);
+    f32x4 ux, uy;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double dx = (double)xv[e] - mx[e], dy = (double)yv[e] - my[e];
+      ux[e] = xv[e] > 0.f ? (float)fma(cb[e], dy, fma(ca[e], dx, ox[e])) : 0.f;
+      uy[e] = yv[e] > 0.f ? (float)fma(cb[e], dx, fma(ca[e], dy, oy[e])) : 0.f;
+    }
+    if (gx) *reinterpret_cast<f32x4 *>(gx + at) = ux;
+    if (gy) *reinterpret_cast<f32x4 *>(gy + at) = uy;
+  }
+}
+
+// ---- the renormalisation exponents ----------------------------------------------------------------------------------
+// |float| as an unsigned integer orders like the value, every NaN above +inf: the maximum needs no float compare.
+// grid (nblk, n); g: n images of `units` 16-byte units each.
+__global__ __launch_bounds__(256) void absmax_partial_kernel(const u32x4 *__restrict__ g, long units,
+                                                             unsigned *__restrict__ part) {
+  __shared__ unsigned red[4];
+  const int img = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
+  const u32x4 *p = g + (size_t)img * units;
+  unsigned m = 0;
+#pragma unroll 4
+  for (long u = (long)blk * 256 + threadIdx.x; u < units; u += (long)nblk * 256) {
+    const u32x4 v = p[u];
+    m = max(max(m, v[0] & 0x7fffffffu), max(v[1] & 0x7fffffffu, max(v[2] & 0x7fffffffu, v[3] & 0x7fffffffu)));
+  }
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(size_t)img * nblk + blk] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+// grid n, one wave per image.  kexp[img] = k; ktot[img] += k when ktot is given (one writer per image).
+__global__ __launch_bounds__(64) void exponent_finish_kernel(const unsigned *__restrict__ part, int nblk,
+                                                             int *__restrict__ kexp, int *__restrict__ ktot) {
+  const int img = blockIdx.x;
+  unsigned m = 0;
+  for (int i = threadIdx.x; i < nblk; i += 64) m = max(m, part[(size_t)img * nblk + i]);
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+  if (threadIdx.x) return;
+  int k = 0;
+  if (m != 0 && m < 0x7f800000u) {
+    // max = f 2^e with f in [0.5, 1) (frexp), from the bits: a normal float's biased exponent - 126; a subnormal one is
+    // m 2^-149 with its highest set bit at 31 - clz(m)
+    const int e = (m >> 23) ? (int)(m >> 23) - 126 : (31 - __clz((int)m)) - 148;
+    k = 8 - e;
+  }
+  kexp[img] = k;
+  if (ktot) ktot[img] += k;
+}
+
+// ---------------------------------------------------------------------------------
+// host launchers
+// ---------------------------------------------------------------------------------
+// blocks per pair of the sums kernel: enough to fill the device, few enough that the fold stays small
+static int loss_sums_nblk(int HW, int C) {
+  const int PL = 256 / (C / 4);
+  const int n = cdiv(HW, PL * 8);
+  return n < 1024 ? n : 1024;
+}
+static int loss_sums_ppb(int HW, int C) {
+  const int PL = 256 / (C / 4);
+  return cdiv(cdiv(HW, loss_sums_nblk(HW, C)), PL) * PL;
+}
+
+size_t loss_stats_backward_doubles(int B, int HW, int C) {
+  const int nblk = cdiv(HW, loss_sums_ppb(HW, C));
+  return (size_t)B * nblk * C * 5 + (size_t)B * C * NQA_COEF;
+}
+
+int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,
+                        long g_stride, double *ws, float *gx, float *gy, hipStream_t st) {
+  const int ppb = loss_sums_ppb(HW, C), nblk = cdiv(HW, ppb);
+  double *part = ws, *coef = ws + (size_t)B * nblk * C * 5;
+  StageDesc d = {};
+  d.nblk[0] = nblk;
+  d.hw[0] = HW;
+  d.c[0] = C;
+  d.nstage = 1;
+  d.ctot = C;
+  int rc;
+  {
+    TimedLaunch t(NQA_K_STATS, st);
+    loss_stats_sums_kernel<<<dim3(nblk, B), 256, 0, st>>>(tx, ty, HW, C, ppb, part);
+    if ((rc = check_launch("loss_stats_sums"))) return rc;
+  }
+  {
+    TimedLaunch t(NQA_K_STATS, st);
+    loss_stats_coef_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, d, g_s1, g_s2, g_stride, coef);
+    if ((rc = check_launch("loss_stats_coef"))) return rc;
+  }
+  const int PL = 256 / (C / 4), gppb = PL * 8;
+  TimedLaunch t(NQA_K_STATS, st);
+  loss_stats_grad_kernel<<<dim3(cdiv(HW, gppb), B), 256, 0, st>>>(tx, ty, HW, C, gppb, coef, gx, gy);
+  return check_launch("loss_stats_grad");
+}
+
+int grad_exponent_nblk(long per_image) {
+  const long n = (per_image / 4 + 256 * 8 - 1) / (256 * 8);
+  return n < 1 ? 1 : n > 512 ? 512 : (int)n;
+}
+
+int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st) {
+  const int nblk = grad_exponent_nblk(per_image);
+  int rc;
+  {
+    TimedLaunch t(NQA_K_POOL, st);
+    absmax_partial_kernel<<<dim3(nblk, n), 256, 0, st>>>(reinterpret_cast<const u32x4 *>(g), per_image / 4, ws);
+    if ((rc = check_launch("absmax_partial"))) return rc;
+  }
+  TimedLaunch t(NQA_K_POOL, st);
+  exponent_finish_kernel<<<n, 64, 0, st>>>(ws, nblk, kexp, ktot);
+  return check_launch("exponent_finish");
+}
+
+}  // namespace nqa

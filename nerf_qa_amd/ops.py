@@ -549,3 +549,95 @@ def conv1_1_backward(gm: torch.Tensor, w0: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
     _call(dev, lib().nqa_conv1_1_backward, ptr(gm), ptr(w0), n, h, w, ptr(out), stream_ptr(dev))
     return out
+
+
+# ---- DISTS as a loss: the same chain without a device -> host read (include/nqa.h, nqa_loss_backward.hip) ----------
+def dists_stats_nhwc_backward(tx: torch.Tensor, ty: torch.Tensor, g_s1: torch.Tensor, g_s2: torch.Tensor, col: int,
+                              need_x: bool = True, need_y: bool = True, out_x: torch.Tensor | None = None,
+                              out_y: torch.Tensor | None = None):
+    """(gx, gy): d(sum g_s1 S1 + g_s2 S2)/d(tx), /d(ty) for one pair of float NHWC taps (B,H,W,C), each times its tap's
+    ReLU mask (t > 0); None where need_x / need_y is False (nothing is computed for it).  g_s1, g_s2: float (B, ctot)
+    upstream gradients, the tap's C columns starting at `col`.  out_x / out_y: where to write (tx's shape), else new."""
+    dev = _need_cuda(tx, ty, g_s1, g_s2)
+    assert tx.dtype == ty.dtype == torch.float32 and tx.is_contiguous() and ty.is_contiguous() and tx.shape == ty.shape
+    assert g_s1.dtype == g_s2.dtype == torch.float32 and g_s1.is_contiguous() and g_s2.is_contiguous()
+    b, h, w, c = tx.shape
+    if g_s1.shape != g_s2.shape or g_s1.dim() != 2 or g_s1.shape[0] != b or col < 0 or col + c > g_s1.shape[1]:
+        raise ValueError(f"expected gradients of shape ({b}, >= {col + c}), got {tuple(g_s1.shape)} / {tuple(g_s2.shape)}")
+    gx = (torch.empty_like(tx) if out_x is None else out_x) if need_x else None
+    gy = (torch.empty_like(ty) if out_y is None else out_y) if need_y else None
+    for g in (gx, gy):
+        assert g is None or (g.shape == tx.shape and g.dtype == torch.float32 and g.is_contiguous())
+    if gx is None and gy is None:
+        return None, None
+    nbytes = lib().nqa_dists_stats_nhwc_backward_bytes(b, h, w, c)
+    if not nbytes:
+        raise _lib.NqaError(f"dists_stats_nhwc_backward: unsupported tap shape {tuple(tx.shape)}")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_dists_stats_nhwc_backward, ptr(tx), ptr(ty), b, h, w, c, ptr(g_s1) + 4 * col, ptr(g_s2) + 4 * col,
+          g_s1.shape[1], ptr(buf), buf.numel(), None if gx is None else ptr(gx), None if gy is None else ptr(gy),
+          stream_ptr(dev))
+    return gx, gy
+
+
+def grad_exponent(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
+    """k[i] (int32, on the device) = the exponent with max|g[i]| * 2^k[i] in [128, 256), 0 where that maximum is 0 or
+    not finite; k_total[i] += k[i].  g: float, image i = g[i].  Nothing comes back to the host."""
+    dev = _need_cuda(g, k)
+    n = g.shape[0]
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
+    assert k_total is None or (k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
+                               and k_total.device == dev)
+    per = g.numel() // n
+    nbytes = lib().nqa_grad_exponent_bytes(n, per)
+    if not nbytes:
+        raise _lib.NqaError(f"grad_exponent: unsupported shape {tuple(g.shape)} (elements per image must be a multiple of 4)")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_grad_exponent, ptr(g), n, per, ptr(buf), buf.numel(), ptr(k), None if k_total is None else ptr(k_total),
+          stream_ptr(dev))
+
+
+def relu_mask_split16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16: bool, k: torch.Tensor) -> torch.Tensor:
+    """relu_mask_split16(g * 2^k[image], act): the exponents (int32, one per image g[i]) are read on the device."""
+    dev = _need_cuda(g, act, k)
+    g = _f32c(g)
+    assert act.dtype == torch.float32 and act.is_contiguous() and act.shape == g.shape
+    n, c = g.shape[0], g.shape[-1]
+    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
+    out = torch.empty_like(g)
+    _call(dev, lib().nqa_relu_mask_split16_scaled, ptr(g), ptr(act), int(act_is_split16), n, g.numel() // (n * c), c, ptr(k),
+          ptr(out), stream_ptr(dev))
+    return out
+
+
+def l2pool_backward_scaled(tap: torch.Tensor, g_pooled: torch.Tensor, g_tap: torch.Tensor, k_total: torch.Tensor) -> torch.Tensor:
+    """g_tap * 2^k_total[image] + d(L2-pool)/d(tap) applied to g_pooled, as a new float (n,H,W,C) tensor."""
+    dev = _need_cuda(tap, g_pooled, g_tap, k_total)
+    n, h, w, c = tap.shape
+    assert tap.dtype == torch.float32 and tap.is_contiguous()
+    assert g_tap.shape == tap.shape and g_tap.dtype == torch.float32 and g_tap.is_contiguous()
+    assert g_pooled.shape == (n, (h + 1) // 2, (w + 1) // 2, c)
+    assert k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
+    out = torch.empty_like(tap)
+    _call(dev, lib().nqa_l2pool_backward_scaled, ptr(tap), ptr(_f32c(g_pooled)), ptr(g_tap), ptr(k_total), n, h, w, c, ptr(out),
+          stream_ptr(dev))
+    return out
+
+
+def conv1_1_backward_scaled(g: torch.Tensor, relu1_1_split16: torch.Tensor | None, w0: torch.Tensor, k: torch.Tensor,
+                            k_total: torch.Tensor) -> torch.Tensor:
+    """conv1_1_backward(g * 2^k[image] * (relu1_1 > 0), w0) * 2^-k_total[image]: float NHWC (n,H,W,64) -> float NCHW
+    (n,3,H,W).  relu1_1_split16: conv1_1's f32s output (None: no mask)."""
+    dev = _need_cuda(g, w0, k, k_total)
+    g, w0 = _f32c(g), _f32c(w0)
+    n, h, w, c = g.shape
+    assert c == 64 and tuple(w0.shape) == (64, 3, 3, 3)
+    assert relu1_1_split16 is None or (relu1_1_split16.shape == g.shape and relu1_1_split16.dtype == torch.float32
+                                       and relu1_1_split16.is_contiguous() and relu1_1_split16.device == dev)
+    for t in (k, k_total):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_conv1_1_backward_scaled, ptr(g), None if relu1_1_split16 is None else ptr(relu1_1_split16), ptr(w0),
+          ptr(k), ptr(k_total), n, h, w, ptr(out), stream_ptr(dev))
+    return out
