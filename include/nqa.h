@@ -347,6 +347,26 @@ int nqa_l2pool_backward_scaled(const float *tap_nhwc, const float *g_pooled_nhwc
 int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16, const float *w_oihw_dev, const int *k,
                                 const int *k_total, int n, int H, int W, float *g_image_nchw, void *stream);
 
+/* ---- windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments;
+ * nqa_window_moments.hip).  x, y: dev float NCHW maps taken as P = B * C independent planes of H x W; the window is the
+ * normalised 21-tap Gaussian of sigma 7 as an outer product, valid correlation: h = H - 20, w = W - 20.
+ *
+ *   nqa_window_moments_forward    out (n, P, h, w) dev float: with y the n = 5 window means E[x], E[y], E[x^2], E[y^2],
+ *       E[xy], with y null the n = 2 means E[x], E[x^2].  One launch; the products never reach memory.
+ *   nqa_window_moments_backward   g0 .. g4: upstream gradients of those five maps, each (P, h, w) dev float, null = zero.
+ *       gx = W^T g0 + 2 x W^T g2 + y W^T g4 and gy = W^T g1 + 2 y W^T g3 + x W^T g4 (P, H, W), W^T the transposed
+ *       correlation as a gather: a pixel sums over the windows that contain it, so no term of any other window can reach
+ *       it.  gx or gy null: that side is skipped, the other is bit-identical to the two-sided call.  With y null (the
+ *       moments of x alone) g1, g3, g4 and gy must be null.  One launch, one writer per element, no atomics.
+ * Both need no workspace, read nothing back to the host and are counted as NQA_K_ADISTS.  Where W % 4 == 0 rows move
+ * as 16-byte accesses and every pointer must be 16-byte aligned (a contiguous batch or channel slice of an aligned
+ * tensor always is); for any other W nothing beyond a float's alignment is asked.  NQA_E_ARG: null pointer, P <= 0,
+ * misaligned with W % 4 == 0; NQA_E_SHAPE: H or
+ * W below 21 (no window fits: the head's global branch), H > 2^20, or more than 2^30 pixels per plane. */
+int nqa_window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, void *stream);
+int nqa_window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *g0, const float *g1,
+                                const float *g2, const float *g3, const float *g4, float *gx, float *gy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

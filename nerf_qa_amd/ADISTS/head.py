@@ -5,10 +5,11 @@ through the texture probabilities (:71-100, from x only), the entropy channel we
 and the windowed T / S terms (:165-191) back to both images.  The scoring path (`as_loss=False`, no gradient: every
 caller in the reference) is the fused HIP kernel `nqa_adists_forward`; THIS file is used only when a gradient is actually
 asked for: the tapped maps come from `autograd.PyramidTaps` (HIP forward, HIP backward through the 13 conv layers) and the
-head below is plain torch on the GPU, so autograd differentiates it.  It is written for that purpose -- the 21 x 21
-Gaussian window as two 1-D passes, the fall-back to global moments where a map is smaller than the window (the
-reference's try / except) decided from the shape -- and is checked against float64 autograd over the CPU oracle
-(tests/test_gpu_backward.py)."""
+head below is torch on the GPU, so autograd differentiates it.  It is written for that purpose -- the fall-back to
+global moments where a map is smaller than the window (the reference's try / except) decided from the shape -- and is
+checked against float64 autograd over the CPU oracle (tests/test_gpu_backward.py).  The 21 x 21 Gaussian window means,
+the only part that touches every value of every map 42 times, are `autograd.WindowMoments` on float32 CUDA maps (one
+HIP launch forward, one backward: csrc/nqa_window_moments.hip) and two 1-D passes of shifted slices everywhere else."""
 from __future__ import annotations
 
 import math
@@ -47,6 +48,23 @@ def _window_mean(t: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _moments(x: torch.Tensor, y, window_size: int, window_impl: str):
+    """Window means (E[x], E[x^2]) of x alone or (E[x], E[y], E[x^2], E[y^2], E[xy]) of a pair.  "auto": the HIP kernels
+    where they apply (float32 CUDA maps, the library's 21-tap window), the slices of _window_mean otherwise (CPU tensors,
+    float64, other window sizes); "slices": always those."""
+    if window_impl not in ("auto", "slices"):
+        raise ValueError(f"window_impl must be 'auto' or 'slices', got {window_impl!r}")
+    hip = (window_impl == "auto" and window_size == 21 and x.is_cuda and x.dtype == torch.float32
+           and (y is None or (y.is_cuda and y.dtype == torch.float32)))
+    if hip:
+        from ..autograd import WindowMoments
+        return WindowMoments.apply(x, y)
+    g = gauss_1d(window_size, x)
+    if y is None:
+        return _window_mean(x, g), _window_mean(x * x, g)
+    return _window_mean(x, g), _window_mean(y, g), _window_mean(x * x, g), _window_mean(y * y, g), _window_mean(x * y, g)
+
+
 def _windowed(t: torch.Tensor, window_size: int) -> bool:
     return t.shape[2] >= window_size and t.shape[3] >= window_size  # (where F.conv2d would raise: ADISTS.py:79,91)
 
@@ -57,15 +75,14 @@ def _minmax(p: torch.Tensor) -> torch.Tensor:
     return (p - lo) / (hi - lo + C0)
 
 
-def texture_probabilities(feats: Sequence[torch.Tensor], window_size: int) -> List[torch.Tensor]:
+def texture_probabilities(feats: Sequence[torch.Tensor], window_size: int, window_impl: str = "auto") -> List[torch.Tensor]:
     """ps of every stage, coarse to fine products (ADISTS.py:71-100); feats = [image, relu1_2 .. relu5_3] of x."""
     prod = torch.ones_like(feats[0][:, 0:1])
     out = []
     for f in reversed(feats):
         if _windowed(f, window_size):
-            g = gauss_1d(window_size, f)
-            m = _window_mean(f, g)
-            v = _window_mean(f * f, g) - m * m
+            m, m2 = _moments(f, None, window_size, window_impl)
+            v = m2 - m * m
             gamma = (v / (m + C0)).mean(dim=1, keepdim=True)
             z = (gamma - gamma.mean(dim=(2, 3), keepdim=True)) / (gamma.std(dim=(2, 3), keepdim=True) + C0)
             ps = _minmax(torch.sigmoid(z))
@@ -97,19 +114,20 @@ def channel_weights(feats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
     return list(torch.split(w, [f.shape[1] for f in feats], dim=1))
 
 
-def adists_d(feats_x: Sequence[torch.Tensor], feats_y: Sequence[torch.Tensor], window_size: int = 21) -> torch.Tensor:
-    """D (B,) of ADISTS.py:147-191 from the two pyramids (lists of six NCHW maps); the module returns 1 - D or 1 - mean(D)."""
-    ps_x = texture_probabilities(feats_x, window_size)
+def adists_d(feats_x: Sequence[torch.Tensor], feats_y: Sequence[torch.Tensor], window_size: int = 21,
+             window_impl: str = "auto") -> torch.Tensor:
+    """D (B,) of ADISTS.py:147-191 from the two pyramids (lists of six NCHW maps); the module returns 1 - D or 1 - mean(D).
+    window_impl="slices" forces the shifted-slice window means on every device (see _moments)."""
+    ps_x = texture_probabilities(feats_x, window_size, window_impl)
     wl = channel_weights(feats_x)
     d = 0
     for k in range(len(feats_x) - 1, -1, -1):
         fx, fy = F.normalize(feats_x[k], dim=(2, 3)), F.normalize(feats_y[k], dim=(2, 3))
         if _windowed(fx, window_size):
-            g = gauss_1d(window_size, fx)
-            xm, ym = _window_mean(fx, g), _window_mean(fy, g)
-            xv = _window_mean(fx * fx, g) - xm * xm
-            yv = _window_mean(fy * fy, g) - ym * ym
-            cov = _window_mean(fx * fy, g) - xm * ym
+            xm, ym, xx, yy, xy = _moments(fx, fy, window_size, window_impl)
+            xv = xx - xm * xm
+            yv = yy - ym * ym
+            cov = xy - xm * ym
         else:
             xm, ym = fx.mean(dim=(2, 3), keepdim=True), fy.mean(dim=(2, 3), keepdim=True)
             xv = ((fx - xm) ** 2).mean(dim=(2, 3), keepdim=True)

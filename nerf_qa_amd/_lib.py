@@ -79,6 +79,8 @@ _SIGNATURES = {
     "nqa_relu_mask_split16_scaled": (_i, [_vp, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
     "nqa_l2pool_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "nqa_conv1_1_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "nqa_window_moments_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "nqa_window_moments_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nqa_set_conv_variant": (_i, [_i]),
     "nqa_timing_enable": (_i, [_i]),
     "nqa_timing_collect": (_i, [C.POINTER(_i), C.POINTER(C.c_double)]),

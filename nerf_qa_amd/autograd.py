@@ -329,3 +329,27 @@ class FeatsSimilarities(torch.autograd.Function):
             return (None,) * 12
         gx, gy = ops.dists_stats_nchw_backward(f[:6], f[6:], ctx.scratch, g1, g2, need[:6], need[6:])
         return tuple(None if g is None else g.to(dt) for g, dt in zip(gx + gy, ctx.dtypes))
+
+
+class WindowMoments(torch.autograd.Function):
+    """(x, y | None) -> the 21 x 21 Gaussian window means of NCHW maps (ops.window_moments: two maps of x alone, five of a
+    pair), differentiable in both: what the A-DISTS head is built from (ADISTS.py:79-86, :165-175).  Saves x and y only;
+    the backward is one launch of csrc/nqa_window_moments.hip for the sides that need a gradient, in which no window's
+    term can reach a pixel outside that window.  Gradients come back in the inputs' dtype and shape."""
+
+    @staticmethod
+    def forward(ctx, x, y=None):
+        fx, fy = ops._f32c(x), None if y is None else ops._f32c(y)
+        ctx.save_for_backward(fx, fy)
+        ctx.set_materialize_grads(False)  # an unused map's gradient stays None: its pass of the backward is skipped
+        ctx.dtypes = (x.dtype, None if y is None else y.dtype)
+        return ops.window_moments(fx, fy)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        fx, fy = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], fy is not None and ctx.needs_input_grad[1])
+        if not any(need):
+            return None, None
+        gx, gy = ops.window_moments_backward(fx, fy, grads, need)
+        return (None if gx is None else gx.to(ctx.dtypes[0])), (None if gy is None else gy.to(ctx.dtypes[1]))

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
 SOURCES = ["nqa_api.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
-           "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip"]
+           "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_window_moments.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]  # the remarks are parsed below: no hand-scheduled kernel may spill
@@ -25,7 +25,7 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_regw_kernel", "conv3x3_regw128_ke
               "adists_window_lds_kernel", "adists_window_planar_kernel", "l2pool_kernel", "stats_nhwc_kernel",
               "stats_coef_kernel", "stats_grad_kernel", "loss_stats_sums_kernel", "loss_stats_coef_kernel", "loss_stats_grad_kernel",
               "absmax_partial_kernel", "exponent_finish_kernel", "relu_mask_split16_kernel", "l2pool_backward_kernel",
-              "conv1_1_backward_kernel")
+              "conv1_1_backward_kernel", "window_moments_fwd_kernel", "window_moments_bwd_kernel")
 
 
 def parse_resource_remarks(text: str) -> dict:
@@ -71,10 +71,11 @@ def check_no_scratch(res: dict) -> list:
 # nqa_adists.hip: the window kernels' tap arithmetic is written as scalar float FMAs with literal-constant weights
 # (v_fmac_f32 with a 32-bit immediate); the SLP vectorizer would pair them into v_pk_*_f32, which issue at half
 # rate on gfx950 and need a {w, w} register pair built per tap
+# nqa_window_moments.hip: the same tap arithmetic (literal weights, one scalar FMA per tap), for the same reason
 # nqa_conv_pool.hip: the fused epilogue is written as slices of a few scalar float instructions per k-step; SLP would
 # pair instructions of DIFFERENT slices (packed f32 ops, packed conversions) and drag them out of the MFMAs' shadow
 FILE_FLAGS = {"nqa_adists.hip": ["-fno-slp-vectorize"], "nqa_conv_pool.hip": ["-fno-slp-vectorize"],
-              "nqa_conv1_pool.hip": ["-fno-slp-vectorize"]}
+              "nqa_conv1_pool.hip": ["-fno-slp-vectorize"], "nqa_window_moments.hip": ["-fno-slp-vectorize"]}
 
 
 def source_hash() -> str:

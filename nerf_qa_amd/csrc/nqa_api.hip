@@ -1163,4 +1163,56 @@ int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16
                                  static_cast<hipStream_t>(stream));
 }
 
+// ---- windowed moments of the A-DISTS head (nqa_window_moments.hip) ---------------------------------------------------
+static int window_bad_shape(const char *who, int P, int H, int W) {
+  if (P <= 0) {
+    set_error("%s: bad argument (P %d <= 0)", who, P);
+    return NQA_E_ARG;
+  }
+  if (H < 21 || W < 21) {
+    set_error("%s: %d x %d is smaller than the 21 x 21 window", who, H, W);
+    return NQA_E_SHAPE;
+  }
+  return 0;
+}
+// (checked after the pointers' alignment, so that what refuses a call can be told apart without a launch)
+static int window_too_large(const char *who, int H, int W) {
+  if (H > (1 << 20) || (long)H * W > (1L << 30)) {
+    set_error("%s: %d x %d: H > 2^20 or more than 2^30 pixels per plane", who, H, W);
+    return NQA_E_SHAPE;
+  }
+  return 0;
+}
+
+int nqa_window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, void *stream) {
+  if (!x || !out) {
+    set_error("window_moments_forward: bad argument (null pointer)");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_bad_shape("window_moments_forward", P, H, W)) return rc;
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15)) {  // (rows move as 16-byte accesses then)
+    set_error("window_moments_forward: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_too_large("window_moments_forward", H, W)) return rc;
+  return window_moments_forward(x, y, P, H, W, out, static_cast<hipStream_t>(stream));
+}
+
+int nqa_window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *g0, const float *g1,
+                                const float *g2, const float *g3, const float *g4, float *gx, float *gy, void *stream) {
+  if (!x || (!gx && !gy) || (!y && (g1 || g3 || g4 || gy))) {
+    set_error("window_moments_backward: bad argument (null pointer, no gradient to write, or y's terms given without y)");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_bad_shape("window_moments_backward", P, H, W)) return rc;
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)g3 |
+                      (uintptr_t)g4 | (uintptr_t)gx | (uintptr_t)gy) & 15)) {
+    set_error("window_moments_backward: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_too_large("window_moments_backward", H, W)) return rc;
+  const float *const g[5] = {g0, g1, g2, g3, g4};
+  return window_moments_backward(x, y, P, H, W, g, gx, gy, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -273,6 +273,11 @@ int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, 
                         long g_stride, double *ws, float *gx, float *gy, hipStream_t st);
 int grad_exponent_nblk(long per_image);
 int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
+// ---- windowed moments of the A-DISTS head and their backward (nqa_window_moments.hip) ----
+// out: moment m of plane p at (m * P + p) * h * w (five moments with y, two without); g[q] null = zero
+int window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st);
+int window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
+                            float *gy, hipStream_t st);
 int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off,
                           int relu, void *out, hipStream_t st);
 int l2pool_to_split16(const void *in_f16, int n, int H, int W, int C, void *out_split16, hipStream_t st);

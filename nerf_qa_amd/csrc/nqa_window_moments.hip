@@ -1,0 +1,300 @@
+// Windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments) for gfx950:
+// the 21 x 21 Gaussian window means E[x], E[y], E[x^2], E[y^2], E[xy] of float NCHW maps, and their backward.
+//
+//   window_moments_fwd_kernel   one launch reads x (and y) once and writes the two (five) maps of window means; the
+//                               products are formed in registers
+//   window_moments_bwd_kernel   gx = W^T g0 + 2 x W^T g2 + y W^T g4, gy = W^T g1 + 2 y W^T g3 + x W^T g4, W^T the
+//                               transposed (full) correlation written as a GATHER: every input pixel sums over the windows
+//                               that contain it
+//
+// Both work on P = B * C independent planes and share one shape.  A block of 256 threads owns a 24 x 64 tile of what it
+// writes and stages the 44 x 84 halo tile it needs in LDS (zero outside the map).  A vertical pass then forms the 21-tap
+// column sums of the tile (a thread per column and group of 8 rows: 28 LDS reads slide through 8 accumulators), a
+// horizontal pass the 21-tap row sums of those (a thread per 4 adjacent columns: six 16-byte LDS reads slide through 4
+// accumulators).  The transposed correlation of the backward is the same pair of passes on the upstream map padded with
+// 20 zeros on every side, because the window is symmetric.  One moment is processed at a time, so the column sums need a
+// single 24 x 88 plane of LDS and few registers.
+//
+// Every tap is one scalar float FMA with a literal weight (see kG in nqa_adists.hip for why), summed in tap order.
+// One writer per element, no atomics: bitwise repeatable.  In the backward every intermediate that feeds pixel (r, c)
+// is a sum over windows (i, j) with i in [r-20, r], j in [c-20, c], all of which contain the pixel: a term of a window
+// that does not contain a pixel can never reach it, whatever its size (head.py divides by window means that are zero on
+// dead regions of a channel, so upstream values of 1e12 sit next to ordinary ones).  The side that is not asked for
+// (gx or gy null) costs nothing, and the other side's instructions do not depend on it: it is bit-identical.
+#include <math.h>
+
+#include "nqa_common.h"
+
+namespace nqa {
+
+static constexpr int kWin = 21;
+static constexpr int kTH = 24, kTW = 64;                          // tile of outputs
+static constexpr int kIH = kTH + kWin - 1, kIW = kTW + kWin - 1;  // 44 x 84 halo tile
+static constexpr int kVS = 88;                                    // row stride of the column sums (16-byte rows)
+static constexpr int kVRows = 8;                                  // rows per thread of the vertical pass
+static constexpr int kHItems = kTH * (kTW / 4);                   // (row, 4 columns) items of the horizontal pass
+static_assert(kTH % kVRows == 0 && kIW * (kTH / kVRows) <= 256 && kHItems <= 512 && kIW % 4 == 0 && kIW <= kVS, "tile shape");
+
+// gaussian(21, 7) as head.gauss_1d builds it, the literals of nqa_adists.hip's kG; window_gauss_ok() recomputes the
+// taps on the host and both entry points refuse to launch if they disagree.
+static constexpr float kG[kWin] = {
+    0x1.8453aep-6f, 0x1.d76892p-6f, 0x1.185a34p-5f, 0x1.46b8bap-5f, 0x1.75117ap-5f, 0x1.a16246p-5f, 0x1.c987c2p-5f,
+    0x1.eb6810p-5f, 0x1.02907ep-4f, 0x1.0a9a20p-4f, 0x1.0d5620p-4f, 0x1.0a9a20p-4f, 0x1.02907ep-4f, 0x1.eb6810p-5f,
+    0x1.c987c2p-5f, 0x1.a16246p-5f, 0x1.75117ap-5f, 0x1.46b8bap-5f, 0x1.185a34p-5f, 0x1.d76892p-6f, 0x1.8453aep-6f};
+static_assert(kG[0] == kG[20] && kG[4] == kG[16] && kG[9] == kG[11], "the transposed pass relies on a symmetric window");
+
+// the averaged quantity Q of one pixel: x, y, x^2, y^2, xy
+template <int Q>
+__device__ inline float moment_term(float x, float y) {
+  return Q == 0 ? x : Q == 1 ? y : Q == 2 ? x * x : Q == 3 ? y * y : x * y;
+}
+
+// Stage the halo tile whose first element is (r0, c0) of the nr x nc plane `src` into LDS, zero where it leaves the plane.
+// c0 is a multiple of 4; with nc a multiple of 4 (vec) and a 16-byte aligned plane every 4-column chunk is wholly inside
+// or wholly outside and is moved as one 16-byte access.
+__device__ inline void stage_tile(const float *__restrict__ src, int nr, int nc, int r0, int c0, bool vec, float *tile) {
+  if (vec) {
+    for (int i = threadIdx.x; i < kIH * (kIW / 4); i += 256) {
+      const int lr = i / (kIW / 4), lc = (i % (kIW / 4)) * 4;
+      const int r = r0 + lr, c = c0 + lc;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (r >= 0 && r < nr && c >= 0 && c < nc) v = *reinterpret_cast<const f32x4 *>(src + (size_t)r * nc + c);
+      *reinterpret_cast<f32x4 *>(tile + lr * kIW + lc) = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < kIH * kIW; i += 256) {
+      const int lr = i / kIW, lc = i % kIW;
+      const int r = r0 + lr, c = c0 + lc;
+      tile[i] = (r >= 0 && r < nr && c >= 0 && c < nc) ? src[(size_t)r * nc + c] : 0.f;
+    }
+  }
+}
+
+// Column sums of moment Q: V[o][c] = sum_k kG[k] * term(tile[o + k][c]), o < 24, c < 84.
+template <int Q>
+__device__ inline void vertical_pass(const float *sx, const float *sy, float *V) {
+  const int t = threadIdx.x;
+  if (t >= kIW * (kTH / kVRows)) return;
+  const int col = t % kIW, row0 = (t / kIW) * kVRows;
+  float acc[kVRows];
+#pragma unroll
+  for (int r = 0; r < kVRows + kWin - 1; ++r) {
+    const float xv = (Q != 1 && Q != 3) ? sx[(row0 + r) * kIW + col] : 0.f;
+    const float yv = (Q == 1 || Q == 3 || Q == 4) ? sy[(row0 + r) * kIW + col] : 0.f;
+    const float v = moment_term<Q>(xv, yv);
+#pragma unroll
+    for (int o = 0; o < kVRows; ++o) {
+      const int k = r - o;
+      if (k == 0) acc[o] = kG[0] * v;
+      else if (k > 0 && k < kWin) acc[o] = fmaf(kG[k], v, acc[o]);
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < kVRows; ++o) V[(row0 + o) * kVS + col] = acc[o];
+}
+
+// Row sums for item (row, 4 columns from col4): out[e] = sum_k kG[k] * V[row][col4 + e + k].
+__device__ inline void horizontal_item(const float *V, int row, int col4, float (&out)[4]) {
+  float v[kWin + 3];
+#pragma unroll
+  for (int j = 0; j < (kWin + 3) / 4; ++j) {
+    const f32x4 q = *reinterpret_cast<const f32x4 *>(V + row * kVS + col4 + 4 * j);
+    v[4 * j] = q[0];
+    v[4 * j + 1] = q[1];
+    v[4 * j + 2] = q[2];
+    v[4 * j + 3] = q[3];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float a = kG[0] * v[e];
+#pragma unroll
+    for (int k = 1; k < kWin; ++k) a = fmaf(kG[k], v[e + k], a);
+    out[e] = a;
+  }
+}
+
+// 4 floats of one row: a 16-byte store where the row allows it, else the elements that are inside
+__device__ inline void store4(float *row, int c, int nc, bool vec, const float (&v)[4]) {
+  if (vec) {
+    if (c < nc) *reinterpret_cast<f32x4 *>(row + c) = f32x4{v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c + e < nc) row[c + e] = v[e];
+  }
+}
+
+// grid (cdiv(w, 64), cdiv(h, 24), planes).  out: moment m of plane p at ((m * P + p) * h * w); P: planes of the whole
+// call, p0: the first plane of this launch.  PAIR: five moments of (x, y); else E[x], E[x^2] of x.
+template <bool PAIR>
+__global__ __launch_bounds__(256) void window_moments_fwd_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                                 int H, int W, int P, int p0, float *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float sx[kIH * kIW];
+  __shared__ __attribute__((aligned(16))) float sy[PAIR ? kIH * kIW : 4];
+  __shared__ __attribute__((aligned(16))) float V[kTH * kVS];
+  const int h = H - (kWin - 1), w = W - (kWin - 1);
+  const int p = p0 + blockIdx.z, oy0 = blockIdx.y * kTH, ox0 = blockIdx.x * kTW;
+  const bool vec = (W & 3) == 0;
+  stage_tile(x + (size_t)p * H * W, H, W, oy0, ox0, vec, sx);
+  if (PAIR) stage_tile(y + (size_t)p * H * W, H, W, oy0, ox0, vec, sy);
+  __syncthreads();
+  const size_t plane = (size_t)h * w;
+#define NQA_WM_MOMENT(Q, M)                                                                   \
+  {                                                                                           \
+    vertical_pass<Q>(sx, sy, V);                                                              \
+    __syncthreads();                                                                          \
+    float *o = out + ((size_t)(M)*P + p) * plane;                                             \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                           \
+      const int it = threadIdx.x + u * 256;                                                   \
+      const int row = it / (kTW / 4), col4 = (it % (kTW / 4)) * 4;                            \
+      if (it < kHItems && oy0 + row < h && ox0 + col4 < w) {                                  \
+        float r[4];                                                                           \
+        horizontal_item(V, row, col4, r);                                                     \
+        store4(o + (size_t)(oy0 + row) * w, ox0 + col4, w, vec, r);                           \
+      }                                                                                       \
+    }                                                                                         \
+    __syncthreads();                                                                          \
+  }
+  if (PAIR) {
+    NQA_WM_MOMENT(0, 0) NQA_WM_MOMENT(1, 1) NQA_WM_MOMENT(2, 2) NQA_WM_MOMENT(3, 3) NQA_WM_MOMENT(4, 4)
+  } else {
+    NQA_WM_MOMENT(0, 0) NQA_WM_MOMENT(2, 1)
+  }
+#undef NQA_WM_MOMENT
+}
+
+struct WindowGrads {
+  const float *g[5];  // upstream of E[x], E[y], E[x^2], E[y^2], E[xy], each (P, h, w); null = zero (or not needed)
+};
+
+// grid (cdiv(W, 64), cdiv(H, 24), planes).  The host has already dropped the maps the wanted sides do not read
+// (g0, g2 without gx; g1, g3 without gy), so what is left is folded in the fixed order 0, 1, 2, 3, 4.
+__global__ __launch_bounds__(256) void window_moments_bwd_kernel(const float *__restrict__ x, const float *__restrict__ y,
+                                                                 int H, int W, int p0, WindowGrads wg,
+                                                                 float *__restrict__ gx, float *__restrict__ gy) {
+  __shared__ __attribute__((aligned(16))) float sg[kIH * kIW];
+  __shared__ __attribute__((aligned(16))) float V[kTH * kVS];
+  const int h = H - (kWin - 1), w = W - (kWin - 1);
+  const int p = p0 + blockIdx.z, r0 = blockIdx.y * kTH, c0 = blockIdx.x * kTW;
+  const bool vec = (W & 3) == 0;
+  const size_t in_plane = (size_t)p * H * W, g_plane = (size_t)p * h * w;
+  // this thread's pixels: item u = (row, 4 columns)
+  bool live[2];
+  size_t at[2];
+  int col[2];
+  float xr[2][4], yr[2][4], ax[2][4], ay[2][4];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int it = threadIdx.x + u * 256;
+    const int row = it / (kTW / 4), col4 = (it % (kTW / 4)) * 4;
+    live[u] = it < kHItems && r0 + row < H && c0 + col4 < W;
+    col[u] = c0 + col4;
+    at[u] = in_plane + (size_t)(r0 + row) * W;
+    if (vec) {  // (W % 4 == 0: the four columns are inside together, one 16-byte load each)
+      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, yv = {0.f, 0.f, 0.f, 0.f};
+      if (live[u]) xv = *reinterpret_cast<const f32x4 *>(x + at[u] + col[u]);
+      if (live[u] && y) yv = *reinterpret_cast<const f32x4 *>(y + at[u] + col[u]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        xr[u][e] = xv[e];
+        yr[u][e] = yv[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool in = live[u] && col[u] + e < W;
+        xr[u][e] = in ? x[at[u] + col[u] + e] : 0.f;
+        yr[u][e] = (in && y) ? y[at[u] + col[u] + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ax[u][e] = ay[u][e] = 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    if (!wg.g[q]) continue;  // (uniform over the grid)
+    stage_tile(wg.g[q] + g_plane, h, w, r0 - (kWin - 1), c0 - (kWin - 1), vec, sg);
+    __syncthreads();
+    vertical_pass<0>(sg, sg, V);
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (!live[u]) continue;
+      const int it = threadIdx.x + u * 256;
+      float a[4];
+      horizontal_item(V, it / (kTW / 4), (it % (kTW / 4)) * 4, a);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (q == 0) ax[u][e] = a[e];
+        if (q == 1) ay[u][e] = a[e];
+        if (q == 2) ax[u][e] = fmaf(2.f * xr[u][e], a[e], ax[u][e]);
+        if (q == 3) ay[u][e] = fmaf(2.f * yr[u][e], a[e], ay[u][e]);
+        if (q == 4) {
+          ax[u][e] = fmaf(yr[u][e], a[e], ax[u][e]);
+          ay[u][e] = fmaf(xr[u][e], a[e], ay[u][e]);
+        }
+      }
+    }
+    // (the next moment's stage_tile writes sg, which nobody reads any more; its barrier precedes the next write of V)
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (!live[u]) continue;
+    if (gx) store4(gx + at[u], col[u], W, vec, ax[u]);
+    if (gy) store4(gy + at[u], col[u], W, vec, ay[u]);
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// host launchers
+// ---------------------------------------------------------------------------------
+static bool window_gauss_ok(const char *who) {
+  // gaussian(21, 7) as nqa_adists.hip's make_gauss() forms it: exp in double stored as float, normalised in float
+  static const int bad = [] {
+    float v[kWin];
+    double sd = 0.0;
+    for (int i = 0; i < kWin; ++i) {
+      v[i] = (float)exp(-(double)((i - 10) * (i - 10)) / (2.0 * 7.0 * 7.0));
+      sd += (double)v[i];
+    }
+    const float s = (float)sd;
+    for (int i = 0; i < kWin; ++i)
+      if (v[i] / s != kG[i]) return i + 1;
+    return 0;
+  }();
+  if (bad) set_error("%s: this host's exp() gives a different Gaussian window than the kernels' constants (tap %d)", who, bad - 1);
+  return !bad;
+}
+
+static constexpr int kMaxGridZ = 65535;
+
+int window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st) {
+  if (!window_gauss_ok("window_moments_forward")) return NQA_E_LAUNCH;
+  const int h = H - (kWin - 1), w = W - (kWin - 1);
+  for (int p0 = 0; p0 < P; p0 += kMaxGridZ) {
+    const dim3 grid(cdiv(w, kTW), cdiv(h, kTH), P - p0 < kMaxGridZ ? P - p0 : kMaxGridZ);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    if (y) window_moments_fwd_kernel<true><<<grid, 256, 0, st>>>(x, y, H, W, P, p0, out);
+    else window_moments_fwd_kernel<false><<<grid, 256, 0, st>>>(x, nullptr, H, W, P, p0, out);
+    if (int rc = check_launch("window_moments_fwd")) return rc;
+  }
+  return 0;
+}
+
+int window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
+                            float *gy, hipStream_t st) {
+  if (!window_gauss_ok("window_moments_backward")) return NQA_E_LAUNCH;
+  WindowGrads wg;
+  for (int q = 0; q < 5; ++q) wg.g[q] = g[q];
+  if (!gx) wg.g[0] = wg.g[2] = nullptr;
+  if (!gy) wg.g[1] = wg.g[3] = nullptr;
+  for (int p0 = 0; p0 < P; p0 += kMaxGridZ) {
+    const dim3 grid(cdiv(W, kTW), cdiv(H, kTH), P - p0 < kMaxGridZ ? P - p0 : kMaxGridZ);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    window_moments_bwd_kernel<<<grid, 256, 0, st>>>(x, y, H, W, p0, wg, gx, gy);
+    if (int rc = check_launch("window_moments_bwd")) return rc;
+  }
+  return 0;
+}
+
+}  // namespace nqa

@@ -641,3 +641,57 @@ def conv1_1_backward_scaled(g: torch.Tensor, relu1_1_split16: torch.Tensor | Non
     _call(dev, lib().nqa_conv1_1_backward_scaled, ptr(g), None if relu1_1_split16 is None else ptr(relu1_1_split16), ptr(w0),
           ptr(k), ptr(k_total), n, h, w, ptr(out), stream_ptr(dev))
     return out
+
+
+# ---- windowed moments of the A-DISTS head (include/nqa.h, nqa_window_moments.hip) ---------------------------------
+WINDOW = 21  # the library's window: the normalised 21-tap Gaussian of sigma 7, as head.gauss_1d(21, .)
+
+
+def _window_planes(x: torch.Tensor, y: torch.Tensor | None):
+    dev = _need_cuda(*([x] if y is None else [x, y]))
+    for t in (x,) if y is None else (x, y):
+        if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"window_moments: expected contiguous float32 NCHW maps, got {t.dtype} {tuple(t.shape)}")
+    if y is not None and y.shape != x.shape:
+        raise ValueError(f"window_moments: x {tuple(x.shape)} and y {tuple(y.shape)} differ")
+    return dev
+
+
+def window_moments(x: torch.Tensor, y: torch.Tensor | None = None):
+    """The 21 x 21 Gaussian window means of float32 NCHW maps (B,C,H,W), each (B,C,H-20,W-20): (E[x], E[x^2]) of x alone,
+    (E[x], E[y], E[x^2], E[y^2], E[xy]) of a pair.  One launch; the products are formed in registers."""
+    dev = _window_planes(x, y)
+    b, c, h, w = x.shape
+    n = 2 if y is None else 5
+    out = torch.empty((n, b, c, max(h - WINDOW + 1, 0), max(w - WINDOW + 1, 0)), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_window_moments_forward, ptr(x), None if y is None else ptr(y), b * c, h, w, ptr(out), stream_ptr(dev))
+    return out.unbind(0)
+
+
+def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequence, need=(True, True)):
+    """(gx, gy) of window_moments(x, y) for the upstream gradients `grads` of its maps (two without y, five with; None =
+    zero): gx = W^T g_x + 2 x W^T g_xx + y W^T g_xy and its mirror, every pixel summing over the windows that contain it.
+    None where need[i] is False (nothing is computed for that side; the other is bit-identical) and for gy without y."""
+    dev = _window_planes(x, y)
+    b, c, h, w = x.shape
+    grads = list(grads)
+    if len(grads) != (2 if y is None else 5):
+        raise ValueError(f"window_moments_backward: expected {2 if y is None else 5} upstream maps, got {len(grads)}")
+    g5 = [grads[0], None, grads[1], None, None] if y is None else grads
+    shape = (b, c, h - WINDOW + 1, w - WINDOW + 1)
+    for i, g in enumerate(g5):
+        if g is None:
+            continue
+        _need_cuda(x, g)
+        if tuple(g.shape) != shape:
+            raise ValueError(f"window_moments_backward: upstream map of shape {tuple(g.shape)}, expected {shape}")
+        g5[i] = _f32c(g)
+    need_x, need_y = bool(need[0]), bool(need[1]) and y is not None
+    if not (need_x or need_y):
+        return None, None
+    gx = torch.empty_like(x) if need_x else None
+    gy = torch.empty_like(y) if need_y else None
+    _call(dev, lib().nqa_window_moments_backward, ptr(x), None if y is None else ptr(y), b * c, h, w,
+          *[None if g is None else ptr(g) for g in g5], None if gx is None else ptr(gx), None if gy is None else ptr(gy),
+          stream_ptr(dev))
+    return gx, gy

@@ -1,0 +1,163 @@
+"""What one optimisation step on A-DISTS costs, and what the HIP windowed moments (csrc/nqa_window_moments.hip) change:
+forward + backward of `ADISTS(x, y)` (as_loss=True) on the stand-in weights at 256 x 256 B=8 and 1080 x 1920 B=1, with a
+gradient on y only and on both images, run two ways in one process:
+
+  slices    head.adists_d(..., window_impl="slices"): every window mean as 2 x 21 shifted-slice multiply-adds in torch
+            (the head's arithmetic before the kernels existed);
+  default   the window means from autograd.WindowMoments (one HIP launch forward, one backward, per stage and use).
+
+The same split for the head alone on fixed taps (no pyramid, no conv backward), and the two kernels' own times on the
+largest windowed stage (relu1_2) with their fraction of the HBM stream figure of profiles/r04_stream_bw.txt and of the
+non-packed fp32 vector rate (210 multiply-adds per value pair forward: 5 moments x 42 taps).
+
+Times from device events after warm-up: median [min, max] of REPS windows of ITERS steps.
+
+Usage: python tools/gpu_adists_loss_bench.py [OUT]  -- prints the report, and also writes it to OUT when given
+(profiles/adists_loss_step_bench.txt is one such report)."""
+import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
+import functools
+import re
+import subprocess
+import sys
+import warnings
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from nerf_qa_amd import build, ops, synth  # noqa: E402
+from nerf_qa_amd.ADISTS import ADISTS, head  # noqa: E402
+
+WARMUP, ITERS, REPS = 2, 10, 5
+SHAPES = ((256, 256, 8), (1080, 1920, 1))
+FMA_PER_S = 256 * 64 * 2.4e9  # 256 CUs x 64 lanes x one non-packed fp32 FMA per lane and clock at 2.4 GHz
+
+
+def timed(fn):
+    for _ in range(WARMUP):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(REPS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(ITERS):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / ITERS)
+    out.sort()
+    return out[len(out) // 2], out[0], out[-1]
+
+
+def commit():
+    try:
+        rev = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+        dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain"], capture_output=True, text=True).stdout.strip()
+        return (rev or "unknown") + ("+changes" if dirty else "")
+    except OSError:
+        return "unknown"
+
+
+def stream_gbs():
+    """The best copy figure of profiles/r04_stream_bw.txt (GB/s)."""
+    best = 0.0
+    with open(os.path.join(ROOT, "profiles", "r04_stream_bw.txt")) as f:
+        for line in f:
+            m = re.search(r"^copy .*?([0-9.]+) GB/s", line)
+            if m:
+                best = max(best, float(m.group(1)))
+    return best
+
+
+def main():
+    dev = torch.device("cuda:0")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        model = ADISTS().to(dev).eval()
+    stream = stream_gbs()
+    lines = [f"# tools/gpu_adists_loss_bench.py  ({torch.cuda.get_device_name(dev)}; torch {torch.__version__}; commit {commit()}; "
+             f"HIP sources {build.source_hash()})",
+             "# forward + backward of ADISTS(x, y) (as_loss=True), stand-in weights; device events, median [min, max] of "
+             f"{REPS} windows of {ITERS} steps after {WARMUP} warm-up steps",
+             f"# HBM stream figure {stream:.0f} GB/s (profiles/r04_stream_bw.txt); non-packed fp32 vector rate "
+             f"{FMA_PER_S / 1e12:.1f} T multiply-adds/s"]
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    plain = head.adists_d
+    slices = functools.partial(plain, window_impl="slices")
+    for h, w, b in SHAPES:
+        xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
+        x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
+        tx = [x0] + model._taps_nograd(x0)
+        ty = [y0] + model._taps_nograd(y0)
+
+        def step(both):
+            x = x0.detach().requires_grad_() if both else x0
+            y = y0.detach().requires_grad_()
+            model(x, y).backward()
+            return y.grad
+
+        def head_step(both):
+            fx = [t.detach().requires_grad_() for t in tx] if both else tx
+            fy = [t.detach().requires_grad_() for t in ty]
+            (1 - head.adists_d(fx, fy, 21).mean()).backward()
+            return fy[1].grad
+
+        say(f"\n{h}x{w} B={b}")
+        res = {}
+        for what, fn in (("loss step", step), ("head alone", head_step)):
+            for both in (False, True):
+                for impl, f in (("slices", slices), ("default", plain)):
+                    head.adists_d = f  # (ADISTS._loss_with_grad and head_step look it up at call time)
+                    try:
+                        torch.cuda.empty_cache()
+                        torch.cuda.reset_peak_memory_stats(dev)
+                        name = f"{what}, grad on {'x and y' if both else 'y only'}, {impl}"
+                        res[what, both, impl] = timed(lambda: fn(both))
+                    finally:
+                        head.adists_d = plain
+                    m, lo, hi = res[what, both, impl]
+                    say(f"  {name:42s} {m:9.3f} ms  [{lo:.3f}, {hi:.3f}]   peak memory "
+                        f"{torch.cuda.max_memory_allocated(dev) / 2 ** 30:6.2f} GiB")
+        for what in ("loss step", "head alone"):
+            for both in (False, True):
+                s, d = res[what, both, "slices"], res[what, both, "default"]
+                say(f"  {what}, grad on {'x and y' if both else 'y only'}: slices / default = {s[0] / d[0]:.2f} "
+                    f"(worst case, slowest default window against fastest slices window: {s[1] / d[2]:.2f}; "
+                    f"min-to-max spread of the repeats: slices {(s[2] - s[1]) / s[0] * 100:.1f} %, default {(d[2] - d[1]) / d[0] * 100:.1f} %)")
+        head.adists_d = slices
+        ga = head_step(True).clone()
+        head.adists_d = plain
+        gb = head_step(True).clone()
+        say(f"  max |g_default - g_slices| / max |g_slices| on relu1_2 of y (head alone): {((ga - gb).abs().max() / ga.abs().max()).item():.2e}")
+        # the kernels alone, on the largest windowed stage
+        fx, fy = tx[1], ty[1]
+        pb, c, hh, ww = fx.shape
+        gs = [torch.randn_like(m) for m in ops.window_moments(fx, fy)]
+        vals = pb * c * hh * ww
+        outs = pb * c * (hh - 20) * (ww - 20)
+        for name, fn, nbytes, fma in (
+                ("window_moments forward, pair", lambda: ops.window_moments(fx, fy), 4 * (2 * vals + 5 * outs), 210 * outs),
+                ("window_moments forward, x only", lambda: ops.window_moments(fx), 4 * (vals + 2 * outs), 84 * outs),
+                ("window_moments backward, gx and gy", lambda: ops.window_moments_backward(fx, fy, gs), 4 * (4 * vals + 5 * outs), 210 * vals),
+                ("window_moments backward, gy only", lambda: ops.window_moments_backward(fx, fy, gs, (False, True)),
+                 4 * (3 * vals + 3 * outs), 126 * vals)):
+            m, lo, hi = timed(fn)
+            say(f"  {name:38s} on relu1_2 {tuple(fx.shape)}: {m:8.3f} ms  [{lo:.3f}, {hi:.3f}]   {nbytes / m / 1e6:7.0f} GB/s compulsory "
+                f"= {nbytes / m / 1e6 / stream * 100:5.1f} % of stream;  {fma / m / 1e9:6.2f} T multiply-adds/s useful "
+                f"= {fma / m * 1e3 / FMA_PER_S * 100:5.1f} % of the vector rate")
+        del x0, y0, tx, ty, fx, fy, gs
+        torch.cuda.empty_cache()
+    if len(sys.argv) > 1:
+        out = sys.argv[1]
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
