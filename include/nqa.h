@@ -52,8 +52,10 @@ extern "C" {
  * matrix cores with both operands split into (hi, lo) half pairs (3 MFMAs per product block,
  * ~2^-21 relative error per product) -- near-f32 results at a fraction of the f32-MFMA cost.
  *
- * NQA_PREC_F32M ("mixed", DISTS pyramid entry points only: nqa_pack_vgg_weights, nqa_workspace_bytes,
- * nqa_vgg_pyramid, nqa_dists_forward): stages 1..3 (conv layers 0..6) keep f16 NHWC activations and multiply them
+ * NQA_PREC_F32M ("mixed", a mode of the DISTS pyramid: nqa_pack_vgg_weights, nqa_workspace_bytes, nqa_vgg_pyramid,
+ * nqa_dists_forward, and the single operators that run one of its layers on a mixed blob -- nqa_conv1_1, nqa_conv1_fused,
+ * nqa_conv3x3_relu, nqa_l2pool, nqa_l2pool_f16_to_split16; the A-DISTS entry points and nqa_nhwc_to_nchw_f32 refuse it):
+ * stages 1..3 (conv layers 0..6) keep f16 NHWC activations and multiply them
  * with weights held as f16 (hi, lo) pairs -- TWO MFMAs per product, the weights' 11-bit rounding removed -- and
  * stages 4..5 (layers 7..12) run as NQA_PREC_F32S; the L2-pool after stage 3 turns the f16 tap into split16
  * records.  Taps 1..3 are half, taps 4..5 float.  What is left of the 16-bit error is the activation rounding of the
@@ -100,27 +102,40 @@ int nqa_pack_vgg_weights(const float *const w_host[NQA_NUM_CONVS], const float *
 
 /* conv1_1 with the input normalisation folded in front: h=(x-mean)/std (DISTS_pt.py:92),
  * zero padding applied to h, conv3x3(3->64)+bias+ReLU (features[0,1]).  x: dev float32
- * NCHW (n,3,H,W); out: dev NHWC (n,H,W,64) in prec's element type (split16 in NQA_PREC_F32S). */
+ * NCHW (n,3,H,W); out: dev NHWC (n,H,W,64) in prec's element type (split16 in NQA_PREC_F32S).
+ * A mixed mode: the exact float convolution stored as half, the form the pyramid runs where it does not fuse stage 1. */
 int nqa_conv1_1(const float *x_nchw, int n, int H, int W, const void *packed_w, int prec, void *out_nhwc,
                 void *stream);
 
 /* Stage 1 in one kernel (16-bit modes and NQA_PREC_F32S): conv1_1 as above followed by conv1_2+ReLU
  * (features[0..3], DISTS_pt.py:36-37), the 64-channel intermediate staying in LDS.
  * x: dev float32 NCHW (n,3,H,W); out: dev NHWC (n,H,W,64) = relu1_2 in prec's element type (float in NQA_PREC_F32S, whose
- * products are three-term (hi, lo) splits in both convolutions).  NQA_PREC_F32 has no fused form. */
+ * products are three-term (hi, lo) splits in both convolutions).  NQA_PREC_F32 has no fused form.
+ * A mixed mode: both convolutions on two-term weights, half out (the normalised pixels and relu1_1 are rounded to half);
+ * the pyramid takes this form only for W >= 16 with the first-forms bit of nqa_set_conv_variant clear, and so does this
+ * call: NQA_E_SHAPE otherwise (run nqa_conv1_1 and nqa_conv3x3_relu(layer 1) then, as the pyramid does). */
 int nqa_conv1_fused(const float *x_nchw, int n, int H, int W, const void *packed_w, int prec, void *out_nhwc,
                     void *stream);
 
 /* conv3x3 stride 1 pad 1 + bias + ReLU for VGG layer `layer` (1..12), NHWC in/out
  * (torchvision Conv2d+ReLU pairs, DISTS_pt.py:36-49).  NQA_PREC_F32S: split16 in; float out for
- * the tapped layers (1, 3, 6, 9, 12), split16 out otherwise. */
+ * the tapped layers (1, 3, 6, 9, 12), split16 out otherwise.  A mixed mode: the layer as the pyramid runs it on the
+ * mixed blob -- half in and out on two-term weights where the layer's stage is a 16-bit one (NQA_MIXED_STAGES), the
+ * formats and kernels of NQA_PREC_F32S behind it. */
 int nqa_conv3x3_relu(const void *in_nhwc, int n, int H, int W, int layer, const void *packed_w, int prec,
                      void *out_nhwc, void *stream);
 
 /* L2pooling.forward, DISTS_pt.py:22-25 (= Downsample, ADISTS.py:28-31):
  * sqrt(depthwise 3x3 Hanning, stride 2, pad 1, of x^2, + 1e-12).  NHWC (n,H,W,C) ->
- * (n,ceil(H/2),ceil(W/2),C).  NQA_PREC_F32S: float in (a tapped map), split16 out. */
+ * (n,ceil(H/2),ceil(W/2),C).  NQA_PREC_F32S: float in (a tapped map), split16 out.  A mixed mode: the pool between two
+ * of its 16-bit stages, i.e. NQA_PREC_F16 (the call has no stage argument; the boundary pool is the next function). */
 int nqa_l2pool(const void *in_nhwc, int n, int H, int W, int C, int prec, void *out_nhwc, void *stream);
+
+/* The L2-pool at a mixed mode's boundary, behind its last 16-bit stage: half NHWC (n,H,W,C) in, split16 records
+ * (n,ceil(H/2),ceil(W/2),C) out, C a multiple of 16.  The pooled value is formed in float from the half inputs and split
+ * as everywhere: hi = half(v), lo = half(v - hi).  Below 2^-14 hi is a subnormal half and lo adds nothing, so such a value
+ * is kept to an absolute 2^-25, not to float precision. */
+int nqa_l2pool_f16_to_split16(const void *in_nhwc_f16, int n, int H, int W, int C, void *out_split16, void *stream);
 
 /* NHWC (prec element type) -> float32 NCHW, so forward_once can return the
  * reference's tensor format (DISTS_pt.py:103). */

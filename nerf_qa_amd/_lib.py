@@ -39,6 +39,7 @@ _SIGNATURES = {
     "nqa_conv1_fused": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "nqa_conv3x3_relu": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "nqa_l2pool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "nqa_l2pool_f16_to_split16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "nqa_nhwc_to_nchw_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nqa_split16_encode": (_i, [_vp, C.c_long, _i, _vp, _vp]),
     "nqa_split16_decode": (_i, [_vp, C.c_long, _i, _vp, _vp]),

@@ -333,19 +333,23 @@ static int run_stages(const float *x, const float *y, int nx, void *bufA, void *
 // `chan`: the widest H x W map the call addresses with 32-bit in-image byte offsets (the conv DMA
 // plan): 64 channels for the pyramid paths (H, W are stage-1 sizes; later stages have 1/4 of the
 // pixels per doubling of the channels), the layer's own input width for the single-operator calls.
-static bool bad_dims(const char *who, int n, int H, int W, int prec, int chan = 512, bool pyramid = false) {
+// `mixed_ok`: the entry point takes the mixed modes.  `stage` >= 0: a single-operator call on a map of that pyramid
+// stage (0-based), whose element size is the stage's own (stage_prec) -- in a mixed mode 2 or 4 bytes by stage.
+static bool bad_dims(const char *who, int n, int H, int W, int prec, int chan = 512, bool mixed_ok = false,
+                     int stage = -1) {
   if (n <= 0 || H <= 0 || W <= 0) {
     set_error("%s: non-positive size n=%d H=%d W=%d", who, n, H, W);
     return true;
   }
-  if (!(pyramid ? prec_valid_pyramid(prec) : prec_valid(prec))) {
-    set_error(is_mixed(prec) ? "%s: NQA_PREC_F32M / F32M2 (%d) is a mode of the DISTS pyramid entry points only"
-                                    : "%s: unknown prec %d", who, prec);
+  if (!(mixed_ok ? prec_valid_pyramid(prec) : prec_valid(prec))) {
+    set_error(is_mixed(prec) ? "%s: takes no mixed mode (prec %d): pass the kernel precision of the map's own stage"
+                             : "%s: unknown prec %d", who, prec);
     return true;
   }
-  if (chan > 0 && (long)H * W * chan * (long)prec_elem_bytes(prec) >= (1L << 31)) {
+  const long eb = (long)prec_elem_bytes(stage >= 0 ? stage_prec(prec, stage) : prec);
+  if (chan > 0 && (long)H * W * chan * eb >= (1L << 31)) {
     set_error("%s: map too large for 32-bit in-image byte offsets (H*W*%d channels*%d bytes >= 2^31)", who, chan,
-              (int)prec_elem_bytes(prec));
+              (int)eb);
     return true;
   }
   return false;
@@ -639,7 +643,9 @@ int nqa_conv1_1(const float *x, int n, int H, int W, const void *packed, int pre
     set_error("conv1_1: null pointer");
     return NQA_E_ARG;
   }
-  if (bad_dims("conv1_1", n, H, W, prec, 64)) return NQA_E_ARG;
+  if (bad_dims("conv1_1", n, H, W, prec, 64, true, 0)) return NQA_E_ARG;
+  if (is_mixed(prec))  // what run_stages calls where it does not fuse stage 1: the exact float conv, half out
+    return conv1_1_blob(x, n, H, W, packed, prec, NQA_PREC_F16, out, static_cast<hipStream_t>(stream));
   return conv1_1(x, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
 }
 
@@ -648,7 +654,15 @@ int nqa_conv1_fused(const float *x, int n, int H, int W, const void *packed, int
     set_error("conv1_fused: null pointer");
     return NQA_E_ARG;
   }
-  if (bad_dims("conv1_fused", n, H, W, prec, 64)) return NQA_E_ARG;
+  if (bad_dims("conv1_fused", n, H, W, prec, 64, true, 0)) return NQA_E_ARG;
+  if (is_mixed(prec)) {  // the fused form exactly where run_stages takes it, never another kernel under its name
+    if (W < 16 || mixed_stage1_unfused()) {
+      set_error("conv1_fused: a mixed mode runs stage 1 fused only for W >= 16 with the first-forms bit of "
+                "nqa_set_conv_variant clear (W = %d): nqa_conv1_1 + nqa_conv3x3_relu(layer 1) otherwise", W);
+      return NQA_E_SHAPE;
+    }
+    return conv1_fused_blob(x, nullptr, n, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
+  }
   if (prec == NQA_PREC_F32S) return conv1_fused_split(x, nullptr, n, n, H, W, packed, out, static_cast<hipStream_t>(stream));
   return conv1_fused(x, nullptr, n, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
 }
@@ -663,8 +677,12 @@ int nqa_conv3x3_relu(const void *in, int n, int H, int W, int layer, const void 
     set_error("conv3x3_relu: layer %d out of range 1..12", layer);
     return NQA_E_ARG;
   }
-  if (bad_dims("conv3x3_relu", n, H, W, prec, kConvs[layer].cin > kConvs[layer].cout ? kConvs[layer].cin : kConvs[layer].cout))
+  if (bad_dims("conv3x3_relu", n, H, W, prec, kConvs[layer].cin > kConvs[layer].cout ? kConvs[layer].cin : kConvs[layer].cout,
+               true, kConvs[layer].stage))
     return NQA_E_ARG;
+  if (is_mixed(prec))  // the layer as run_stages runs it: the stage's kernels on the mixed blob's rows
+    return conv3x3_blob(in, n, H, W, layer, packed, prec, stage_prec(prec, kConvs[layer].stage), out,
+                        static_cast<hipStream_t>(stream));
   return conv3x3(in, n, H, W, layer, packed, prec, out, static_cast<hipStream_t>(stream));
 }
 
@@ -673,12 +691,27 @@ int nqa_l2pool(const void *in, int n, int H, int W, int C, int prec, void *out, 
     set_error("l2pool: null pointer");
     return NQA_E_ARG;
   }
-  if (bad_dims("l2pool", n, H, W, prec, C > 0 ? C : 1)) return NQA_E_ARG;
+  if (bad_dims("l2pool", n, H, W, prec, C > 0 ? C : 1, true, 0)) return NQA_E_ARG;
   if (C <= 0 || C % 8) {
     set_error("l2pool: C=%d must be a positive multiple of 8", C);
     return NQA_E_SHAPE;
   }
-  return l2pool(in, n, H, W, C, prec, out, static_cast<hipStream_t>(stream));
+  // a mixed mode: the pool INSIDE its 16-bit stages (half in, half out); the boundary pool is nqa_l2pool_f16_to_split16
+  return l2pool(in, n, H, W, C, is_mixed(prec) ? NQA_PREC_F16 : prec, out, static_cast<hipStream_t>(stream));
+}
+
+int nqa_l2pool_f16_to_split16(const void *in, int n, int H, int W, int C, void *out, void *stream) {
+  if (!in || !out) {
+    set_error("l2pool_f16_to_split16: null pointer");
+    return NQA_E_ARG;
+  }
+  // (sized by the 4-byte records it writes; its input is half as large)
+  if (bad_dims("l2pool_f16_to_split16", n, H, W, NQA_PREC_F32S, C > 0 ? C : 1)) return NQA_E_ARG;
+  if (C <= 0 || C % 16) {  // a split16 record holds 16 channels
+    set_error("l2pool_f16_to_split16: C=%d must be a positive multiple of 16", C);
+    return NQA_E_SHAPE;
+  }
+  return l2pool_to_split16(in, n, H, W, C, out, static_cast<hipStream_t>(stream));
 }
 
 int nqa_nhwc_to_nchw_f32(const void *in, int n, int H, int W, int C, int prec, float *out, void *stream) {

@@ -86,36 +86,43 @@ def pack_vgg_weights(convs: Sequence, prec) -> torch.Tensor:
 TAP_LAYERS = (1, 3, 6, 9, 12)  # conv layers whose output is tapped (relu1_2 .. relu5_3)
 
 
+def _stage_dtype(p: int, stage: int) -> torch.dtype:
+    """Element type of the maps of pyramid stage `stage` (0-based) in mode p: in a mixed mode the stage's own."""
+    return PREC_DTYPE[_lib.stage_prec(p, stage)]
+
+
 def conv1_1(x: torch.Tensor, packed: torch.Tensor, prec) -> torch.Tensor:
     """relu1_1 as NHWC in prec's activation format ("f32s": split16 bytes in a float32 tensor, see
-    include/nqa.h Layouts; split16_decode turns them into floats)."""
+    include/nqa.h Layouts; split16_decode turns them into floats).  A mixed mode: the exact float conv, half out."""
     p = prec_id(prec)
     dev = _need_cuda(x, packed)
     x = _f32c(x)
     n, c, h, w = x.shape
     assert c == 3
-    out = torch.empty((n, h, w, 64), dtype=PREC_DTYPE[p], device=dev)
+    out = torch.empty((n, h, w, 64), dtype=_stage_dtype(p, 0), device=dev)
     _call(dev, lib().nqa_conv1_1, ptr(x), n, h, w, ptr(packed), p, ptr(out), stream_ptr(dev))
     return out
 
 
 def conv1_fused(x: torch.Tensor, packed: torch.Tensor, prec) -> torch.Tensor:
-    """relu1_2 (NHWC) straight from the image: conv1_1 + conv1_2 in one kernel (16-bit modes and "f32s": float out)."""
+    """relu1_2 (NHWC) straight from the image: conv1_1 + conv1_2 in one kernel (16-bit modes and "f32s": float out; a
+    mixed mode: two-term weights, half out, only where the pyramid fuses stage 1 -- NqaError for W < 16)."""
     p = prec_id(prec)
     dev = _need_cuda(x, packed)
     x = _f32c(x)
     n, c, h, w = x.shape
     assert c == 3
-    out = torch.empty((n, h, w, 64), dtype=PREC_DTYPE[p], device=dev)
+    out = torch.empty((n, h, w, 64), dtype=_stage_dtype(p, 0), device=dev)
     _call(dev, lib().nqa_conv1_fused, ptr(x), n, h, w, ptr(packed), p, ptr(out), stream_ptr(dev))
     return out
 
 
 def conv3x3_relu(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec) -> torch.Tensor:
-    """One VGG conv layer, NHWC.  "f32s": split16 in; float out for TAP_LAYERS, split16 out otherwise."""
+    """One VGG conv layer, NHWC.  "f32s": split16 in; float out for TAP_LAYERS, split16 out otherwise.  A mixed mode:
+    half in and out where the layer's stage is a 16-bit one, the f32s formats behind it."""
     p = prec_id(prec)
     dev = _need_cuda(inp, packed)
-    assert inp.dtype == PREC_DTYPE[p] and inp.is_contiguous()
+    assert inp.dtype == _stage_dtype(p, CONV_STAGE[layer]) and inp.is_contiguous()
     n, h, w, c = inp.shape
     assert c == CONV_CIN[layer]
     out = torch.empty((n, h, w, CONV_COUT[layer]), dtype=inp.dtype, device=dev)
@@ -124,13 +131,24 @@ def conv3x3_relu(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec) -> t
 
 
 def l2pool(inp: torch.Tensor, prec) -> torch.Tensor:
-    """L2-pool of a tapped map, NHWC.  "f32s": float in, split16 out (it feeds the next conv)."""
+    """L2-pool of a tapped map, NHWC.  "f32s": float in, split16 out (it feeds the next conv).  A mixed mode: the pool
+    between two of its 16-bit stages (half in, half out); its boundary pool is l2pool_f16_to_split16."""
     p = prec_id(prec)
     dev = _need_cuda(inp)
-    assert inp.dtype == PREC_DTYPE[p] and inp.is_contiguous()
+    assert inp.dtype == _stage_dtype(p, 0) and inp.is_contiguous()
     n, h, w, c = inp.shape
     out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=inp.dtype, device=dev)
     _call(dev, lib().nqa_l2pool, ptr(inp), n, h, w, c, p, ptr(out), stream_ptr(dev))
+    return out
+
+
+def l2pool_f16_to_split16(inp: torch.Tensor) -> torch.Tensor:
+    """The L2-pool behind a mixed mode's last 16-bit stage: half NHWC in, split16 records out (float32-typed tensor)."""
+    dev = _need_cuda(inp)
+    assert inp.dtype == torch.float16 and inp.is_contiguous()
+    n, h, w, c = inp.shape
+    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_l2pool_f16_to_split16, ptr(inp), n, h, w, c, ptr(out), stream_ptr(dev))
     return out
 
 

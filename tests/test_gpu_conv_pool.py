@@ -40,40 +40,37 @@ SHAPES = [(1, 4, 16), (1, 8, 32), (2, 16, 48), (1, 5, 16), (1, 4, 17), (3, 13, 3
 
 
 @pytest.mark.parametrize("b,h,w", SHAPES, ids=[f"{b}x{h}x{w}" for b, h, w in SHAPES])
-@pytest.mark.parametrize("prec", ["f16", "f32m"])
+@pytest.mark.parametrize("prec", ["f16", "f32m", "f16w"])
 def test_fused_conv_pool_stats_against_the_unfused_operators(b, h, w, prec, dev, blobs):
     from nerf_qa_amd import ops
     inp = _input(2 * b, h, w, dev, seed=h * 1000 + w + b)
     kprec = "f16"
     pooled, sums = ops.conv_pool_stats(inp, 3, blobs[prec], prec)
-    # the unfused pair: conv2_2 (same kernels' MFMA order) then the L2-pool
-    if prec == "f16":
-        tap = ops.conv3x3_relu(inp, 3, blobs[prec], prec)
-    else:  # the mixed blobs' conv layers are reached through the pyramid only: emulate with the f16w blob's own path
-        tap = None
-    if tap is not None:
-        ref_pool = ops.l2pool(tap, kprec)
-        d = (pooled.float() - ref_pool.float()).abs()
-        ulp = torch.maximum(ref_pool.float().abs(), torch.tensor(6.1e-5, device=dev)) * 2.0 ** -10
-        assert (d <= ulp).all(), (b, h, w, float((d / ulp).max()))
-        frac = float((d > 0).float().mean())
-        assert frac < 2e-2, frac  # a different summation order flips the last bit of a few results, no more
-        t = tap.double()
-        tx, ty = t[:b], t[b:]
-        want = torch.stack([tx.sum((1, 2)), ty.sum((1, 2)), (tx * tx).sum((1, 2)), (ty * ty).sum((1, 2)), (tx * ty).sum((1, 2))], -1)
-        npx = h * w
-        mx, my = want[..., 0] / npx, want[..., 1] / npx
-        var_x, var_y = want[..., 2] / npx - mx * mx, want[..., 3] / npx - my * my
-        got = sums
-        gmx, gmy = got[..., 0] / npx, got[..., 1] / npx
-        gvx, gvy = got[..., 2] / npx - gmx * gmx, got[..., 3] / npx - gmy * gmy
-        gcov, cov = got[..., 4] / npx - gmx * gmy, want[..., 4] / npx - mx * my
-        scale = torch.maximum(var_x + var_y, torch.tensor(1e-12, device=dev, dtype=torch.float64))
-        assert ((gmx - mx).abs() <= 1e-6 * (mx.abs() + 1e-3)).all() and ((gmy - my).abs() <= 1e-6 * (my.abs() + 1e-3)).all()
-        # variances / covariance to 1e-5 of the variance itself (the nearly constant channel 5 included)
-        assert ((gvx - var_x).abs() <= 2e-5 * scale + 1e-12).all(), float(((gvx - var_x).abs() / scale).max())
-        assert ((gvy - var_y).abs() <= 2e-5 * scale + 1e-12).all()
-        assert ((gcov - cov).abs() <= 2e-5 * scale + 1e-12).all()
+    # the unfused pair: conv2_2 (same kernels' MFMA order; the mixed blobs' two-term layer through the same entry point)
+    # then the L2-pool
+    tap = ops.conv3x3_relu(inp, 3, blobs[prec], prec)
+    ref_pool = ops.l2pool(tap, kprec)
+    d = (pooled.float() - ref_pool.float()).abs()
+    ulp = torch.maximum(ref_pool.float().abs(), torch.tensor(6.1e-5, device=dev)) * 2.0 ** -10
+    assert (d <= ulp).all(), (b, h, w, float((d / ulp).max()))
+    frac = float((d > 0).float().mean())
+    assert frac < 2e-2, frac  # a different summation order flips the last bit of a few results, no more
+    t = tap.double()
+    tx, ty = t[:b], t[b:]
+    want = torch.stack([tx.sum((1, 2)), ty.sum((1, 2)), (tx * tx).sum((1, 2)), (ty * ty).sum((1, 2)), (tx * ty).sum((1, 2))], -1)
+    npx = h * w
+    mx, my = want[..., 0] / npx, want[..., 1] / npx
+    var_x, var_y = want[..., 2] / npx - mx * mx, want[..., 3] / npx - my * my
+    got = sums
+    gmx, gmy = got[..., 0] / npx, got[..., 1] / npx
+    gvx, gvy = got[..., 2] / npx - gmx * gmx, got[..., 3] / npx - gmy * gmy
+    gcov, cov = got[..., 4] / npx - gmx * gmy, want[..., 4] / npx - mx * my
+    scale = torch.maximum(var_x + var_y, torch.tensor(1e-12, device=dev, dtype=torch.float64))
+    assert ((gmx - mx).abs() <= 1e-6 * (mx.abs() + 1e-3)).all() and ((gmy - my).abs() <= 1e-6 * (my.abs() + 1e-3)).all()
+    # variances / covariance to 1e-5 of the variance itself (the nearly constant channel 5 included)
+    assert ((gvx - var_x).abs() <= 2e-5 * scale + 1e-12).all(), float(((gvx - var_x).abs() / scale).max())
+    assert ((gvy - var_y).abs() <= 2e-5 * scale + 1e-12).all()
+    assert ((gcov - cov).abs() <= 2e-5 * scale + 1e-12).all()
     assert torch.isfinite(pooled.float()).all() and torch.isfinite(sums).all()
     assert pooled.shape == (2 * b, (h + 1) // 2, (w + 1) // 2, 128)
 
