@@ -227,6 +227,36 @@ int nqa_adists_dists_forward(const float *x_nchw, const float *y_nchw, int B, in
                              int prec, void *workspace, size_t workspace_bytes, float *d, float *s1, float *s2,
                              float *map, void *stream);
 
+/* ONE stage of nqa_adists_forward's heavy pass on its own, for tests and tools: the launch that turns a tap pair into
+ * the stage's three channel-reduced maps, exactly as nqa_adists_forward enqueues it (the same launch functions, with the
+ * stage's channels as the whole channel vector: ctot = C, offset 0).  No workspace.
+ *   fx, fy  C == 3: dev float32 NCHW planes (B,3,H,W), whatever prec is.  C in {64,128,256,512}: dev NHWC taps
+ *           (B,H,W,C) in prec's storage type (float for NQA_PREC_F32 / NQA_PREC_F32S).
+ *   q       dev float32 [8][B][C], rows as the forward's preparation kernel writes them: 0 inv_x, 1 inv_y
+ *           (1 / max(||f||_2, 1e-12) of the raw maps), 2 unused here, 3..7 mean_x mean_y var_x var_y cov of the raw maps
+ *           (population), read by the global branch only.
+ *   wgt     dev float32 [B][C] channel weights.
+ *   gamma, tw, sw   dev float32 (B, H-20, W-20): gamma = mean_c (E[x^2] - E[x]^2) / (E[x] + 1e-12) of the RAW x maps
+ *           under the 21 x 21 window (ADISTS.py:84-86), tw = sum_c w_c T_c, sw = sum_c w_c S_c of the normalised maps
+ *           (ADISTS.py:165-183).  H < 21 or W < 21: the global branch (ADISTS.py:91-97,176-180) from q rows 3..7, B values
+ *           per map.
+ * Dispatch: C == 3 the planar kernel; float taps the LDS kernel, or the first form when the calling thread's
+ * nqa_set_conv_variant bit 3 is set; 16-bit taps the first form.
+ *   strip   0: the launcher's own strip height.  1 <= strip <= H-20: that many output rows per block of the LDS kernel
+ *           (more than 64 makes a block flush its rows in groups of 64); ignored where no LDS kernel runs.  The launcher
+ *           itself never goes past 256 rows; taller forced strips are allowed (nothing in the kernel is sized by the
+ *           strip) but the tests force at most 150.
+ * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, prec outside the four kernel-level
+ * modes, strip < 0 or > H-20; NQA_E_SHAPE any other C, or H * W * C elements of the tap's type reaching 2^31 bytes (the
+ * kernels' in-image byte offsets are 32-bit; nqa_adists_forward refuses its own form of this limit, on the frame, with
+ * NQA_E_ARG -- the two codes differ).
+ * nqa_adists_window_grid: the LDS kernel's grid for the same arguments and the calling thread's variant, grid[0..2] =
+ * column groups, row strips, strip height (from the launcher's own function); zeros where no LDS kernel would run.
+ * The same refusals. */
+int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W, int C, int prec, const float *q,
+                            const float *wgt, int strip, float *gamma, float *tw, float *sw, void *stream);
+int nqa_adists_window_grid(int B, int H, int W, int C, int prec, int strip, int *grid);
+
 /* ---- input preparation on the device (decoded uint8 frame -> metric input) ------------ */
 
 /* transforms.ToTensor / `torch.from_numpy(frame).permute(2,0,1).float() / 255.0` (prep.py:89,

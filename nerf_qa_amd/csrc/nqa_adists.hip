@@ -1081,25 +1081,40 @@ static int launch_window_planar(const float *x, const float *y, int B, int H, in
   return check_launch("adists_window_planar");
 }
 
+// Grid of the LDS form of the window pass: column groups of 4, and strips as tall as the grid allows (up to 256
+// rows): the fewest strips that still give the chip ~8 rounds of blocks (3 blocks per CU), else 64-row strips.
+// strip_req in [1, Ho] replaces that choice of height (nqa_adists_window_stage: tests reach the multi-group
+// strips at small shapes with it); 0 is the launcher's own.
+static void window_lds_grid(int Ho, int Wo, int B, int strip_req, int &nbx, int &nby, int &strip) {
+  nbx = cdiv(Wo, 4);
+  if (strip_req > 0) {
+    strip = strip_req;
+  } else {
+    nby = cdiv(Ho, 256);
+    while (nby < cdiv(Ho, 64) && (long)nbx * nby * B < 6144) ++nby;
+    strip = cdiv(Ho, nby);
+  }
+  nby = cdiv(Ho, strip);
+}
+
+// Which form of the NHWC pass runs: the LDS kernel (instantiated for float taps only) unless the calling thread asked
+// for the first form.  The launcher and nqa_adists_window_grid both decide by this.
+static bool window_uses_lds(size_t tap_elem_bytes) { return tap_elem_bytes == 4 && !adists_window_legacy(); }
+
 template <typename P>
 static int launch_window_lanes(const void *fx, const void *fy, int B, int H, int W, int C, const float *q, int ctot,
                                int coff, const float *wgt, const Gauss &g, float *gamma, float *tw, float *sw,
-                               hipStream_t st) {
+                               hipStream_t st, int strip_req = 0) {
   const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
   const typename P::T *px = reinterpret_cast<const typename P::T *>(fx), *py = reinterpret_cast<const typename P::T *>(fy);
   // the shipped form for float taps (f32 / f32s): taps shared through LDS, XCD-aware column order.  16-bit taps
   // (the opt-in f16 / bf16 modes) measured 20 % slower that way (2-byte LDS reads + conversions) and keep the first form
   if constexpr (sizeof(typename P::T) == 4) {  // (the LDS kernel is instantiated for float taps only)
-  if (!adists_window_legacy()) {
+  if (window_uses_lds(sizeof(typename P::T))) {
     // four ring slots + the waves' channel constants (3 x 64 floats each): 51 KB, three blocks per CU
     const int LDS = 4 * 2 * 24 * 64 * 4 + 4 * 768;
-    // strips as tall as the grid allows (up to 256 rows): the fewest strips that still give the chip ~8 rounds
-    // of blocks (3 blocks per CU), else 64-row strips
-    const int nbx = cdiv(Wo, 4);
-    int nby = cdiv(Ho, 256);
-    while (nby < cdiv(Ho, 64) && (long)nbx * nby * B < 6144) ++nby;
-    const int strip = cdiv(Ho, nby);
-    nby = cdiv(Ho, strip);
+    int nbx, nby, strip;
+    window_lds_grid(Ho, Wo, B, strip_req, nbx, nby, strip);
     const long nblk = (long)nbx * nby * B;
     if (nblk > 0x7FFFFFFFL) {
       set_error("adists_window: grid too large");
@@ -1130,6 +1145,25 @@ static int launch_window_lanes(const void *fx, const void *fy, int B, int H, int
     default: set_error("adists_window_lanes: unsupported channel count %d", C); return NQA_E_SHAPE;
   }
   return check_launch("adists_window_lanes");
+}
+
+static int launch_global(const float *q, int B, int ctot, int coff, int creal, const float *wgt, float *gamma,
+                         float *tw, float *sw, hipStream_t st) {
+  TimedLaunch t(NQA_K_ADISTS, st);
+  adists_global_kernel<<<B, 256, 0, st>>>(q, B, ctot, coff, creal, wgt, gamma, tw, sw);
+  return check_launch("adists_global");
+}
+
+// The window as the host computes it, or null (error set) if it is not the kernels' compile-time taps.
+static const Gauss *checked_gauss(const char *who) {
+  static const Gauss gauss = make_gauss();
+  for (int i = 0; i < kWin; ++i)
+    if (gauss.g[i] != kG[i]) {
+      set_error("%s: this host's exp() gives a different Gaussian window than the kernels' constants "
+                "(tap %d: %a vs %a)", who, i, (double)gauss.g[i], (double)kG[i]);
+      return nullptr;
+    }
+  return &gauss;
 }
 
 }  // namespace nqa
@@ -1259,21 +1293,15 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
     if ((rc = check_launch("adists_weights"))) return rc;
   }
   // ---- heavy pass: gamma / TW / SW maps per stage ----
-  static const Gauss gauss = make_gauss();
-  for (int i = 0; i < kWin; ++i)
-    if (gauss.g[i] != kG[i]) {
-      set_error("adists_forward: this host's exp() gives a different Gaussian window than the kernels' constants "
-                "(tap %d: %a vs %a)", i, (double)gauss.g[i], (double)kG[i]);
-      return NQA_E_LAUNCH;
-    }
+  const Gauss *gp = checked_gauss("adists_forward");
+  if (!gp) return NQA_E_LAUNCH;
+  const Gauss &gauss = *gp;
   for (int k = 0; k < 6; ++k) {
     float *gamma = reinterpret_cast<float *>(base + p.maps[k][0]);
     float *tw = reinterpret_cast<float *>(base + p.maps[k][1]);
     float *sw = reinterpret_cast<float *>(base + p.maps[k][2]);
     if (!p.windowed[k]) {
-      TimedLaunch t(NQA_K_ADISTS, st);
-      adists_global_kernel<<<B, 256, 0, st>>>(q, B, ctot, p.sd.coff[k], p.c[k], wgt, gamma, tw, sw);
-      if ((rc = check_launch("adists_global"))) return rc;
+      if ((rc = launch_global(q, B, ctot, p.sd.coff[k], p.c[k], wgt, gamma, tw, sw, st))) return rc;
       continue;
     }
     if (k == 0) {
@@ -1342,7 +1370,62 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
   return NQA_OK;
 }
 
+// One stage of the heavy pass on its own, dispatched as the loop above dispatches it (ctot = C, coff = 0).
+static int window_stage_check(const char *who, int B, int H, int W, int C, int prec, int strip) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || !prec_valid(prec)) {
+    set_error("%s: bad size or prec (B=%d H=%d W=%d C=%d prec=%d)", who, B, H, W, C, prec);
+    return NQA_E_ARG;
+  }
+  const bool windowed = H >= kWin && W >= kWin;
+  if (strip < 0 || (windowed && strip > H - (kWin - 1))) {
+    set_error("%s: strip %d outside [0, %d]", who, strip, windowed ? H - (kWin - 1) : 0);
+    return NQA_E_ARG;
+  }
+  if (C != 3 && C != 64 && C != 128 && C != 256 && C != 512) {
+    set_error("%s: unsupported channel count %d (3, 64, 128, 256 or 512)", who, C);
+    return NQA_E_SHAPE;
+  }
+  if ((long)H * W * C * (long)(C == 3 ? 4 : prec_elem_bytes(prec)) >= (1L << 31)) {
+    set_error("%s: map too large for 32-bit in-image byte offsets", who);
+    return NQA_E_SHAPE;
+  }
+  return NQA_OK;
+}
+
 extern "C" {
+
+int nqa_adists_window_grid(int B, int H, int W, int C, int prec, int strip, int *grid) {
+  if (!grid) {
+    set_error("adists_window_grid: null pointer");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_stage_check("adists_window_grid", B, H, W, C, prec, strip)) return rc;
+  grid[0] = grid[1] = grid[2] = 0;
+  if (H >= kWin && W >= kWin && C != 3 && window_uses_lds(prec_elem_bytes(prec)))
+    window_lds_grid(H - (kWin - 1), W - (kWin - 1), B, strip, grid[0], grid[1], grid[2]);
+  return NQA_OK;
+}
+
+int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W, int C, int prec, const float *q,
+                            const float *wgt, int strip, float *gamma, float *tw, float *sw, void *stream) {
+  if (!fx || !fy || !q || !wgt || !gamma || !tw || !sw) {
+    set_error("adists_window_stage: null pointer");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_stage_check("adists_window_stage", B, H, W, C, prec, strip)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (H < kWin || W < kWin) return launch_global(q, B, C, 0, C, wgt, gamma, tw, sw, st);
+  const Gauss *gp = checked_gauss("adists_window_stage");
+  if (!gp) return NQA_E_LAUNCH;
+  if (C == 3)
+    return launch_window_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, C, 0, wgt,
+                                *gp, gamma, tw, sw, st);
+  switch (storage_prec(prec)) {
+    case NQA_PREC_F32: return launch_window_lanes<PrecF32>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
+    case NQA_PREC_BF16: return launch_window_lanes<PrecBF16>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
+    default: return launch_window_lanes<PrecF16>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
+  }
+}
 
 int nqa_adists_forward(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
                        size_t ws_bytes, float *d_out, void *stream) {

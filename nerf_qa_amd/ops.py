@@ -436,6 +436,69 @@ def adists_dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor,
     return (d, s1, s2, m) if with_map else (d, s1, s2)
 
 
+def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, p: int, strip: int):
+    """Every check of adists_window_stage on its inputs; (B, H, W, C, output shape).  C is q's: 3 means float32 NCHW
+    planes, anything else NHWC taps in prec's storage type."""
+    if p not in PREC_DTYPE:
+        raise ValueError(f"adists_window_stage: prec {p} is not one of the kernel-level modes")
+    if q.dim() != 3 or q.shape[0] != 8 or q.shape[2] not in CHNS:
+        raise ValueError(f"adists_window_stage: q must be (8, B, C) with C in {sorted(set(CHNS))}, got {tuple(q.shape)}")
+    b, c = int(q.shape[1]), int(q.shape[2])
+    if fx.dim() != 4 or fx.shape != fy.shape or fx.numel() == 0:
+        raise ValueError(f"adists_window_stage: expected two non-empty 4-d taps of equal shape, got {tuple(fx.shape)} / "
+                         f"{tuple(fy.shape)}")
+    if c == 3:
+        h, w = int(fx.shape[2]), int(fx.shape[3])
+        shape, want = (b, 3, h, w), torch.float32
+    else:
+        h, w = int(fx.shape[1]), int(fx.shape[2])
+        shape, want = (b, h, w, c), PREC_DTYPE[p]
+    for name, t, sh, dt in (("fx", fx, shape, want), ("fy", fy, shape, want), ("q", q, (8, b, c), torch.float32),
+                            ("wgt", wgt, (b, c), torch.float32)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"adists_window_stage: {name} must be contiguous {dt} {sh}, got {t.dtype} {tuple(t.shape)}"
+                             f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    windowed = h >= WINDOW and w >= WINDOW
+    out = (b, h - WINDOW + 1, w - WINDOW + 1) if windowed else (b, 1, 1)
+    if strip < 0 or (windowed and strip > out[1]):
+        raise ValueError(f"adists_window_stage: strip {strip} outside [0, {out[1] if windowed else 0}]")
+    return b, h, w, c, out
+
+
+def adists_window_stage(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, prec, strip: int = 0):
+    """One stage of the A-DISTS heavy pass as adists_forward launches it (include/nqa.h, nqa_adists_window_stage):
+    (gamma, tw, sw), each (B, H-20, W-20) float32, or (B, 1, 1) from the global branch when H or W is under 21.
+    q (8,B,C) and wgt (B,C) float32; fx, fy (B,3,H,W) float32 planes for C == 3, else (B,H,W,C) NHWC taps in prec's
+    storage type.  strip: see the header (0 = the launcher's choice)."""
+    _need_cuda(fx, fy, q, wgt)
+    out_shape = _window_stage_dims(fx, fy, q, wgt, prec_id(prec), int(strip))[4]
+    out = torch.empty((3,) + out_shape, dtype=torch.float32, device=fx.device)
+    adists_window_stage_into(fx, fy, q, wgt, prec, strip, out[0], out[1], out[2])
+    return out[0], out[1], out[2]
+
+
+def adists_window_stage_into(fx, fy, q, wgt, prec, strip, gamma, tw, sw) -> None:
+    """adists_window_stage into caller-owned contiguous float32 maps of the shape it would return (tests place them
+    between guard regions).  Every check of adists_window_stage applies."""
+    p, strip = prec_id(prec), int(strip)
+    dev = _need_cuda(fx, fy, q, wgt, gamma, tw, sw)
+    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip)
+    for t in (gamma, tw, sw):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"adists_window_stage: outputs must be contiguous float32 {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    _call(dev, lib().nqa_adists_window_stage, ptr(fx), ptr(fy), b, h, w, c, p, ptr(q), ptr(wgt), strip, ptr(gamma),
+          ptr(tw), ptr(sw), stream_ptr(dev))
+
+
+def adists_window_grid(b: int, h: int, w: int, c: int, prec, strip: int = 0) -> tuple:
+    """(column groups, row strips, strip height) of the LDS window kernel for these arguments under the calling thread's
+    conv variant, from the launcher's own function; zeros where another kernel would run."""
+    g = (C.c_int * 3)()
+    check(lib().nqa_adists_window_grid(int(b), int(h), int(w), int(c), prec_id(prec), int(strip), g))
+    return tuple(g)
+
+
 # ---- input preparation (SURVEY.md section 8 f2) ---------------------------------------------------
 def u8hwc_to_f32nchw(frames: torch.Tensor, pil_roundtrip: bool = False) -> torch.Tensor:
     """ToTensor on the device: uint8 (n,H,W,3) -> float32 (n,3,H,W) / 255 (prep.py:89, data.py:80)."""
