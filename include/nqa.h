@@ -318,7 +318,13 @@ int nqa_conv_pool_stats(const void *in, int B, int H, int W, int layer, const vo
  * pool + statistics pass over the tap it wrote) instead of conv + L2-pool + statistics in one kernel (nqa_conv_pool.hip);
  * adding 128 does the same for stage 1 (conv1_regw_kernel + pool_stats_kernel instead of nqa_conv1_pool.hip's kernel);
  * adding 8 selects the first form of the A-DISTS window pass (every wave loads its own taps instead of sharing them
- * through LDS).  Results agree in every variant to the rounding of a different summation order inside a layer (the
+ * through LDS).  Bits 8-9 choose the implicit GEMM's grid on maps whose last 32-wide tile column is at most half full
+ * (1 <= W % 32 <= 16): by default such a layer takes ONE launch of 32-wide tiles plus 16-wide tiles down the right edge
+ * (conv3x3_igemm_mixed_kernel) wherever that needs fewer rounds of blocks over the chip than the plain grid of 32-wide
+ * tiles; adding 256 keeps the plain grid everywhere (A/B runs), adding 512 takes the mixed grid on every such map
+ * whatever the block count (so tests reach it at small sizes); 256 + 512 is refused.  The two grids are bit-identical.
+ * nqa_set_conv_variant(1024) is a query: it changes nothing and returns how many mixed grids the calling thread has
+ * launched since it last asked (>= 0).  Results agree in every variant to the rounding of a different summation order inside a layer (the
  * tile variants are bit-identical); this only exists so they can be timed against each other in one process.
  * The choice is thread-local (it applies to the calling thread's later calls only). */
 int nqa_set_conv_variant(int variant);

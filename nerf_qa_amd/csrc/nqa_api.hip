@@ -403,7 +403,8 @@ int nqa_version(void) { return NQA_VERSION; }
 const char *nqa_last_error(void) { return g_err; }
 
 int nqa_set_conv_variant(int variant) {
-  if (variant < 0 || variant > 255 || (variant & 3) == 3) {
+  if (variant == 1024) return take_mixed_grid_launches();  // the query: changes nothing
+  if (variant < 0 || variant > 1023 || (variant & 3) == 3 || (variant & 768) == 768) {
     set_error("set_conv_variant: unknown variant %d", variant);
     return NQA_E_ARG;
   }
@@ -412,6 +413,7 @@ int nqa_set_conv_variant(int variant) {
   set_conv_first_forms((variant >> 4) & 3);
   set_fuse_taps((variant & 64) ? 0 : 1);
   set_fuse_stage1((variant & 128) ? 0 : 1);
+  set_conv_edge_grid((variant >> 8) & 3);
   return NQA_OK;
 }
 

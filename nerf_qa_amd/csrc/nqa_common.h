@@ -238,6 +238,8 @@ size_t max_act_elems(int H, int W);  // largest activation map of the pyramid, e
 // ---- host launchers shared between translation units ---------------------------------
 void set_conv_variant(int v);
 void set_conv_first_forms(int on);
+void set_conv_edge_grid(int mode);  // 0: mixed grid where it saves a round of blocks; 1: plain grids only; 2: mixed wherever it applies
+int take_mixed_grid_launches();     // mixed grids the calling thread has launched since it last asked
 void set_adists_window_legacy(bool on);
 int conv1_1(const float *x, int n, int H, int W, const void *packed, int prec, void *out, hipStream_t st);
 int conv1_fused(const float *x, const float *y, int B, int n, int H, int W, const void *packed, int prec, void *out,

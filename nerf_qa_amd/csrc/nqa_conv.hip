@@ -190,14 +190,15 @@ __host__ __device__ inline int lds_swz(int r) {
 // main one, go to an accumulator of their own and are added once at the end.  The main accumulator is then rounded once
 // per k-step instead of three times -- its rounding is what a 4608-term float sum loses (2.0e-6 of the largest output at
 // 512 input channels with one accumulator; the operands themselves are good for 8e-7).
+// conv3x3_igemm_tile is one block's whole work on the TH x TW output patch at (x0, y0) of image n, channel tile ct (all
+// block-uniform); the __global__ kernels below only choose the patch.
 template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16, int NTERM = 1, bool LOACC = false>
-__global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
-    const typename P::T *__restrict__ in, const char *__restrict__ wpk, const float *__restrict__ bias,
-    typename P::T *__restrict__ out, int H, int W, int Cin, int Cout, int tiles_x, int out_split, float floor_v) {
+__device__ __forceinline__ void conv3x3_igemm_tile(
+    const typename P::T *in, const char *wpk, const float *bias, typename P::T *out, int H, int W, int Cin, int Cout,
+    int out_split, float floor_v, const int n, const int x0, const int y0, const int ct, char *const smem) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the LDS-DMA builtin exists in the device pass only
   typedef typename P::T T;
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [A0][A1][W0][W1]
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;  // smem: the block's dynamic LDS, [A0][A1][W0][W1]
 
   const int tid = threadIdx.x, lane = tid & 63;
   // the wave index as a provably wave-uniform (SGPR) value: every LDS-DMA destination is then
@@ -211,17 +212,6 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
 #define NQA_PRIO_SPLIT 2
 #endif
   if (NQA_PRIO_SPLIT && M16 && WAVES_N * WAVES_M == 8 && wave >= 4) __builtin_amdgcn_s_setprio(NQA_PRIO_SPLIT);
-  // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs, so workgroup ids that
-  // are equal mod 8 share an L2.  Give each of those classes a contiguous run of pixel tiles so
-  // that neighbouring tiles' halo overlap is an L2 hit (speed only; any placement is correct).
-  int tile_id = blockIdx.x;
-  {
-    const int nb = gridDim.x, qq = nb >> 3, rr = nb & 7, xcd = tile_id & 7, local = tile_id >> 3;
-    tile_id = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + local;
-  }
-  const int bx = tile_id % tiles_x, by = tile_id / tiles_x;
-  const int n = blockIdx.y, ct = blockIdx.z;
-  const int x0 = bx * TW, y0 = by * G::TH;
   const int wn = wave % WAVES_N, wm = wave / WAVES_N;
   const int nCC = Cin / P::KC;
   const int S = nCC * 3 * NTERM;
@@ -600,6 +590,58 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
     }
   }
 #endif
+}
+
+// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs, so workgroup ids that
+// are equal mod 8 share an L2.  Give each of those classes a contiguous run of pixel tiles so
+// that neighbouring tiles' halo overlap is an L2 hit (speed only; any placement is correct).
+// A bijection of [0, nb) for every nb.
+__device__ __forceinline__ int xcd_tile_order(int id, int nb) {
+  const int qq = nb >> 3, rr = nb & 7, xcd = id & 7, local = id >> 3;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + local;
+}
+
+// The plain grid: (pixel tiles of one image, images, channel tiles), every tile TH x TW.
+template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool M16, int NTERM = 1, bool LOACC = false>
+__global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
+    const typename P::T *__restrict__ in, const char *__restrict__ wpk, const float *__restrict__ bias,
+    typename P::T *__restrict__ out, int H, int W, int Cin, int Cout, int tiles_x, int out_split, float floor_v) {
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tile_id = xcd_tile_order(blockIdx.x, gridDim.x);
+  const int bx = tile_id % tiles_x, by = tile_id / tiles_x;
+  conv3x3_igemm_tile<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC>(
+      in, wpk, bias, out, H, W, Cin, Cout, out_split, floor_v, blockIdx.y, bx * TW, by * G::TH, blockIdx.z, smem);
+}
+
+// The mixed grid, for maps whose last 32-wide tile column would be at least half empty (1 <= W % 32 <= 16): blocks
+// [0, n_main) run the 32-wide tile on the columns [0, 32 * main_tx), main_tiles of them per (image, channel tile) in the
+// plain grid's order (tile fastest, then image, then channel tile) and XCD-aware over the whole main region (a one-
+// dimensional grid: block id mod 8 IS the XCD); blocks [n_main, gridDim.x) run the 16-wide tile of the same wave layout
+// and the same pixel count (twice the rows) down the one column strip at x = 32 * main_tx, edge_ty of them per (image,
+// channel tile).  They come last, so they fill the last round of the grid.  The branch is block-uniform; both bodies are
+// the plain kernels' own (same contraction order per pixel: the results are bit-identical to the plain grid's).
+template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, bool M16, int NTERM = 1>
+__global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_mixed_kernel(
+    const typename P::T *__restrict__ in, const char *__restrict__ wpk, const float *__restrict__ bias,
+    typename P::T *__restrict__ out, int H, int W, int Cin, int Cout, int N, int main_tx, int main_tiles, int n_main,
+    int edge_ty, int out_split, float floor_v) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // sized for the larger of the two geometries
+  const int b = blockIdx.x;
+  if (b < n_main) {
+    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32> G;
+    const int g = xcd_tile_order(b, n_main);
+    const int slab = g / main_tiles, tile_id = g - slab * main_tiles;
+    const int bx = tile_id % main_tx, by = tile_id / main_tx;
+    conv3x3_igemm_tile<P, WAVES_N, WAVES_M, WN_T, WM_T, 32, M16, NTERM>(
+        in, wpk, bias, out, H, W, Cin, Cout, out_split, floor_v, slab % N, bx * 32, by * G::TH, slab / N, smem);
+  } else {
+    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16> G;
+    const int e = b - n_main;
+    const int slab = e / edge_ty, by = e - slab * edge_ty;
+    conv3x3_igemm_tile<P, WAVES_N, WAVES_M, WN_T, WM_T, 16, M16, NTERM>(
+        in, wpk, bias, out, H, W, Cin, Cout, out_split, floor_v, slab % N, main_tx * 32, by * G::TH, slab / N, smem);
+  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -2397,9 +2439,19 @@ static thread_local int g_conv_variant = 1;  // 0: 4-wave tiles everywhere; 1: +
 static thread_local int g_stage1_variant = 0;  // 0: persistent two-phase kernel (conv1_fused_kernel); 1: conv1_tile_kernel
 static thread_local int g_no_regw128 = 0;  // 1: conv2_2 / conv3_1 on the implicit GEMM instead of the register-weights kernel (A/B timing)
 static thread_local int g_first_forms = 0;  // 1: the round-1 forms of stage 1 (two-phase kernel) and conv2_1 (implicit GEMM), for A/B timing
+// the grid of the implicit GEMM on maps with 1 <= W % 32 <= 16: 0 = mixed (16-wide tiles on the right edge) where it
+// saves a round of blocks, 1 = plain grids only (A/B timing), 2 = mixed on every such map (tests reach it at small sizes)
+static thread_local int g_edge_grid = 0;
+static thread_local int g_mixed_launches = 0;  // mixed grids this thread has launched since it last asked
 void set_conv_variant(int v) {
   g_conv_variant = v & 3;
   g_stage1_variant = (v >> 2) & 1;
+}
+void set_conv_edge_grid(int mode) { g_edge_grid = mode; }
+int take_mixed_grid_launches() {
+  const int c = g_mixed_launches;
+  g_mixed_launches = 0;
+  return c;
 }
 bool mixed_stage1_unfused() { return g_first_forms != 0; }
 void set_conv_first_forms(int on) {
@@ -2444,6 +2496,54 @@ static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, 
 
 // compute units of the current device (cached per device: a process may drive several)
 static int num_cus();
+
+// Whether a layer on 32-wide tiles of MP pixels takes the mixed grid (conv3x3_igemm_mixed_kernel).  Counted, not named:
+// the plain grid is cdiv(W, 32) tile columns of cdiv(H, MP/32) tiles, the mixed one floor(W / 32) such columns plus one
+// of cdiv(H, MP/16) 16-wide tiles; it is taken where that needs fewer rounds of `slots` = CUs x blocks per CU (so never
+// below one full round: small batches keep the plain grid).  E.g. conv4_x of a 1080p batch of 8 pairs, 135 x 240 x 512
+// on 256 x 256 tiles: 17*8*16*2 = 4352 blocks = 17 rounds of 256 plain, 17*7*16*2 + 9*16*2 = 4096 = 16 rounds mixed.
+static bool use_mixed_grid(int n, int H, int W, int ctiles, int MP, int blocks_per_cu) {
+  const int rem = W % 32;
+  if (g_edge_grid == 1 || rem < 1 || rem > 16 || W < 32) return false;
+  if (g_edge_grid == 2) return true;
+  const long slots = (long)num_cus() * blocks_per_cu;
+  if (slots <= 0) return false;
+  const long per = (long)n * ctiles;
+  const long plain = (long)cdiv(W, 32) * cdiv(H, MP / 32) * per;
+  const long mixed = ((long)(W / 32) * cdiv(H, MP / 32) + cdiv(H, MP / 16)) * per;
+  return (mixed + slots - 1) / slots < (plain + slots - 1) / slots;
+}
+
+template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, bool M16 = (sizeof(typename P::T) == 2), int NTERM = 1>
+static int launch_igemm_mixed(const void *in, int n, int H, int W, int cin, int cout, const char *wpk, const float *bias,
+                              void *out, int out_split, hipStream_t st) {
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32> GM;
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16> GE;
+  constexpr int LDS = GM::LDS_BYTES > GE::LDS_BYTES ? GM::LDS_BYTES : GE::LDS_BYTES;
+  static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
+  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
+  if (!attr_done) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
+      set_error("conv3x3_igemm_mixed: cannot raise the dynamic LDS limit to %d bytes", LDS);
+      return NQA_E_LAUNCH;
+    }
+    attr_done = true;
+  }
+  const int main_tx = W / 32, main_tiles = main_tx * cdiv(H, GM::TH), edge_ty = cdiv(H, GE::TH);
+  const long slabs = (long)n * (cout / GM::BN);
+  const long n_main = main_tiles * slabs, n_total = n_main + edge_ty * slabs;
+  if (main_tx < 1 || n_total > 0x7fffffffL) {
+    set_error("conv3x3_igemm_mixed: %d x %d x %d images do not fit the mixed grid", n, H, W);
+    return NQA_E_SHAPE;
+  }
+  TimedLaunch t(NQA_K_CONV, st);
+  conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM><<<dim3((unsigned)n_total), GM::THREADS, LDS, st>>>(
+      reinterpret_cast<const typename P::T *>(in), wpk, bias, reinterpret_cast<typename P::T *>(out), H, W, cin, cout, n,
+      main_tx, main_tiles, (int)n_main, edge_ty, out_split, 0.f);
+  ++g_mixed_launches;
+  return check_launch("conv3x3_igemm_mixed");
+}
 
 // conv2_1 (64 -> 128; NCG = 4) and, on two-term weights, conv1_2 (64 -> 64; NCG = 2) with register-resident
 // weights, 16-bit kernels; persistent, one 8-wave block per CU
@@ -2560,6 +2660,10 @@ static int launch_conv_2term(const void *in, int n, int H, int W, int layer, con
   return narrow ? launch_igemm<P, WN, WM, TN, TM, 16, M16, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st) \
                 : launch_igemm<P, WN, WM, TN, TM, 32, M16, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st)
     if (cs.cout == 64) { NQA_GO2(1, 4, 2, 2, false); }
+    if (!narrow && use_mixed_grid(n, H, W, cs.cout / (big ? 256 : 128), big ? 256 : 128, big ? 1 : 2)) {
+      if (!big) return launch_igemm_mixed<P, 2, 2, 2, 2, true, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st);
+      return launch_igemm_mixed<P, 2, 4, 4, 2, true, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st);
+    }
     if (!big) { NQA_GO2(2, 2, 2, 2, true); }
     NQA_GO2(2, 4, 4, 2, true);
 #undef NQA_GO2
@@ -2622,6 +2726,11 @@ static int launch_conv(const void *in, int n, int H, int W, int layer, const cha
       if ((layer == 3 || layer == 4) && !g_no_regw128 && !g_first_forms && W >= 16)
         return launch_regw128<P>(in, n, H, W, layer, packed, out, st);
     }
+  }
+  // a right edge that fills at most half of a 32-wide tile: 16-wide tiles there, in the same launch, where that saves a round
+  if (!narrow && use_mixed_grid(n, H, W, cs.cout / (big ? 256 : 128), big ? 256 : 128, big ? 1 : 2)) {
+    if (!big) return launch_igemm_mixed<P, 2, 2, 2, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
+    return launch_igemm_mixed<P, 2, 4, 4, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
   }
   if (!big) { NQA_GO(2, 2, 2, 2); }                             // 128 ch x 128 px, 4 waves
   NQA_GO(2, 4, 4, 2);                                           // 256 ch x 256 px, 8 waves

@@ -357,8 +357,19 @@ def dists_score(s1: torch.Tensor, s2: torch.Tensor, alpha: torch.Tensor, beta: t
 DEFAULT_CONV_VARIANT = 1  # the library's start-up value (include/nqa.h)
 
 
+CONV_PLAIN_GRID, CONV_MIXED_GRID = 256, 512  # implicit-GEMM grid on maps with 1 <= W % 32 <= 16: never / always mixed
+
+
 def set_conv_variant(v: int) -> None:
     check(lib().nqa_set_conv_variant(int(v)))
+
+
+def mixed_grid_launches() -> int:
+    """Mixed-grid conv launches (32-wide tiles + 16-wide edge tiles) of this thread since the last call."""
+    n = lib().nqa_set_conv_variant(1024)
+    if n < 0:
+        check(n)
+    return n
 
 
 def dists_fused_taps(b: int, h: int, w: int, prec) -> tuple:
