@@ -16,7 +16,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "nqa_common.h"
+#include "nqa_stages.h"
 
 namespace nqa {
 
@@ -24,9 +24,7 @@ static constexpr int kWin = 21;
 static constexpr int kChainBlocks = 1024;  // most blocks per image of the chain's reduction kernels
 
 // tuning hook (nqa_set_conv_variant bit 3): the per-wave-loads form of the window pass, kept for A/B timing
-static thread_local bool g_window_legacy = false;
-void set_adists_window_legacy(bool on) { g_window_legacy = on; }
-static bool adists_window_legacy() { return g_window_legacy; }
+static bool adists_window_legacy() { return tuning().window_legacy; }
 
 struct Gauss {
   float g[kWin];
@@ -1214,40 +1212,17 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
 
   // ---- pyramids (x images [0,B), y images [B,2B)) with the global statistics per tap ----
   if ((rc = stats_nchw(x, y, B, 3, H * W, part + p.sd.part_off[0], st))) return rc;
-  // (f32s: conv1_regw_split_kernel, as in nqa_api.hip's run_stages; frames in f32s are >= 128 x 128 pixels under the
-  // default `auto`, far from the tiny-frame knife edge that made a conv1_1 rounding pattern matter, section 4.4)
-  const bool fused_s = prec == NQA_PREC_F32S && !mixed_stage1_unfused();
-  const bool fused1 = prec_elem_bytes(prec) == 2 || fused_s;
-  if (!fused1) {
-    if ((rc = conv1_1(x, B, H, W, packed, prec, base + p.bufA, st))) return rc;
-    if ((rc = conv1_1(y, B, H, W, packed, prec, base + p.bufA + (size_t)B * H * W * 64 * esz, st))) return rc;
-  }
-  {
-    // same chaining as nqa_vgg_pyramid, taps kept
-    void *bufA = base + p.bufA, *bufB = base + p.bufB, *cur = bufA;
-    for (int layer = 1; layer < NQA_NUM_CONVS; ++layer) {
-      const ConvSpec &cs = kConvs[layer];
-      const int k = cs.stage;
-      void *dst = cs.last ? taps[k] : (cur == bufA ? bufB : bufA);
-      if (layer == 1 && fused1) {
-        if ((rc = fused_s ? conv1_fused_split(x, y, B, 2 * B, H, W, packed, dst, st)
-                          : conv1_fused(x, y, B, 2 * B, H, W, packed, prec, dst, st)))
-          return rc;
-      } else if ((rc = conv3x3(cur, 2 * B, p.h[k + 1], p.w[k + 1], layer, packed, prec, dst, st))) {
-        return rc;
-      }
-      cur = dst;
-      if (cs.last) {
-        double *pk = part + p.sd.part_off[k + 1];
-        if (k < 4) {
-          if ((rc = pool_stats(cur, B, p.h[k + 1], p.w[k + 1], cs.cout, prec, bufA, pk, st))) return rc;
-          cur = bufA;
-        } else if ((rc = stats_nhwc(cur, B, p.h[k + 1] * p.w[k + 1], cs.cout, prec, pk, st))) {
-          return rc;
-        }
-      }
-    }
-  }
+  // (f32s stage 1 is conv1_regw_split_kernel: frames in f32s are >= 128 x 128 pixels under the default `auto`, far from
+  // the tiny-frame knife edge that made a conv1_1 rounding pattern matter, section 4.4)
+  rc = run_stages(x, y, B, base + p.bufA, base + p.bufB, 2 * B, H, W, packed, prec, taps,
+                  [&](int k, void *tap, int hk, int wk, int ck, void *pool_dst) {
+                    double *pk = part + p.sd.part_off[k + 1];
+                    if (!pool_dst) return stats_nhwc(tap, B, hk * wk, ck, prec, pk, st);
+                    const int rc2 = pool_stats(tap, B, hk, wk, ck, prec, pool_dst, pk, st);
+                    return rc2 ? rc2 : 1;
+                  },
+                  st);
+  if (rc) return rc;
   // ---- DISTS' S1 / S2 from the same sums (nqa_adists_dists_forward only).  `part` is complete here and nothing
   // below writes it: adists_prep_kernel reads it, hsum reuses rows of q, the chain's `ones` lives in bufB ----
   if (s1_out && (rc = finalize(part, p.sd, B, s1_out, s2_out, st))) return rc;

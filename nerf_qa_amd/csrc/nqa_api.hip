@@ -8,7 +8,7 @@
 #include <thread>
 #include <vector>
 
-#include "nqa_common.h"
+#include "nqa_stages.h"
 
 namespace nqa {
 
@@ -29,6 +29,12 @@ int check_launch(const char *what) {
     return NQA_E_LAUNCH;
   }
   return NQA_OK;
+}
+
+// ---- tuning state (nqa_common.h) ---------------------------------------------------
+Tuning &tuning() {
+  static thread_local Tuning t;
+  return t;
 }
 
 // ---- timing ring ------------------------------------------------------------------
@@ -171,20 +177,6 @@ static int weight_scale_exp(const float *w, size_t count) {
 }
 
 // ---- drivers ----------------------------------------------------------------------------
-struct PyrDims {
-  int h[5], w[5];
-};
-static PyrDims pyr_dims(int H, int W) {
-  PyrDims d;
-  d.h[0] = H;
-  d.w[0] = W;
-  for (int k = 1; k < 5; ++k) {
-    d.h[k] = (d.h[k - 1] + 1) / 2;
-    d.w[k] = (d.w[k - 1] + 1) / 2;
-  }
-  return d;
-}
-
 // Elements of the largest activation map of the pyramid, per image.  For ordinary frames that is
 // stage 1 (H*W*64), but the maps shrink by ceil(./2) while the channels double, so below ~8 pixels
 // a side a LATER stage is the largest (a 1x1 frame: 64 elements at stage 1, 512 at stages 4 and 5);
@@ -215,119 +207,6 @@ static size_t act_bytes(int n, int H, int W, int prec) {
     return align_up((size_t)n * m, 256);
   }
   return align_up((size_t)n * max_act_elems(H, W) * prec_elem_bytes(prec), 256);
-}
-
-// Runs the 13 convs and the four L2-pools on `n` images: images [0,nx) come from x, the rest from
-// y (fp32 NCHW).  Stage 1 is the fused conv1_1+conv1_2 kernel in the 16-bit modes and two kernels
-// in f32.  Stage k's last conv writes into taps[k] when taps is given, else into the ping-pong pair.
-// on_tap(k, tap, Hk, Wk, Ck, pool_dst) is called once that conv is enqueued; pool_dst is where
-// the stage's L2-pool output must go (null after stage 5).  It returns 1 if it pooled the tap
-// itself (the fused pool+statistics pass), 0 to have the plain L2-pool run, <0 on error.
-// fuse_tap(k, in, Hk, Wk, layer, pool_dst): the DISTS path's offer to run stage k's LAST conv, its L2-pool and its
-// statistics as one kernel (nqa_conv_pool.hip); it returns 1 if it did, 0 to decline (then the conv, on_tap and the
-// pool run as usual), < 0 on error.  Only asked when the batch is x | y pairs (n == 2 * nx) and no taps are wanted.
-struct NoFuse {
-  int operator()(int, const void *, int, int, int, void *) const { return 0; }
-};
-// fuse_stage1(pool_dst): the same offer for the whole of stage 1 (nqa_conv1_pool.hip: normalisation, conv1_1, conv1_2,
-// L2-pool and the statistics of tap 1 from the raw images); 1 = done, `pool_dst` holds the pooled relu1_2.
-struct NoFuse1 {
-  int operator()(void *) const { return 0; }
-};
-template <typename F, typename FU = NoFuse, typename FS = NoFuse1>
-static int run_stages(const float *x, const float *y, int nx, void *bufA, void *bufB, int n, int H, int W,
-                      const void *packed, int prec, void *const *taps, F on_tap, hipStream_t st, FU fuse_tap = FU(),
-                      FS fuse_stage1 = FS()) {
-  const PyrDims d = pyr_dims(H, W);
-  void *cur = bufA;
-  int rc;
-  if (is_mixed(prec)) {
-    // mixed mode: conv1_1 exact in float -> half; layers 1..6 the f16 kernels on two-term weights; the pool behind
-    // stage 3 writes split16 records; layers 7..12 the f32s kernels.  on_tap sees the stage's own kernel precision.
-    const bool fused_m = W >= 16 && !mixed_stage1_unfused();
-    if (!fused_m) {  // conv1_1 exact in float -> half, then conv1_2 as a layer of its own
-      if ((rc = conv1_1_blob(x, nx, H, W, packed, prec, NQA_PREC_F16, bufA, st))) return rc;
-      if (n > nx && (rc = conv1_1_blob(y, n - nx, H, W, packed, prec, NQA_PREC_F16,
-                                       static_cast<char *>(bufA) + (size_t)nx * H * W * 64 * 2, st)))
-        return rc;
-    }
-    for (int layer = 1; layer < NQA_NUM_CONVS; ++layer) {
-      const ConvSpec &cs = kConvs[layer];
-      const int k = cs.stage, kp = stage_prec(prec, k);
-      void *dst = (cs.last && taps) ? taps[k] : (cur == bufA ? bufB : bufA);
-      if (cs.last && k < 4 && !taps && n == 2 * nx && layer > 1) {
-        if ((rc = fuse_tap(k, cur, d.h[k], d.w[k], layer, dst)) < 0) return rc;
-        if (rc == 1) {  // conv + pool + statistics done: `dst` holds the POOLED map
-          cur = dst;
-          continue;
-        }
-      }
-      if (layer == 1 && fused_m) {
-        if ((rc = conv1_fused_blob(x, y, nx, n, H, W, packed, prec, dst, st))) return rc;
-      } else if ((rc = conv3x3_blob(cur, n, d.h[k], d.w[k], layer, packed, prec, kp, dst, st))) {
-        return rc;
-      }
-      cur = dst;
-      if (cs.last) {
-        void *pdst = k < 4 ? ((cur == bufA) ? bufB : bufA) : nullptr;
-        if ((rc = on_tap(k, cur, d.h[k], d.w[k], cs.cout, pdst)) < 0) return rc;
-        if (k < 4) {
-          if (rc == 0) {
-            const bool boundary = kp == NQA_PREC_F16 && stage_prec(prec, k + 1) == NQA_PREC_F32S;
-            rc = boundary ? l2pool_to_split16(cur, n, d.h[k], d.w[k], cs.cout, pdst, st)
-                          : l2pool(cur, n, d.h[k], d.w[k], cs.cout, kp, pdst, st);
-            if (rc) return rc;
-          }
-          cur = pdst;
-        }
-      }
-    }
-    return NQA_OK;
-  }
-  // f32s: conv1_regw_split_kernel (three-term products, relu1_1 stays in LDS) unless the first-forms bit asks for the
-  // round-2 pair conv1_1_kernel (VALU, split16 out) + implicit GEMM
-  const bool fused_s = prec == NQA_PREC_F32S && !mixed_stage1_unfused();
-  const bool fused1 = prec_elem_bytes(prec) == 2 || fused_s;
-  int first_layer = 1;
-  if (!taps && n == 2 * nx) {  // stage 1 with its pool and statistics in one kernel: the layer loop starts at conv2_1
-    if ((rc = fuse_stage1(bufA)) < 0) return rc;
-    if (rc == 1) first_layer = 2;
-  }
-  if (!fused1 && first_layer == 1) {
-    if ((rc = conv1_1(x, nx, H, W, packed, prec, bufA, st))) return rc;
-    if (n > nx && (rc = conv1_1(y, n - nx, H, W, packed, prec,
-                                static_cast<char *>(bufA) + (size_t)nx * H * W * 64 * prec_elem_bytes(prec), st)))
-      return rc;
-  }
-  for (int layer = first_layer; layer < NQA_NUM_CONVS; ++layer) {
-    const ConvSpec &cs = kConvs[layer];
-    const int k = cs.stage;
-    void *dst = (cs.last && taps) ? taps[k] : (cur == bufA ? bufB : bufA);
-    if (cs.last && k < 4 && !taps && n == 2 * nx && layer > 1) {
-      if ((rc = fuse_tap(k, cur, d.h[k], d.w[k], layer, dst)) < 0) return rc;
-      if (rc == 1) {
-        cur = dst;
-        continue;
-      }
-    }
-    if (layer == 1 && fused1) {
-      if ((rc = fused_s ? conv1_fused_split(x, y, nx, n, H, W, packed, dst, st)
-                        : conv1_fused(x, y, nx, n, H, W, packed, prec, dst, st)))
-        return rc;
-    } else if ((rc = conv3x3(cur, n, d.h[k], d.w[k], layer, packed, prec, dst, st))) {
-      return rc;
-    }
-    cur = dst;
-    if (cs.last) {
-      void *pdst = k < 4 ? ((cur == bufA) ? bufB : bufA) : nullptr;
-      if ((rc = on_tap(k, cur, d.h[k], d.w[k], cs.cout, pdst)) < 0) return rc;
-      if (k < 4) {
-        if (rc == 0 && (rc = l2pool(cur, n, d.h[k], d.w[k], cs.cout, prec, pdst, st))) return rc;
-        cur = pdst;
-      }
-    }
-  }
-  return NQA_OK;
 }
 
 // `chan`: the widest H x W map the call addresses with 32-bit in-image byte offsets (the conv DMA
@@ -403,17 +282,24 @@ int nqa_version(void) { return NQA_VERSION; }
 const char *nqa_last_error(void) { return g_err; }
 
 int nqa_set_conv_variant(int variant) {
-  if (variant == 1024) return take_mixed_grid_launches();  // the query: changes nothing
+  Tuning &t = tuning();
+  if (variant == 1024) {  // the query: changes no choice, and starts the count again
+    const int c = t.mixed_launches;
+    t.mixed_launches = 0;
+    return c;
+  }
   if (variant < 0 || variant > 1023 || (variant & 3) == 3 || (variant & 768) == 768) {
     set_error("set_conv_variant: unknown variant %d", variant);
     return NQA_E_ARG;
   }
-  set_conv_variant(variant & 7);
-  set_adists_window_legacy((variant & 8) != 0);
-  set_conv_first_forms((variant >> 4) & 3);
-  set_fuse_taps((variant & 64) ? 0 : 1);
-  set_fuse_stage1((variant & 128) ? 0 : 1);
-  set_conv_edge_grid((variant >> 8) & 3);
+  t.conv_variant = variant & 3;
+  t.stage1_variant = (variant >> 2) & 1;
+  t.window_legacy = (variant & 8) != 0;
+  t.first_forms = (variant & 16) != 0;
+  t.no_regw128 = (variant & 32) != 0;
+  t.fuse_taps = !(variant & 64);
+  t.fuse_stage1 = !(variant & 128);
+  t.edge_grid = (variant >> 8) & 3;
   return NQA_OK;
 }
 
@@ -646,8 +532,6 @@ int nqa_conv1_1(const float *x, int n, int H, int W, const void *packed, int pre
     return NQA_E_ARG;
   }
   if (bad_dims("conv1_1", n, H, W, prec, 64, true, 0)) return NQA_E_ARG;
-  if (is_mixed(prec))  // what run_stages calls where it does not fuse stage 1: the exact float conv, half out
-    return conv1_1_blob(x, n, H, W, packed, prec, NQA_PREC_F16, out, static_cast<hipStream_t>(stream));
   return conv1_1(x, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
 }
 
@@ -657,15 +541,12 @@ int nqa_conv1_fused(const float *x, int n, int H, int W, const void *packed, int
     return NQA_E_ARG;
   }
   if (bad_dims("conv1_fused", n, H, W, prec, 64, true, 0)) return NQA_E_ARG;
-  if (is_mixed(prec)) {  // the fused form exactly where run_stages takes it, never another kernel under its name
-    if (W < 16 || mixed_stage1_unfused()) {
-      set_error("conv1_fused: a mixed mode runs stage 1 fused only for W >= 16 with the first-forms bit of "
-                "nqa_set_conv_variant clear (W = %d): nqa_conv1_1 + nqa_conv3x3_relu(layer 1) otherwise", W);
-      return NQA_E_SHAPE;
-    }
-    return conv1_fused_blob(x, nullptr, n, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
+  // a mixed mode: the fused form exactly where run_stages takes it, never another kernel under its name
+  if (is_mixed(prec) && !stage1_is_fused(prec, W)) {
+    set_error("conv1_fused: a mixed mode runs stage 1 fused only for W >= 16 with the first-forms bit of "
+              "nqa_set_conv_variant clear (W = %d): nqa_conv1_1 + nqa_conv3x3_relu(layer 1) otherwise", W);
+    return NQA_E_SHAPE;
   }
-  if (prec == NQA_PREC_F32S) return conv1_fused_split(x, nullptr, n, n, H, W, packed, out, static_cast<hipStream_t>(stream));
   return conv1_fused(x, nullptr, n, n, H, W, packed, prec, out, static_cast<hipStream_t>(stream));
 }
 
@@ -682,9 +563,6 @@ int nqa_conv3x3_relu(const void *in, int n, int H, int W, int layer, const void 
   if (bad_dims("conv3x3_relu", n, H, W, prec, kConvs[layer].cin > kConvs[layer].cout ? kConvs[layer].cin : kConvs[layer].cout,
                true, kConvs[layer].stage))
     return NQA_E_ARG;
-  if (is_mixed(prec))  // the layer as run_stages runs it: the stage's kernels on the mixed blob's rows
-    return conv3x3_blob(in, n, H, W, layer, packed, prec, stage_prec(prec, kConvs[layer].stage), out,
-                        static_cast<hipStream_t>(stream));
   return conv3x3(in, n, H, W, layer, packed, prec, out, static_cast<hipStream_t>(stream));
 }
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/nqa.h"
 
 namespace nqa {
@@ -235,28 +237,48 @@ __device__ inline PlaneMoments plane_moments(const double *__restrict__ part, co
 
 size_t max_act_elems(int H, int W);  // largest activation map of the pyramid, elements per image (nqa_api.hip)
 
+// ---- launch preparation (nqa_conv.hip) ---------------------------------------------------
+int current_device();  // a failing hipGetDevice reads as device 0
+// compute units of the current device, cached per device (a process may drive several); 0 if the device cannot be
+// queried, with "<who>: cannot query the device" as the error when `who` is given
+int num_cus(const char *who);
+int raise_lds_limit(const void *kernel, std::atomic<bool> *done_dev, int bytes, const char *who);
+// Raises the dynamic-LDS limit of kernel K to `bytes`, once per device (the attribute is per device) and per
+// instantiation: the flags belong to K.  NQA_OK, or NQA_E_LAUNCH with the error set under the kernel's name `who`.
+template <auto K>
+static int lds_limit(int bytes, const char *who) {
+  static std::atomic<bool> done_dev[64];
+  return raise_lds_limit(reinterpret_cast<const void *>(K), done_dev, bytes, who);
+}
+
+// ---- tuning state: what nqa_set_conv_variant decodes (include/nqa.h), A/B switches for the tools and tests ----
+// One object per thread (nqa_api.hip): a choice made by one thread never changes what another thread's calls launch.
+struct Tuning {
+  int conv_variant = 1;        // bits 0-1.  0: 4-wave tiles everywhere; 1: + 8-wave 256x256 tiles; 2: + 8-wave 128x512 tiles
+  int stage1_variant = 0;      // bit 2.  0: persistent kernels (conv1_regw_kernel / conv1_fused_kernel); 1: conv1_tile_kernel
+  bool window_legacy = false;  // bit 3: the first form of the A-DISTS window pass (no sharing through LDS)
+  bool first_forms = false;    // bit 4: the round-1 forms of stage 1 (two-phase kernel) and conv2_1 (implicit GEMM)
+  bool no_regw128 = false;     // bit 5: conv2_2 / conv3_1 on the implicit GEMM instead of the register-weights kernel
+  bool fuse_taps = true;       // bit 6 clear: conv2_2 + L2-pool + statistics in one kernel (nqa_conv_pool.hip)
+  bool fuse_stage1 = true;     // bit 7 clear: stage 1 + L2-pool + statistics in one kernel (nqa_conv1_pool.hip)
+  // bits 8-9, the grid of the implicit GEMM on maps with 1 <= W % 32 <= 16: 0 = mixed (16-wide tiles on the right
+  // edge) where it saves a round of blocks, 1 = plain grids only, 2 = mixed on every such map (tests, at small sizes)
+  int edge_grid = 0;
+  int mixed_launches = 0;  // mixed grids this thread has launched since it last asked (variant 1024)
+};
+Tuning &tuning();
+
 // ---- host launchers shared between translation units ---------------------------------
-void set_conv_variant(int v);
-void set_conv_first_forms(int on);
-void set_conv_edge_grid(int mode);  // 0: mixed grid where it saves a round of blocks; 1: plain grids only; 2: mixed wherever it applies
-int take_mixed_grid_launches();     // mixed grids the calling thread has launched since it last asked
-void set_adists_window_legacy(bool on);
+// The conv entry points take the BLOB's mode `prec`, plain or mixed, and run the layer with the kernels of its own
+// stage (stage_prec / layer_terms: in a mixed mode F16 on two-term weights up to the boundary, F32S behind it).
 int conv1_1(const float *x, int n, int H, int W, const void *packed, int prec, void *out, hipStream_t st);
+// stage 1 (conv1_1 + conv1_2) of images [x(0..B), y(0..n-B)) in one kernel; every mode but NQA_PREC_F32 has one
 int conv1_fused(const float *x, const float *y, int B, int n, int H, int W, const void *packed, int prec, void *out,
                 hipStream_t st);
+// whether the pyramid runs stage 1 of W-wide frames as conv1_fused (else conv1_1 followed by layer 1)
+bool stage1_is_fused(int prec, int W);
+// an F32S layer leaves plain float where it is tapped, split16 records otherwise
 int conv3x3(const void *in, int n, int H, int W, int layer, const void *packed, int prec, void *out, hipStream_t st);
-// one conv layer of a blob packed for `blob_prec` run by the kernels of `kprec` (mixed mode: F16 with two-term
-// weights for layers 1..6, F32S for the rest); out_float: an F32S layer leaves plain float (a tapped map)
-int conv3x3_blob(const void *in, int n, int H, int W, int layer, const void *packed, int blob_prec, int kprec,
-                 void *out, hipStream_t st);
-int conv1_1_blob(const float *x, int n, int H, int W, const void *packed, int blob_prec, int kprec, void *out,
-                 hipStream_t st);
-int conv1_fused_blob(const float *x, const float *y, int B, int n, int H, int W, const void *packed, int blob_prec,
-                     void *out, hipStream_t st);
-bool mixed_stage1_unfused();  // (A/B switch of nqa_set_conv_variant's first-forms bit)
-// stage 1 of an f32s blob in one kernel (three-term products, float NHWC out), images [x(0..B), y(0..n-B))
-int conv1_fused_split(const float *x, const float *y, int B, int n, int H, int W, const void *packed, void *out,
-                      hipStream_t st);
 int relu_mask_split16(const float *g, const void *act, int act_split, long npix, int C, void *out, hipStream_t st);
 int l2pool_backward(const float *x, const void *y_split16, const float *gy, int n, int H, int W, int C, float *gx,
                     hipStream_t st);
@@ -308,8 +330,6 @@ int nhwc_to_nchw(const void *in, int n, int HW, int C, int prec, float *out, hip
 // rows of statistics partials a fused tap reserves per pair (= the largest grid the fused kernel runs; unwritten rows are zero)
 #define NQA_FUSED_PART_BLOCKS 256
 #define NQA_FUSED_PART_BLOCKS_S1 512  // (the fused stage 1 leaves two rows per block)
-void set_fuse_taps(int on);
-void set_fuse_stage1(int on);
 int pool_seam_finish(const float *seam, void *pooled, int nimg, int strips, int Ho, int Wo, int C, hipStream_t st);
 bool conv1_pool_fusable(int B, int H, int W, int blob_prec);
 int conv1_pool_stats_fused(const float *x, const float *y, int B, int H, int W, const void *packed, void *pooled, float *seam,

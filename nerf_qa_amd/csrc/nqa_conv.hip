@@ -22,7 +22,6 @@
 // Three more kernels live here: conv1_fused_kernel and conv1_tile_kernel (stage 1 without its HBM
 // intermediate, two forms) and the precision variants of the implicit GEMM (f32: exact-f32 MFMA;
 // f32s: split-f16 products on split16 activations; 16-bit: v_mfma_f32_16x16x32).
-#include <atomic>
 
 #include "nqa_common.h"
 
@@ -2428,35 +2427,38 @@ extern "C" int nqa_debug_stamps(unsigned long long *out8, int reset) {
 }
 #endif
 
-static int current_device() {
+// ---- launch preparation (nqa_common.h) ----
+int current_device() {
   int dev = 0;
   return hipGetDevice(&dev) == hipSuccess ? dev : 0;
 }
 
-// thread-local: a tuning choice made by one thread (tools timing variants against each other) never changes what
-// another thread's calls launch
-static thread_local int g_conv_variant = 1;  // 0: 4-wave tiles everywhere; 1: + 8-wave 256x256 tiles; 2: + 8-wave 128x512 tiles
-static thread_local int g_stage1_variant = 0;  // 0: persistent two-phase kernel (conv1_fused_kernel); 1: conv1_tile_kernel
-static thread_local int g_no_regw128 = 0;  // 1: conv2_2 / conv3_1 on the implicit GEMM instead of the register-weights kernel (A/B timing)
-static thread_local int g_first_forms = 0;  // 1: the round-1 forms of stage 1 (two-phase kernel) and conv2_1 (implicit GEMM), for A/B timing
-// the grid of the implicit GEMM on maps with 1 <= W % 32 <= 16: 0 = mixed (16-wide tiles on the right edge) where it
-// saves a round of blocks, 1 = plain grids only (A/B timing), 2 = mixed on every such map (tests reach it at small sizes)
-static thread_local int g_edge_grid = 0;
-static thread_local int g_mixed_launches = 0;  // mixed grids this thread has launched since it last asked
-void set_conv_variant(int v) {
-  g_conv_variant = v & 3;
-  g_stage1_variant = (v >> 2) & 1;
+int num_cus(const char *who) {
+  static std::atomic<int> cus[64];  // (concurrent first calls both query and store the same value)
+  const int dev = current_device() & 63;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+      if (who) set_error("%s: cannot query the device", who);
+      return 0;
+    }
+    n = prop.multiProcessorCount;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
-void set_conv_edge_grid(int mode) { g_edge_grid = mode; }
-int take_mixed_grid_launches() {
-  const int c = g_mixed_launches;
-  g_mixed_launches = 0;
-  return c;
-}
-bool mixed_stage1_unfused() { return g_first_forms != 0; }
-void set_conv_first_forms(int on) {
-  g_first_forms = on & 1;
-  g_no_regw128 = (on >> 1) & 1;
+
+int raise_lds_limit(const void *kernel, std::atomic<bool> *done_dev, int bytes, const char *who) {
+  std::atomic<bool> &done = done_dev[current_device() & 63];
+  if (!done) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+      set_error("%s: cannot raise the dynamic LDS limit to %d bytes", who, bytes);
+      return NQA_E_LAUNCH;
+    }
+    done = true;
+  }
+  return NQA_OK;
 }
 
 template <typename P>
@@ -2475,16 +2477,7 @@ template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool
 static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, const char *wpk, const float *bias,
                         void *out, int out_split, hipStream_t st, float floor_v = 0.f) {
   typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
-  static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) {
-      set_error("conv3x3_igemm: cannot raise the dynamic LDS limit to %d bytes", G::LDS_BYTES);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
+  if (const int rc = lds_limit<conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC>>(G::LDS_BYTES, "conv3x3_igemm")) return rc;
   const int tiles_x = cdiv(W, TW), tiles_y = cdiv(H, G::TH);
   dim3 grid(tiles_x * tiles_y, n, cout / G::BN);
   TimedLaunch t(NQA_K_CONV, st);
@@ -2494,9 +2487,6 @@ static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, 
   return check_launch("conv3x3_igemm");
 }
 
-// compute units of the current device (cached per device: a process may drive several)
-static int num_cus();
-
 // Whether a layer on 32-wide tiles of MP pixels takes the mixed grid (conv3x3_igemm_mixed_kernel).  Counted, not named:
 // the plain grid is cdiv(W, 32) tile columns of cdiv(H, MP/32) tiles, the mixed one floor(W / 32) such columns plus one
 // of cdiv(H, MP/16) 16-wide tiles; it is taken where that needs fewer rounds of `slots` = CUs x blocks per CU (so never
@@ -2504,9 +2494,10 @@ static int num_cus();
 // on 256 x 256 tiles: 17*8*16*2 = 4352 blocks = 17 rounds of 256 plain, 17*7*16*2 + 9*16*2 = 4096 = 16 rounds mixed.
 static bool use_mixed_grid(int n, int H, int W, int ctiles, int MP, int blocks_per_cu) {
   const int rem = W % 32;
-  if (g_edge_grid == 1 || rem < 1 || rem > 16 || W < 32) return false;
-  if (g_edge_grid == 2) return true;
-  const long slots = (long)num_cus() * blocks_per_cu;
+  const int edge_grid = tuning().edge_grid;
+  if (edge_grid == 1 || rem < 1 || rem > 16 || W < 32) return false;
+  if (edge_grid == 2) return true;
+  const long slots = (long)num_cus(nullptr) * blocks_per_cu;
   if (slots <= 0) return false;
   const long per = (long)n * ctiles;
   const long plain = (long)cdiv(W, 32) * cdiv(H, MP / 32) * per;
@@ -2520,16 +2511,7 @@ static int launch_igemm_mixed(const void *in, int n, int H, int W, int cin, int 
   typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32> GM;
   typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16> GE;
   constexpr int LDS = GM::LDS_BYTES > GE::LDS_BYTES ? GM::LDS_BYTES : GE::LDS_BYTES;
-  static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv3x3_igemm_mixed: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
+  if (const int rc = lds_limit<conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM>>(LDS, "conv3x3_igemm_mixed")) return rc;
   const int main_tx = W / 32, main_tiles = main_tx * cdiv(H, GM::TH), edge_ty = cdiv(H, GE::TH);
   const long slabs = (long)n * (cout / GM::BN);
   const long n_main = main_tiles * slabs, n_total = n_main + edge_ty * slabs;
@@ -2541,7 +2523,7 @@ static int launch_igemm_mixed(const void *in, int n, int H, int W, int cin, int 
   conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM><<<dim3((unsigned)n_total), GM::THREADS, LDS, st>>>(
       reinterpret_cast<const typename P::T *>(in), wpk, bias, reinterpret_cast<typename P::T *>(out), H, W, cin, cout, n,
       main_tx, main_tiles, (int)n_main, edge_ty, out_split, 0.f);
-  ++g_mixed_launches;
+  ++tuning().mixed_launches;
   return check_launch("conv3x3_igemm_mixed");
 }
 
@@ -2551,21 +2533,9 @@ template <typename P, int NCG = 4, int NTERM = 1>
 static int launch_regw(const void *in, int n, int H, int W, int layer, const char *packed, void *out, hipStream_t st,
                        int blob_prec = P::ID) {
   constexpr int LDS = 3 * 2 * 1536 * 16;
-  static std::atomic<bool> attr_done_dev[64];
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_regw_kernel<P, NCG, NTERM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv3x3_regw: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = num_cus();
-  if (!cus) {
-    set_error("conv3x3_regw: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv3x3_regw_kernel<P, NCG, NTERM>>(LDS, "conv3x3_regw")) return rc;
+  const int cus = num_cus("conv3x3_regw");
+  if (!cus) return NQA_E_LAUNCH;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 8), total = n * tiles_x * tiles_y;
   const int grid = total < cus ? total : cus;
   const float *bias = reinterpret_cast<const float *>(packed + layer_bias_offset(layer, blob_prec));
@@ -2580,21 +2550,9 @@ static int launch_regw(const void *in, int n, int H, int W, int layer, const cha
 // conv2_1 in f32s with register-resident (hi, lo) weights; persistent, one 8-wave block per CU
 static int launch_regw_split(const void *in, int n, int H, int W, int layer, const char *packed, void *out, hipStream_t st) {
   constexpr int LDS = 2 * 2 * 204 * 160;  // 130 560
-  static std::atomic<bool> attr_done_dev[64];
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_regw_split_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv3x3_regw_split: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = num_cus();
-  if (!cus) {
-    set_error("conv3x3_regw_split: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv3x3_regw_split_kernel>(LDS, "conv3x3_regw_split")) return rc;
+  const int cus = num_cus("conv3x3_regw_split");
+  if (!cus) return NQA_E_LAUNCH;
   const int cout = kConvs[layer].cout, nh = cout / 64;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 4), total = n * tiles_x * tiles_y;
   // the grid is a multiple of 8 XCDs x the layer's 64-channel halves (blocks of one (XCD, stream) share their tiles)
@@ -2614,21 +2572,9 @@ template <typename P, int NTERM = 1>
 static int launch_regw128(const void *in, int n, int H, int W, int layer, const char *packed, void *out, hipStream_t st,
                           int blob_prec = P::ID) {
   constexpr int LDS = 2 * 4 * 1024 * 16, PF = 3;  // fragments three k-steps ahead (2: -6 %, 4: equal)
-  static std::atomic<bool> attr_done_dev[64];
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_regw128_kernel<P, PF, NTERM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv3x3_regw128: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = num_cus();
-  if (!cus) {
-    set_error("conv3x3_regw128: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv3x3_regw128_kernel<P, PF, NTERM>>(LDS, "conv3x3_regw128")) return rc;
+  const int cus = num_cus("conv3x3_regw128");
+  if (!cus) return NQA_E_LAUNCH;
   const int cout = kConvs[layer].cout, nct = cout / (128 / NTERM);  // channel tiles (blocks) per pixel tile
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 4), total = n * tiles_x * tiles_y * nct;
   int grid = total < cus ? total : cus;
@@ -2643,49 +2589,25 @@ static int launch_regw128(const void *in, int n, int H, int W, int layer, const 
   return check_launch("conv3x3_regw128");
 }
 
-// two-term weights (f16 kernels on an NQA_PREC_F32M blob): the same tile choices on the NTERM = 2 instances; the
-// register-weights kernels hold one-term fragments only, so every layer takes the implicit GEMM here
-template <typename P>
-static int launch_conv_2term(const void *in, int n, int H, int W, int layer, const char *packed, int blob_prec,
-                             const ConvSpec &cs, const char *wpk, const float *bias, void *out, bool narrow, bool big,
-                             hipStream_t st) {
-  if constexpr (sizeof(typename P::T) == 2 && P::ID == NQA_PREC_F16) {
-    // layers 1..4 with the weights in registers, as in the one-term 16-bit modes (first-form bits: the implicit GEMM)
-    if (W >= 16 && !g_first_forms) {
-      if (layer == 1) return launch_regw<P, 2, 2>(in, n, H, W, layer, packed, out, st, blob_prec);
-      if (layer == 2) return launch_regw<P, 4, 2>(in, n, H, W, layer, packed, out, st, blob_prec);
-      if ((layer == 3 || layer == 4) && !g_no_regw128) return launch_regw128<P, 2>(in, n, H, W, layer, packed, out, st, blob_prec);
-    }
-#define NQA_GO2(WN, WM, TN, TM, M16)                                                                                \
-  return narrow ? launch_igemm<P, WN, WM, TN, TM, 16, M16, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st) \
-                : launch_igemm<P, WN, WM, TN, TM, 32, M16, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st)
-    if (cs.cout == 64) { NQA_GO2(1, 4, 2, 2, false); }
-    if (!narrow && use_mixed_grid(n, H, W, cs.cout / (big ? 256 : 128), big ? 256 : 128, big ? 1 : 2)) {
-      if (!big) return launch_igemm_mixed<P, 2, 2, 2, 2, true, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st);
-      return launch_igemm_mixed<P, 2, 4, 4, 2, true, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, 0, st);
-    }
-    if (!big) { NQA_GO2(2, 2, 2, 2, true); }
-    NQA_GO2(2, 4, 4, 2, true);
-#undef NQA_GO2
-  }
-  set_error("conv3x3: two-term weights exist for the f16 kernels only");
-  return NQA_E_ARG;
-}
-
-template <typename P>
-static int launch_conv(const void *in, int n, int H, int W, int layer, const char *packed, void *out, hipStream_t st,
-                       int blob_prec = P::ID) {
+// One conv layer of a blob packed for `blob_prec` by the kernels of P.  NTERM = 2: two-term weights (the f16 kernels on
+// the 16-bit stages of a mixed blob); the same tile choices on the NTERM = 2 instances, which exist for PrecF16 only
+// and have no 128 ch x 512 px tile.
+template <typename P, int NTERM>
+static int launch_conv(const void *in, int n, int H, int W, int layer, const char *packed, int blob_prec, void *out,
+                       hipStream_t st) {
+  static_assert(NTERM == 1 || (NTERM == 2 && P::ID == NQA_PREC_F16), "two-term weights exist for the f16 kernels only");
+  constexpr bool B16 = sizeof(typename P::T) == 2;
+  const Tuning &tn = tuning();
   const ConvSpec &cs = kConvs[layer];
   const char *wpk = packed + layer_offset(layer, blob_prec);
   const float *bias = reinterpret_cast<const float *>(packed + layer_bias_offset(layer, blob_prec));
-  const int nterm = layer_terms(blob_prec, layer);
   const bool narrow = W <= 16;  // 32-wide tiles would be half empty
   const int out_split = P::SPLIT && !cs.last;  // f32s: tapped layers leave as float, the others as split16
   // 8-wave 256 ch x 256 px tiles run ~10 % faster per FLOP than 4-wave 128 x 128 tiles on layers
   // with >= 256 output channels (measured), unless their coarser pixel tiling wastes more than most
   // of that on the map's ragged edge (e.g. 68x120) or the map is narrow.  (An 8-wave 128 ch x 256 px
   // tile for the 128-channel layers measured 5-9 % SLOWER than the 4-wave tile.)
-  bool big = g_conv_variant >= 1 && cs.cout >= 256 && !narrow;
+  bool big = tn.conv_variant >= 1 && cs.cout >= 256 && !narrow;
   if (big) {
     const double eff_big = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 8) * 256.0);
     const double eff_small = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 4) * 128.0);
@@ -2695,83 +2617,60 @@ static int launch_conv(const void *in, int n, int H, int W, int layer, const cha
     const long blocks_big = (long)cdiv(W, 32) * cdiv(H, 8) * n * (cs.cout / 256);
     if (blocks_big < 192) big = false;
   }
-  if (nterm == 2) return launch_conv_2term<P>(in, n, H, W, layer, packed, blob_prec, cs, wpk, bias, out, narrow, big, st);
-  // 8-wave 128 ch x 512 px tiles: the loop is bound by what a CU can take in per clock (weights
-  // 3*BN*64 B + halo per stage), and for the same 64 K accumulators 128 x 512 moves 37.6 KB per
-  // stage where 256 x 256 moves 56 KB and two 128 x 128 blocks move 58 KB.
-  bool wide = g_conv_variant >= 2 && cs.cout >= 128 && !narrow && H >= 12;
-  if (wide) {
-    const double eff_wide = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 16) * 512.0);
-    const double eff_small = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 4) * 128.0);
-    wide = eff_wide * 1.10 >= eff_small;
+  // layers 1..4 with the weights in registers (first-form bits of nqa_set_conv_variant: the implicit GEMM, for A/B
+  // runs).  The fragments live in the 16-bit blobs and, as two-term ones, in the mixed blobs; conv1_2 has two-term
+  // fragments only (one-term, it is the 64-channel tile below, whose packed weights conv1_fused shares).
+  const bool regw = B16 && (NTERM == 2 || blob_prec == P::ID) && W >= 16 && !tn.first_forms;
+  if constexpr (NTERM == 2) {
+    if (regw && layer == 1) return launch_regw<P, 2, 2>(in, n, H, W, layer, packed, out, st, blob_prec);
   }
-#define NQA_GO(WN, WM, TN, TM)                                                                                      \
-  return narrow ? launch_igemm<P, WN, WM, TN, TM, 16>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st) \
-                : launch_igemm<P, WN, WM, TN, TM, 32>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st)
-  if (cs.cout == 64) {  // 64 ch x 256 px, 4 waves; 32x32x16 MFMA: its packed weights are shared with conv1_fused
-    return narrow ? launch_igemm<P, 1, 4, 2, 2, 16, false>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st)
-                  : launch_igemm<P, 1, 4, 2, 2, 32, false>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
-  }
-  if constexpr (!P::SPLIT) {
+#define NQA_GO(WN, WM, TN, TM, ...)                                                                                 \
+  return narrow ? launch_igemm<P, WN, WM, TN, TM, 16, __VA_ARGS__>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out,   \
+                                                                   out_split, st)                                  \
+                : launch_igemm<P, WN, WM, TN, TM, 32, __VA_ARGS__>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out,   \
+                                                                   out_split, st)
+  if (cs.cout == 64) { NQA_GO(1, 4, 2, 2, false, NTERM); }  // 64 ch x 256 px, 4 waves; 32x32x16 MFMA
+  if constexpr (NTERM == 1 && !P::SPLIT) {
+    // 8-wave 128 ch x 512 px tiles: the loop is bound by what a CU can take in per clock (weights
+    // 3*BN*64 B + halo per stage), and for the same 64 K accumulators 128 x 512 moves 37.6 KB per
+    // stage where 256 x 256 moves 56 KB and two 128 x 128 blocks move 58 KB.
+    bool wide = tn.conv_variant >= 2 && cs.cout >= 128 && !narrow && H >= 12;
+    if (wide) {
+      const double eff_wide = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 16) * 512.0);
+      const double eff_small = (double)H * W / ((double)cdiv(W, 32) * cdiv(H, 4) * 128.0);
+      wide = eff_wide * 1.10 >= eff_small;
+    }
     if (wide) return launch_igemm<P, 2, 4, 2, 4, 32>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
-  } else {
-    // conv2_1 in f32s: register-resident (hi, lo) weights (first-form bit of nqa_set_conv_variant: the implicit GEMM)
-    if (layer == 2 && blob_prec == NQA_PREC_F32S && !g_first_forms && W >= 16 && H >= 2)
+  }
+  if constexpr (P::SPLIT) {
+    // conv2_1 in f32s: register-resident (hi, lo) weights
+    if (layer == 2 && blob_prec == NQA_PREC_F32S && !tn.first_forms && W >= 16 && H >= 2)
       return launch_regw_split(in, n, H, W, layer, packed, out, st);
   }
-  if constexpr (sizeof(typename P::T) == 2) {
-    // conv2_1: register-resident weights (first-form bit of nqa_set_conv_variant: the implicit GEMM, for A/B runs)
-    if (blob_prec == P::ID) {  // (their fragments live in the 16-bit blobs only)
-      if (layer == 2 && !g_first_forms && W >= 16) return launch_regw<P, 4, 1>(in, n, H, W, layer, packed, out, st);
-      if ((layer == 3 || layer == 4) && !g_no_regw128 && !g_first_forms && W >= 16)
-        return launch_regw128<P>(in, n, H, W, layer, packed, out, st);
-    }
+  if constexpr (B16) {
+    if (regw && layer == 2) return launch_regw<P, 4, NTERM>(in, n, H, W, layer, packed, out, st, blob_prec);
+    if (regw && (layer == 3 || layer == 4) && !tn.no_regw128)
+      return launch_regw128<P, NTERM>(in, n, H, W, layer, packed, out, st, blob_prec);
   }
   // a right edge that fills at most half of a 32-wide tile: 16-wide tiles there, in the same launch, where that saves a round
   if (!narrow && use_mixed_grid(n, H, W, cs.cout / (big ? 256 : 128), big ? 256 : 128, big ? 1 : 2)) {
-    if (!big) return launch_igemm_mixed<P, 2, 2, 2, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
-    return launch_igemm_mixed<P, 2, 4, 4, 2>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
+    if (!big) return launch_igemm_mixed<P, 2, 2, 2, 2, B16, NTERM>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
+    return launch_igemm_mixed<P, 2, 4, 4, 2, B16, NTERM>(in, n, H, W, cs.cin, cs.cout, wpk, bias, out, out_split, st);
   }
-  if (!big) { NQA_GO(2, 2, 2, 2); }                             // 128 ch x 128 px, 4 waves
-  NQA_GO(2, 4, 4, 2);                                           // 256 ch x 256 px, 8 waves
+  if (!big) { NQA_GO(2, 2, 2, 2, B16, NTERM); }  // 128 ch x 128 px, 4 waves
+  NQA_GO(2, 4, 4, 2, B16, NTERM);                // 256 ch x 256 px, 8 waves
 #undef NQA_GO
-}
-
-// compute units of the current device (cached per device: a process may drive several)
-static int num_cus() {
-  static std::atomic<int> cus[64];  // (concurrent first calls both query and store the same value)
-  const int dev = current_device() & 63;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-    n = prop.multiProcessorCount;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
 }
 
 template <typename P>
 static int launch_conv1_fused(const float *x, const float *y, int B, int n, int H, int W, const char *packed,
                               void *out, hipStream_t st) {
   constexpr int LDS = Conv1Fused::LDS_BYTES;
-  static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_fused_kernel<P>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv1_fused: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int g_num_cus = num_cus();
-  if (!g_num_cus) {
-    set_error("conv1_fused: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv1_fused_kernel<P>>(LDS, "conv1_fused")) return rc;
+  const int cus = num_cus("conv1_fused");
+  if (!cus) return NQA_E_LAUNCH;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 4), total = n * tiles_x * tiles_y;
-  const int grid = cdiv(total, 2) < g_num_cus ? cdiv(total, 2) : g_num_cus;  // one persistent block per CU
+  const int grid = cdiv(total, 2) < cus ? cdiv(total, 2) : cus;  // one persistent block per CU
   const char *w1m = packed + layer0_mfma_offset(P::ID);
   const float *b1 = reinterpret_cast<const float *>(packed + layer_bias_offset(0, P::ID));
   const char *w2 = packed + layer_offset(1, P::ID);
@@ -2787,16 +2686,7 @@ static int launch_conv1_tile(const float *x, const float *y, int B, int n, int H
                              hipStream_t st) {
   typedef Conv1Tile::G G;
   constexpr int LDS = Conv1Tile::LDS_BYTES;
-  static std::atomic<bool> attr_done_dev[64];  // the attribute is per device: a process may drive several
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_tile_kernel<P>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv1_tile: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
+  if (const int rc = lds_limit<conv1_tile_kernel<P>>(LDS, "conv1_tile")) return rc;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, G::TH);
   dim3 grid(tiles_x * tiles_y, n);
   const char *w1m = packed + layer0_mfma_offset(P::ID);
@@ -2813,21 +2703,9 @@ template <typename P, int NTERM = 1>
 static int launch_conv1_regw(const float *x, const float *y, int B, int n, int H, int W, const char *packed, void *out,
                              hipStream_t st, int blob_prec = P::ID) {
   constexpr int LDS = 2 * 2 * 340 * 96 + 2 * 13 * 40 * 8 + NTERM * 4 * 2 * 64 * 16 + 256 + 3 * 512 * 4;
-  static std::atomic<bool> attr_done_dev[64];
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_regw_kernel<P, NTERM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv1_regw: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = num_cus();
-  if (!cus) {
-    set_error("conv1_regw: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv1_regw_kernel<P, NTERM>>(LDS, "conv1_regw")) return rc;
+  const int cus = num_cus("conv1_regw");
+  if (!cus) return NQA_E_LAUNCH;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 8), total = n * tiles_x * tiles_y;
   const int grid = total < cus ? total : cus;
   const float *b1 = reinterpret_cast<const float *>(packed + layer_bias_offset(0, blob_prec));
@@ -2842,25 +2720,13 @@ static int launch_conv1_regw(const float *x, const float *y, int B, int n, int H
   return check_launch("conv1_regw");
 }
 
-int conv1_fused_split(const float *x, const float *y, int B, int n, int H, int W, const void *packed_v, void *out,
-                      hipStream_t st) {
-  const char *packed = static_cast<const char *>(packed_v);
+// stage 1 of an f32s blob in one kernel (three-term products, float NHWC out)
+static int launch_conv1_regw_split(const float *x, const float *y, int B, int n, int H, int W, const char *packed,
+                                   void *out, hipStream_t st) {
   constexpr int LDS = 2 * 2 * 204 * 160 + 2 * 2 * 9 * 40 * 8 + 2 * 4 * 2 * 64 * 16 + 256 + 3 * 320 * 4 + 256;  // 162 816
-  static std::atomic<bool> attr_done_dev[64];
-  std::atomic<bool> &attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_regw_split_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      set_error("conv1_regw_split: cannot raise the dynamic LDS limit to %d bytes", LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = num_cus();
-  if (!cus) {
-    set_error("conv1_regw_split: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv1_regw_split_kernel>(LDS, "conv1_regw_split")) return rc;
+  const int cus = num_cus("conv1_regw_split");
+  if (!cus) return NQA_E_LAUNCH;
   const int tiles_x = cdiv(W, 32), tiles_y = cdiv(H, 4), total = n * tiles_x * tiles_y;
   const int grid = total < cus ? total : cus;
   const float *b1 = reinterpret_cast<const float *>(packed + layer_bias_offset(0, NQA_PREC_F32S));
@@ -2873,17 +2739,29 @@ int conv1_fused_split(const float *x, const float *y, int B, int n, int H, int W
   return check_launch("conv1_regw_split");
 }
 
-// stage 1 (conv1_1 + conv1_2) of images [x(0..B), y(0..n-B)) in one kernel; 16-bit modes only
+// Whether the pyramid runs stage 1 of W-wide frames in mode `prec` as conv1_fused: the 16-bit modes always, f32s and the
+// mixed modes unless the first-forms bit of nqa_set_conv_variant asks for the pair of kernels, the mixed modes for
+// W >= 16 only; f32 never.  Otherwise stage 1 is conv1_1 followed by layer 1.
+bool stage1_is_fused(int prec, int W) {
+  if (is_mixed(prec)) return W >= 16 && !tuning().first_forms;
+  if (prec == NQA_PREC_F32S) return !tuning().first_forms;
+  return prec_elem_bytes(prec) == 2;
+}
+
 int conv1_fused(const float *x, const float *y, int B, int n, int H, int W, const void *packed, int prec, void *out,
                 hipStream_t st) {
   const char *p = static_cast<const char *>(packed);
-  if (g_stage1_variant == 1) {
+  // a mixed mode: two-term conv1_1 and conv1_2 in the f16 kernel; f32s: three-term products, float out
+  if (is_mixed(prec)) return launch_conv1_regw<PrecF16, 2>(x, y, B, n, H, W, p, out, st, prec);
+  if (prec == NQA_PREC_F32S) return launch_conv1_regw_split(x, y, B, n, H, W, p, out, st);
+  const Tuning &tn = tuning();
+  if (tn.stage1_variant == 1) {
     switch (prec) {
       case NQA_PREC_BF16: return launch_conv1_tile<PrecBF16>(x, y, B, n, H, W, p, out, st);
       case NQA_PREC_F16: return launch_conv1_tile<PrecF16>(x, y, B, n, H, W, p, out, st);
     }
   }
-  if (g_stage1_variant == 0 && !g_first_forms) {  // the shipped form
+  if (tn.stage1_variant == 0 && !tn.first_forms) {  // the shipped form
     switch (prec) {
       case NQA_PREC_BF16: return launch_conv1_regw<PrecBF16>(x, y, B, n, H, W, p, out, st);
       case NQA_PREC_F16: return launch_conv1_regw<PrecF16>(x, y, B, n, H, W, p, out, st);
@@ -2893,41 +2771,20 @@ int conv1_fused(const float *x, const float *y, int B, int n, int H, int W, cons
     case NQA_PREC_BF16: return launch_conv1_fused<PrecBF16>(x, y, B, n, H, W, p, out, st);
     case NQA_PREC_F16: return launch_conv1_fused<PrecF16>(x, y, B, n, H, W, p, out, st);
   }
-  set_error("conv1_fused: 16-bit precision modes only (prec %d)", prec);
+  set_error("conv1_fused: NQA_PREC_F32 has no fused stage 1 (prec %d)", prec);
   return NQA_E_ARG;
 }
 
 int conv1_1(const float *x, int n, int H, int W, const void *packed, int prec, void *out, hipStream_t st) {
   const char *p = static_cast<const char *>(packed);
-  switch (prec) {
-    case NQA_PREC_F32S: return launch_conv1_1<PrecF32S>(x, n, H, W, p, out, st);  // split16 out
-    case NQA_PREC_F32: return launch_conv1_1<PrecF32>(x, n, H, W, p, out, st);
-    case NQA_PREC_BF16: return launch_conv1_1<PrecBF16>(x, n, H, W, p, out, st);
-    case NQA_PREC_F16: return launch_conv1_1<PrecF16>(x, n, H, W, p, out, st);
+  switch (stage_prec(prec, 0)) {  // (a mixed mode: the exact float convolution stored as half)
+    case NQA_PREC_F32S: return launch_conv1_1<PrecF32S>(x, n, H, W, p, out, st, prec);  // split16 out
+    case NQA_PREC_F32: return launch_conv1_1<PrecF32>(x, n, H, W, p, out, st, prec);
+    case NQA_PREC_BF16: return launch_conv1_1<PrecBF16>(x, n, H, W, p, out, st, prec);
+    case NQA_PREC_F16: return launch_conv1_1<PrecF16>(x, n, H, W, p, out, st, prec);
   }
   set_error("conv1_1: unknown prec %d", prec);
   return NQA_E_ARG;
-}
-
-int conv3x3_blob(const void *in, int n, int H, int W, int layer, const void *packed, int blob_prec, int kprec,
-                 void *out, hipStream_t st) {
-  const char *p = static_cast<const char *>(packed);
-  if (is_mixed(blob_prec)) {
-    if (kprec == NQA_PREC_F16) return launch_conv<PrecF16>(in, n, H, W, layer, p, out, st, blob_prec);
-    if (kprec == NQA_PREC_F32S) return launch_conv<PrecF32S>(in, n, H, W, layer, p, out, st, blob_prec);
-  }
-  set_error("conv3x3_blob: unsupported blob / kernel precision pair %d / %d", blob_prec, kprec);
-  return NQA_E_ARG;
-}
-
-// stage 1 of the mixed mode in one kernel (two-term conv1_1 and conv1_2), images [x(0..B), y(0..n-B))
-int conv1_fused_blob(const float *x, const float *y, int B, int n, int H, int W, const void *packed, int blob_prec,
-                     void *out, hipStream_t st) {
-  if (!is_mixed(blob_prec)) {
-    set_error("conv1_fused_blob: NQA_PREC_F32M blobs only");
-    return NQA_E_ARG;
-  }
-  return launch_conv1_regw<PrecF16, 2>(x, y, B, n, H, W, static_cast<const char *>(packed), out, st, blob_prec);
 }
 
 // A 3x3 convolution that is not a VGG layer of the packed blob: split16 activations in, FLOAT out, weights as one
@@ -2948,21 +2805,19 @@ int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout
                 : launch_igemm<PrecF32S, 1, 4, 2, 2, 32, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
 }
 
-int conv1_1_blob(const float *x, int n, int H, int W, const void *packed, int blob_prec, int kprec, void *out,
-                 hipStream_t st) {
-  const char *p = static_cast<const char *>(packed);
-  if (is_mixed(blob_prec) && kprec == NQA_PREC_F16) return launch_conv1_1<PrecF16>(x, n, H, W, p, out, st, blob_prec);
-  set_error("conv1_1_blob: unsupported blob / kernel precision pair %d / %d", blob_prec, kprec);
-  return NQA_E_ARG;
-}
-
 int conv3x3(const void *in, int n, int H, int W, int layer, const void *packed, int prec, void *out, hipStream_t st) {
   const char *p = static_cast<const char *>(packed);
-  switch (prec) {
-    case NQA_PREC_F32: return launch_conv<PrecF32>(in, n, H, W, layer, p, out, st);
-    case NQA_PREC_BF16: return launch_conv<PrecBF16>(in, n, H, W, layer, p, out, st);
-    case NQA_PREC_F16: return launch_conv<PrecF16>(in, n, H, W, layer, p, out, st);
-    case NQA_PREC_F32S: return launch_conv<PrecF32S>(in, n, H, W, layer, p, out, st);
+  const int kp = stage_prec(prec, kConvs[layer].stage);
+  if (layer_terms(prec, layer) == 2) {
+    if (kp == NQA_PREC_F16) return launch_conv<PrecF16, 2>(in, n, H, W, layer, p, prec, out, st);
+    set_error("conv3x3: two-term weights exist for the f16 kernels only");
+    return NQA_E_ARG;
+  }
+  switch (kp) {
+    case NQA_PREC_F32: return launch_conv<PrecF32, 1>(in, n, H, W, layer, p, prec, out, st);
+    case NQA_PREC_BF16: return launch_conv<PrecBF16, 1>(in, n, H, W, layer, p, prec, out, st);
+    case NQA_PREC_F16: return launch_conv<PrecF16, 1>(in, n, H, W, layer, p, prec, out, st);
+    case NQA_PREC_F32S: return launch_conv<PrecF32S, 1>(in, n, H, W, layer, p, prec, out, st);
   }
   set_error("conv3x3: unknown prec %d", prec);
   return NQA_E_ARG;

@@ -17,7 +17,6 @@
 //     k loops of unit u, two groups of 16 halo pixels per pass;
 //   * halo image: [image][6 x 34 pixels] records of 160 bytes (64 channels as two 32-channel chunks + 32 B pad): a
 //     ds_read_b128 of 16 consecutive pixels is bank-conflict-free at that pitch, every tap an immediate offset.
-#include <atomic>
 #include <type_traits>
 
 #include "nqa_common.h"
@@ -605,26 +604,8 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static int s1_num_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  dev &= 63;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-    n = prop.multiProcessorCount;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-static thread_local int g_fuse_stage1 = 1;  // nqa_set_conv_variant bit 7 (128): 0 = the unfused stage 1 + pool + statistics
-void set_fuse_stage1(int on) { g_fuse_stage1 = on & 1; }
-
 bool conv1_pool_fusable(int B, int H, int W, int blob_prec) {
-  if (!g_fuse_stage1 || blob_prec != NQA_PREC_F16 || W < 16 || H < 4) return false;
+  if (!tuning().fuse_stage1 || blob_prec != NQA_PREC_F16 || W < 16 || H < 4) return false;
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, strips = cdiv(W, 16);
   if ((size_t)H * W * 3 * 4 >= (1ull << 31)) return false;
   if (2ull * B * Ho * Wo * 64 * 2 >= (1ull << 31)) return false;
@@ -636,23 +617,9 @@ template <bool RAGGED>
 static int launch_conv1_pool(const float *x, const float *y, int B, int H, int W, const char *packed, void *pooled, float *seam,
                              double *part, hipStream_t st) {
   typedef S1Geom G;
-  static std::atomic<bool> attr_done_dev[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<bool> &attr_done = attr_done_dev[dev & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_pool_kernel<RAGGED>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            G::LDS) != hipSuccess) {
-      set_error("conv1_pool: cannot raise the dynamic LDS limit to %d bytes", G::LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = s1_num_cus();
-  if (!cus) {
-    set_error("conv1_pool: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv1_pool_kernel<RAGGED>>(G::LDS, "conv1_pool")) return rc;
+  const int cus = num_cus("conv1_pool");
+  if (!cus) return NQA_E_LAUNCH;
   const int spairs = cdiv(W, G::TW), rows = cdiv(H, G::TH);
   const long units = (long)B * spairs * rows;
   int grid = (int)(units < cus ? units : cus);

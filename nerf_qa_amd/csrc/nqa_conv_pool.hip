@@ -24,7 +24,6 @@
 //     vector instructions behind each MFMA (one wave per SIMD: there is no partner wave to run it under), so the matrix
 //     pipe never waits for it.
 // A-DISTS needs the taps themselves and keeps the unfused kernels.
-#include <atomic>
 
 #include "nqa_common.h"
 
@@ -500,27 +499,9 @@ int pool_seam_finish(const float *seam, void *pooled, int nimg, int strips, int 
   return check_launch("pool_seam");
 }
 
-static int pool_num_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  dev &= 63;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-    n = prop.multiProcessorCount;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-static thread_local int g_fuse_taps = 1;  // nqa_set_conv_variant bit 6 (64): 0 = the unfused path, for A/B runs
-void set_fuse_taps(int on) { g_fuse_taps = on; }
-
 // Can conv layer `layer` of a B-pair batch of H x W maps (its input's size) take the fused form?
 bool conv_pool_fusable(int layer, int B, int H, int W, int blob_prec, int kprec) {
-  if (!g_fuse_taps || layer != 3 || kprec != NQA_PREC_F16 || W < 16 || H < 4) return false;
+  if (!tuning().fuse_taps || layer != 3 || kprec != NQA_PREC_F16 || W < 16 || H < 4) return false;
   if (!(blob_prec == NQA_PREC_F16 || is_mixed(blob_prec))) return false;
   const size_t img_in = (size_t)H * W * 128 * 2;
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, strips = cdiv(W, 16);
@@ -541,23 +522,9 @@ template <int NTERM, bool RAGGED>
 static int launch_conv_pool(const void *in, int B, int H, int W, int layer, const char *packed, int blob_prec, void *pooled,
                             float *seam, double *part, hipStream_t st) {
   typedef PoolGeom G;
-  static std::atomic<bool> attr_done_dev[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<bool> &attr_done = attr_done_dev[dev & 63];
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_regw128_pool_kernel<NTERM, RAGGED, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) != hipSuccess) {
-      set_error("conv_pool: cannot raise the dynamic LDS limit to %d bytes", G::LDS);
-      return NQA_E_LAUNCH;
-    }
-    attr_done = true;
-  }
-  const int cus = pool_num_cus();
-  if (!cus) {
-    set_error("conv_pool: cannot query the device");
-    return NQA_E_LAUNCH;
-  }
+  if (const int rc = lds_limit<conv3x3_regw128_pool_kernel<NTERM, RAGGED, false>>(G::LDS, "conv_pool")) return rc;
+  const int cus = num_cus("conv_pool");
+  if (!cus) return NQA_E_LAUNCH;
   const int cout = kConvs[layer].cout, nct = cout / (128 / NTERM);
   const int strips = cdiv(W, G::TWI), rows = cdiv(H, G::TH);
   const long units = (long)B * nct * strips * rows;

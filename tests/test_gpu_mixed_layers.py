@@ -19,7 +19,7 @@ some ten per cent; the fixtures take the bars from what the replay measures when
     and the share of outputs that differ at all from f16(relu(pre)) is capped:
       reference figure: the float32 replay differs in <= 3.9e-3 of the elements (1.8e-3 with the scaled terms)
       bar: 1e-2.  One lo tap lost of nine: >= 7.5e-2; no lo: >= 2.0e-1.
-    Kernels by nqa_set_conv_variant in a mixed mode (nqa_conv.hip, launch_conv / launch_conv_2term):
+    Kernels by nqa_set_conv_variant in a mixed mode (nqa_conv.hip, launch_conv<.., NTERM = 2>):
       1 (default) conv1_2, conv2_1: conv3x3_regw_kernel<.., 2>; conv2_2, conv3_1: conv3x3_regw128_kernel<.., 2> (W >= 16);
                   everything else the implicit GEMM <.., NTERM = 2> in its 64-channel, 4-wave or 8-wave tile, 16 or 32 wide
       0           the 4-wave tile where 1 takes the 8-wave one: >= 256 output channels, W > 16 and >= 192 blocks of it
@@ -29,8 +29,8 @@ some ten per cent; the fixtures take the bars from what the replay measures when
     without effect on a two-term layer: 2 (the 128 x 512 tile is chosen behind the two-term dispatch: same as 1), +4 (tile
     form of the ONE-term fused stage 1), +8 (A-DISTS window pass), +64 / +128 (fusions of the DISTS path, not of an operator).
 (b) float stages of a mixed blob (layers 4 | 7 | 10 behind the boundary of f32m2 | f32m | f32m4, and layer 12):
-    nqa_pack_vgg_weights writes their rows by the same code as for f32s and conv3x3_blob launches the same
-    launch_conv<PrecF32S> instance with the same tile choice, so the result is BIT-EQUAL to the f32s blob's.
+    nqa_pack_vgg_weights writes their rows by the same code as for f32s and conv3x3 launches the same
+    launch_conv<PrecF32S, 1> instance with the same tile choice, so the result is BIT-EQUAL to the f32s blob's.
 (c) the boundary pool f16 -> split16 against dists_oracle.l2pool in float64 of the same half values, float-class:
       reference figure: the float32 oracle is 1.24e-7 | 6.2e-8 | 8.4e-8 | 1.05e-7 of the map's maximum from the float64 one
       bar: 4 x that, per shape (a split16 emulation of the float32 oracle sits at 1.1 ... 2.0e-7).

@@ -148,6 +148,34 @@ def test_pool_stats_matches_separate_kernels(packed, alpha_beta, dev):
             layer += 1
 
 
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("h,w", [(45, 70), (9, 13)], ids=["45x70", "9x13"])
+def test_pyramid_is_a_chain_of_single_operators(prec, h, w, packed, dev):
+    """Every mode's pyramid runs the one stage loop (nqa_stages.h): its taps are, bit for bit, what the single-operator
+    entry points give when chained by hand with nqa_l2pool in the mode's own precision.  Stage 1 is nqa_conv1_fused where
+    the mode has a fused form, conv1_1 + layer 1 in f32.  9 x 13 has W < 16: narrow tiles, no register-weights kernels.
+    (test_gpu_mixed_layers.py holds the mixed modes to the same.)"""
+    from nerf_qa_amd import ops, synth
+    x, _ = synth.frame_batch([3], h, w)
+    x = torch.from_numpy(x).to(dev)
+    taps = ops.vgg_pyramid(x, packed[prec], prec)
+    if prec == "f32":
+        t = ops.conv3x3_relu(ops.conv1_1(x, packed[prec], prec), 1, packed[prec], prec)
+    else:
+        t = ops.conv1_fused(x, packed[prec], prec)
+    bits = torch.int32 if DT[prec] == torch.float32 else torch.int16
+    layer = 2
+    for k in range(5):
+        assert t.dtype == taps[k].dtype == DT[prec] and t.shape == taps[k].shape
+        assert torch.equal(t.view(bits), taps[k].view(bits)), f"tap {k + 1} differs"
+        if k == 4:
+            break
+        t = ops.l2pool(t, prec)
+        for _ in range((2, 2, 3, 3, 3)[k + 1]):
+            t = ops.conv3x3_relu(t, layer, packed[prec], prec)
+            layer += 1
+
+
 CONV_CASES = [  # (layer, n, H, W)
     (1, 2, 13, 37), (1, 1, 32, 64), (1, 2, 9, 16),
     (2, 2, 11, 40), (3, 1, 8, 33), (3, 3, 16, 16), (4, 1, 7, 7),
