@@ -257,6 +257,30 @@ int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W,
                             const float *wgt, int strip, float *gamma, float *tw, float *sw, void *stream);
 int nqa_adists_window_grid(int B, int H, int W, int C, int prec, int strip, int *grid);
 
+/* The BACK part of nqa_adists_forward on its own, for tests and tools: from the six stages' gamma / tw / sw maps (what
+ * the window pass leaves) to the texture-probability chain (compute_prob, ADISTS.py:77-99, coarse to fine), the stages'
+ * D sums, D_b (ADISTS.py:185-191) and, with a map pointer, the as_map=True resampler (ADISTS.py:163,188-189,193).  It is
+ * the launch function nqa_adists_forward itself ends with: the same kernels on the same grids in the same order.
+ *   nqa_adists_chain_dims   mh[k] x mw[k], k = 0..5, of stage k's maps for an H x W frame: the tap is H x W for k = 0
+ *           and 1 and halves (rounding up) from k = 2 on; a tap of at least 21 x 21 gives a (h-20) x (w-20) map of valid
+ *           windows, a smaller one the global branch's 1 x 1.  Returns the number of windowed stages (they are stages
+ *           0 .. n-1; a 21-wide tap is windowed with a 1 x 1 map), or a negative code.
+ *   nqa_adists_chain_bytes  workspace of nqa_adists_chain: the chain's accumulators (6 B), its per-block partial sums and
+ *           the B ones the coarsest stage is multiplied with.  0 for a non-positive size.
+ *   gamma, tw, sw   host arrays of six dev float32 pointers, map k (B, mh[k], mw[k]) contiguous.
+ *   ps_prod         host array of six dev float32 pointers, (B, mh[k], mw[k]): receives stage k's probability map.
+ *   d               dev float32 (B): D_b = sum_k mean_hw((1 - ps_prod_k) tw_k + ps_prod_k sw_k).
+ *   map             null, or dev float32 (B,H,W) as nqa_adists_forward_map writes it.
+ * A windowed stage of ONE element has no unbiased standard deviation: its ps_prod, every finer stage's, d and the map
+ * are NaN, as the reference's torch.std makes them.
+ * Refused on the host, before any launch: NQA_E_ARG null pointer (map excepted; the six pointers of every array
+ * included), non-positive size, a frame of H * W * 64 floats reaching 2^31 bytes (nqa_adists_forward's limit);
+ * NQA_E_WORKSPACE a workspace under nqa_adists_chain_bytes(B, H, W). */
+int nqa_adists_chain_dims(int H, int W, int *mh, int *mw);
+size_t nqa_adists_chain_bytes(int B, int H, int W);
+int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
+                     void *workspace, size_t workspace_bytes, float *const *ps_prod, float *d, float *map, void *stream);
+
 /* ---- input preparation on the device (decoded uint8 frame -> metric input) ------------ */
 
 /* transforms.ToTensor / `torch.from_numpy(frame).permute(2,0,1).float() / 255.0` (prep.py:89,

@@ -978,23 +978,32 @@ struct APlan {
   int ent_ppb[NQA_NUM_TAPS];
 };
 
+// Feature dims of the six taps of an H x W frame (k = 0 the image, k = 1 relu1_2 at full size, then halved, rounding up),
+// and the dims of a stage's gamma / TW / SW / ps_prod maps: valid 21 x 21 windows, or 1 x 1 from the global branch.
+static void tap_dims(int H, int W, int h[NQA_NUM_TAPS], int w[NQA_NUM_TAPS]) {
+  h[0] = h[1] = H;
+  w[0] = w[1] = W;
+  for (int k = 2; k < NQA_NUM_TAPS; ++k) {
+    h[k] = (h[k - 1] + 1) / 2;
+    w[k] = (w[k - 1] + 1) / 2;
+  }
+}
+static void map_dims(const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], int mh[NQA_NUM_TAPS], int mw[NQA_NUM_TAPS],
+                     bool windowed[NQA_NUM_TAPS]) {
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    windowed[k] = h[k] >= kWin && w[k] >= kWin;
+    mh[k] = windowed[k] ? h[k] - (kWin - 1) : 1;
+    mw[k] = windowed[k] ? w[k] - (kWin - 1) : 1;
+  }
+}
+
 static APlan make_plan(int B, int H, int W, int prec) {
   APlan p;
   memset(&p, 0, sizeof(p));
   const size_t esz = prec_elem_bytes(prec);
-  p.h[0] = H;
-  p.w[0] = W;
+  tap_dims(H, W, p.h, p.w);
   p.c[0] = 3;
-  int h = H, w = W;
-  for (int k = 1; k < 6; ++k) {
-    if (k > 1) {
-      h = (h + 1) / 2;
-      w = (w + 1) / 2;
-    }
-    p.h[k] = h;
-    p.w[k] = w;
-    p.c[k] = kChns[k];
-  }
+  for (int k = 1; k < 6; ++k) p.c[k] = kChns[k];
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
@@ -1048,12 +1057,9 @@ static APlan make_plan(int B, int H, int W, int prec) {
   p.ed.ctot = coff;
   p.ent = take((size_t)eoff * 8);
   p.wgt = take((size_t)B * coff * 4);
-  for (int k = 0; k < 6; ++k) {
-    p.windowed[k] = p.h[k] >= kWin && p.w[k] >= kWin;
-    p.mh[k] = p.windowed[k] ? p.h[k] - (kWin - 1) : 1;
-    p.mw[k] = p.windowed[k] ? p.w[k] - (kWin - 1) : 1;
+  map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
+  for (int k = 0; k < 6; ++k)
     for (int j = 0; j < 4; ++j) p.maps[k][j] = take((size_t)B * p.mh[k] * p.mw[k] * 4);
-  }
   p.acc = take((size_t)6 * B * sizeof(ChainAcc));
   p.chain_part = take((size_t)B * kChainBlocks * 2 * sizeof(double));
   p.total = off;
@@ -1177,6 +1183,67 @@ size_t nqa_adists_workspace_bytes(int B, int H, int W, int prec) {
 
 }  // extern "C"
 
+// The back part of the forward: the probability chain from the coarsest stage to the finest, the stages' D sums, D_b and,
+// with map_out, the as_map=True resampler.  adists_run and nqa_adists_chain both launch it through this function.
+struct ChainMaps {
+  const float *gamma[NQA_NUM_TAPS], *tw[NQA_NUM_TAPS], *sw[NQA_NUM_TAPS];  // (B, mh, mw) each
+  float *ps[NQA_NUM_TAPS];                                                 // ps_prod out, (B, mh, mw)
+  int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];
+  bool windowed[NQA_NUM_TAPS];
+};
+
+static int launch_chain(const ChainMaps &m, int B, int H, int W, ChainAcc *acc /* [6][B] */,
+                        double *cp /* [B][kChainBlocks][2] */, float *ones /* [B] */, float *d_out, float *map_out,
+                        hipStream_t st) {
+  int rc;
+  {
+    TimedLaunch t(NQA_K_ADISTS, st);
+    chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc, 6 * B);
+    // initial ps_prod = ones (ADISTS.py:75): a 1x1 map of 1 upsamples to the same constant
+    ones_kernel<<<cdiv(B, 256), 256, 0, st>>>(ones, B);
+    const float *prev = ones;
+    int hp = 1, wp = 1;
+    for (int k = 5; k >= 0; --k) {
+      const float *gamma = m.gamma[k], *tw = m.tw[k], *sw = m.sw[k];
+      float *psprod = m.ps[k];
+      ChainAcc *a = acc + (size_t)k * B;
+      if (m.windowed[k]) {
+        const int n = m.mh[k] * m.mw[k];
+        dim3 grid(min(cdiv(n, 256), kChainBlocks), B);
+        chain_moments_kernel<<<grid, 256, 0, st>>>(gamma, n, cp);
+        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 2, 0, a);
+        chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, a);
+        chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, a);
+        chain_final_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, a, cp);
+        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, a);
+      } else {
+        chain_global_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, a, B);
+      }
+      prev = psprod;
+      hp = m.mh[k];
+      wp = m.mw[k];
+    }
+    DDesc dd;
+    for (int k = 0; k < 6; ++k) dd.n[k] = m.mh[k] * m.mw[k];
+    adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc, dd, B, d_out);
+    if ((rc = check_launch("adists_chain"))) return rc;
+  }
+  if (map_out) {
+    MapDesc md;
+    for (int k = 0; k < 6; ++k) {
+      md.tw[k] = m.tw[k];
+      md.sw[k] = m.sw[k];
+      md.ps[k] = m.ps[k];
+      md.mh[k] = m.mh[k];
+      md.mw[k] = m.mw[k];
+    }
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_map_kernel<<<dim3(cdiv(H * W, 256), B), 256, 0, st>>>(md, H, W, map_out);
+    if ((rc = check_launch("adists_map"))) return rc;
+  }
+  return NQA_OK;
+}
+
 static int adists_run(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
                       size_t ws_bytes, float *d_out, float *map_out, void *stream, float *s1_out = nullptr,
                       float *s2_out = nullptr) {
@@ -1292,58 +1359,101 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
     }
     if (rc) return rc;
   }
-  // ---- probability chain, coarse to fine ----
-  {
-    TimedLaunch t(NQA_K_ADISTS, st);
-    chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc, 6 * B);
-    // initial ps_prod = ones (ADISTS.py:75): a 1x1 map of 1 upsamples to the same constant
-    float *ones = reinterpret_cast<float *>(base + p.bufB);  // the ping-pong buffers are free now
-    ones_kernel<<<cdiv(B, 256), 256, 0, st>>>(ones, B);
-    const float *prev = ones;
-    int hp = 1, wp = 1;
-    for (int k = 5; k >= 0; --k) {
-      const float *gamma = reinterpret_cast<const float *>(base + p.maps[k][0]);
-      const float *tw = reinterpret_cast<const float *>(base + p.maps[k][1]);
-      const float *sw = reinterpret_cast<const float *>(base + p.maps[k][2]);
-      float *psprod = reinterpret_cast<float *>(base + p.maps[k][3]);
-      ChainAcc *a = acc + (size_t)k * B;
-      if (p.windowed[k]) {
-        const int n = p.mh[k] * p.mw[k];
-        dim3 grid(min(cdiv(n, 256), kChainBlocks), B);
-        double *cp = reinterpret_cast<double *>(base + p.chain_part);
-        chain_moments_kernel<<<grid, 256, 0, st>>>(gamma, n, cp);
-        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 2, 0, a);
-        chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, a);
-        chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, p.mh[k], p.mw[k], prev, hp, wp, a);
-        chain_final_kernel<<<grid, 256, 0, st>>>(gamma, p.mh[k], p.mw[k], prev, hp, wp, tw, sw, psprod, a, cp);
-        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, a);
-      } else {
-        chain_global_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, a, B);
-      }
-      prev = psprod;
-      hp = p.mh[k];
-      wp = p.mw[k];
-    }
-    DDesc dd;
-    for (int k = 0; k < 6; ++k) dd.n[k] = p.mh[k] * p.mw[k];
-    adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc, dd, B, d_out);
-    if ((rc = check_launch("adists_chain"))) return rc;
+  // ---- probability chain, coarse to fine; D; the as_map=True resampler ----
+  ChainMaps cm;
+  for (int k = 0; k < 6; ++k) {
+    cm.gamma[k] = reinterpret_cast<const float *>(base + p.maps[k][0]);
+    cm.tw[k] = reinterpret_cast<const float *>(base + p.maps[k][1]);
+    cm.sw[k] = reinterpret_cast<const float *>(base + p.maps[k][2]);
+    cm.ps[k] = reinterpret_cast<float *>(base + p.maps[k][3]);
+    cm.mh[k] = p.mh[k];
+    cm.mw[k] = p.mw[k];
+    cm.windowed[k] = p.windowed[k];
   }
-  if (map_out) {
-    MapDesc md;
-    for (int k = 0; k < 6; ++k) {
-      md.tw[k] = reinterpret_cast<const float *>(base + p.maps[k][1]);
-      md.sw[k] = reinterpret_cast<const float *>(base + p.maps[k][2]);
-      md.ps[k] = reinterpret_cast<const float *>(base + p.maps[k][3]);
-      md.mh[k] = p.mh[k];
-      md.mw[k] = p.mw[k];
-    }
-    TimedLaunch t(NQA_K_ADISTS, st);
-    adists_map_kernel<<<dim3(cdiv(H * W, 256), B), 256, 0, st>>>(md, H, W, map_out);
-    if ((rc = check_launch("adists_map"))) return rc;
+  // initial ps_prod = ones (ADISTS.py:75) lives in bufB: the ping-pong buffers are free now
+  return launch_chain(cm, B, H, W, acc, reinterpret_cast<double *>(base + p.chain_part),
+                      reinterpret_cast<float *>(base + p.bufB), d_out, map_out, st);
+}
+
+// The back part on its own (include/nqa.h).  Workspace: ChainAcc[6][B], the chain's per-block partials, the B ones.
+struct ChainPlan {
+  size_t acc, part, ones, total;
+};
+static ChainPlan chain_plan(int B) {
+  ChainPlan c;
+  c.acc = 0;
+  c.part = align_up((size_t)6 * B * sizeof(ChainAcc), 256);
+  c.ones = c.part + align_up((size_t)B * kChainBlocks * 2 * sizeof(double), 256);
+  c.total = c.ones + align_up((size_t)B * sizeof(float), 256);
+  return c;
+}
+static int chain_frame_check(const char *who, int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) {
+    set_error("%s: bad size (B=%d H=%d W=%d)", who, B, H, W);
+    return NQA_E_ARG;
+  }
+  if ((long)H * W * 64 * 4 >= (1L << 31)) {  // nqa_adists_forward's limit, for its widest element
+    set_error("%s: image too large for 32-bit in-image byte offsets", who);
+    return NQA_E_ARG;
   }
   return NQA_OK;
 }
+
+extern "C" {
+
+int nqa_adists_chain_dims(int H, int W, int *mh, int *mw) {
+  if (!mh || !mw) {
+    set_error("adists_chain_dims: null pointer");
+    return NQA_E_ARG;
+  }
+  if (int rc = chain_frame_check("adists_chain_dims", 1, H, W)) return rc;
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
+  bool windowed[NQA_NUM_TAPS];
+  tap_dims(H, W, h, w);
+  map_dims(h, w, mh, mw, windowed);
+  int nwin = 0;
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) nwin += windowed[k] ? 1 : 0;
+  return nwin;
+}
+
+size_t nqa_adists_chain_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return chain_plan(B).total;
+}
+
+int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
+                     void *ws, size_t ws_bytes, float *const *ps_prod, float *d, float *map, void *stream) {
+  if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
+    set_error("adists_chain: null pointer");
+    return NQA_E_ARG;
+  }
+  for (int k = 0; k < NQA_NUM_TAPS; ++k)
+    if (!gamma[k] || !tw[k] || !sw[k] || !ps_prod[k]) {
+      set_error("adists_chain: null pointer (stage %d)", k);
+      return NQA_E_ARG;
+    }
+  if (int rc = chain_frame_check("adists_chain", B, H, W)) return rc;
+  const ChainPlan c = chain_plan(B);
+  if (ws_bytes < c.total) {
+    set_error("adists_chain: workspace %zu < %zu bytes", ws_bytes, c.total);
+    return NQA_E_WORKSPACE;
+  }
+  ChainMaps cm;
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
+  tap_dims(H, W, h, w);
+  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    cm.gamma[k] = gamma[k];
+    cm.tw[k] = tw[k];
+    cm.sw[k] = sw[k];
+    cm.ps[k] = ps_prod[k];
+  }
+  char *base = static_cast<char *>(ws);
+  return launch_chain(cm, B, H, W, reinterpret_cast<ChainAcc *>(base + c.acc), reinterpret_cast<double *>(base + c.part),
+                      reinterpret_cast<float *>(base + c.ones), d, map, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
 
 // One stage of the heavy pass on its own, dispatched as the loop above dispatches it (ctot = C, coff = 0).
 static int window_stage_check(const char *who, int B, int H, int W, int C, int prec, int strip) {

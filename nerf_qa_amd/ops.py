@@ -510,6 +510,76 @@ def adists_window_grid(b: int, h: int, w: int, c: int, prec, strip: int = 0) -> 
     return tuple(g)
 
 
+def adists_chain_dims(h: int, w: int):
+    """([(mh, mw)] of the six stages' maps for an h x w frame, the number of windowed stages), from the library's own plan
+    (include/nqa.h, nqa_adists_chain_dims)."""
+    mh, mw = (C.c_int * 6)(), (C.c_int * 6)()
+    n = lib().nqa_adists_chain_dims(int(h), int(w), mh, mw)
+    if n < 0:
+        check(n)
+    return list(zip(mh, mw)), n
+
+
+def _chain_lists(**lists) -> None:
+    for name, ts in lists.items():
+        if not isinstance(ts, (list, tuple)) or len(ts) != 6 or not all(torch.is_tensor(t) for t in ts):
+            raise ValueError(f"adists_chain: {name} must be a list of six tensors, one per stage")
+
+
+def _chain_dims(gamma, tw, sw, h: int, w: int):
+    """Every check of adists_chain on its inputs but their device; (B, [(mh, mw)] per stage)."""
+    _chain_lists(gamma=gamma, tw=tw, sw=sw)
+    if gamma[0].dim() != 3 or gamma[0].shape[0] == 0:
+        raise ValueError(f"adists_chain: maps must be (B, mh, mw), got {tuple(gamma[0].shape)}")
+    if int(h) <= 0 or int(w) <= 0:
+        raise ValueError(f"adists_chain: bad frame size {h} x {w}")
+    b = int(gamma[0].shape[0])
+    dims, _ = adists_chain_dims(h, w)
+    for name, ts in (("gamma", gamma), ("tw", tw), ("sw", sw)):
+        for k, t in enumerate(ts):
+            sh = (b,) + dims[k]
+            if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"adists_chain: {name}[{k}] must be contiguous float32 {sh}, got {t.dtype} "
+                                 f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return b, dims
+
+
+def adists_chain(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor], sw: Sequence[torch.Tensor], h: int, w: int,
+                 with_map: bool = True, ws: Workspace | None = None):
+    """The back part of adists_forward as it launches it (include/nqa.h, nqa_adists_chain): from the six stages' gamma /
+    tw / sw maps, each (B, mh, mw) float32 for an h x w frame (adists_chain_dims), to (ps_prod: six (B, mh, mw) maps,
+    D (B,), map (B,h,w) or None)."""
+    _chain_lists(gamma=gamma, tw=tw, sw=sw)
+    dev = _need_cuda(*gamma, *tw, *sw)
+    b, dims = _chain_dims(gamma, tw, sw, h, w)
+    ps = [torch.empty((b,) + d, dtype=torch.float32, device=dev) for d in dims]
+    d = torch.empty((b,), dtype=torch.float32, device=dev)
+    m = torch.empty((b, int(h), int(w)), dtype=torch.float32, device=dev) if with_map else None
+    adists_chain_into(gamma, tw, sw, h, w, ps, d, m, ws)
+    return ps, d, m
+
+
+def adists_chain_into(gamma, tw, sw, h: int, w: int, ps_prod, d, map_out=None, ws: Workspace | None = None) -> None:
+    """adists_chain into caller-owned contiguous float32 outputs of the shapes it would return (tests place them between
+    guard regions); map_out None: no map.  Every check of adists_chain applies."""
+    _chain_lists(gamma=gamma, tw=tw, sw=sw, ps_prod=ps_prod)
+    outs = list(ps_prod) + [d] + ([] if map_out is None else [map_out])
+    if not all(torch.is_tensor(t) for t in outs):
+        raise ValueError("adists_chain: d (and map_out, if given) must be tensors")
+    dev = _need_cuda(*gamma, *tw, *sw, *outs)
+    b, dims = _chain_dims(gamma, tw, sw, h, w)
+    h, w = int(h), int(w)
+    want = [(b,) + dm for dm in dims] + [(b,)] + ([] if map_out is None else [(b, h, w)])
+    for t, sh in zip(outs, want):
+        if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"adists_chain: outputs must be contiguous float32, here {sh}, got {t.dtype} {tuple(t.shape)}")
+    nbytes = lib().nqa_adists_chain_bytes(b, h, w)
+    buf = (ws or Workspace()).get(nbytes, dev)
+    arr = lambda ts: (C.c_void_p * 6)(*[ptr(t) for t in ts])
+    _call(dev, lib().nqa_adists_chain, arr(gamma), arr(tw), arr(sw), b, h, w, ptr(buf), buf.numel(), arr(ps_prod), ptr(d),
+          None if map_out is None else ptr(map_out), stream_ptr(dev))
+
+
 # ---- input preparation (SURVEY.md section 8 f2) ---------------------------------------------------
 def u8hwc_to_f32nchw(frames: torch.Tensor, pil_roundtrip: bool = False) -> torch.Tensor:
     """ToTensor on the device: uint8 (n,H,W,3) -> float32 (n,3,H,W) / 255 (prep.py:89, data.py:80)."""
