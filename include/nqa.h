@@ -281,6 +281,36 @@ size_t nqa_adists_chain_bytes(int B, int H, int W);
 int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
                      void *workspace, size_t workspace_bytes, float *const *ps_prod, float *d, float *map, void *stream);
 
+/* The FRONT part of nqa_adists_forward on its own, for tests and tools: from the two images and the five tapped maps to
+ * the per-channel scalars q and the channel weights wgt that the window pass and the global branch read.  It runs what
+ * nqa_adists_forward runs for them, through the same launch functions, on the same grids, in the same order: the
+ * statistics sums (the plane kernel on the images, the fused pool + statistics pass on taps 1..4 -- its pooled maps go to
+ * the workspace and are discarded -- and the NHWC kernel on tap 5; the forward enqueues these between the layers of its
+ * pyramid), then the preparation kernel, the images as NHWC4, the six entropy passes, their fold and the weights kernel
+ * (ADISTS.py:127-135,150-161,166-167,176-180); the last five steps are one launch function shared with the forward.
+ *   x, y    dev float32 NCHW (B,3,Hk[0],Wk[0]).
+ *   taps    host array of five dev pointers, tap k = 1..5 at taps[k-1]: NHWC (2B,Hk[k],Wk[k],C_k), images x then y, in
+ *           prec's storage type (float for NQA_PREC_F32 / NQA_PREC_F32S); C_k = 64, 128, 256, 512, 512.
+ *   Hk, Wk  host int[6]: the sizes of the image (k = 0) and of every tap, free as in nqa_dists_stats_nchw: nothing here
+ *           needs one tap to be half the previous one.
+ *   q       dev float32 [8][B][1475] as the forward leaves it before the window pass: rows 0, 1 inv_x, inv_y =
+ *           1 / max(||f||_2, 1e-12) of the raw maps; rows 3..7 mean_x mean_y var_x var_y cov of the raw maps (population);
+ *           row 2 is NOT sum_x any more but hsum, the folded per-channel entropy of the x maps: the forward reuses the
+ *           sum_x row for it once the entropy passes have read it.
+ *   wgt     dev float32 [B][1475], the channel weights.
+ * Contract: the maps are taken as NON-NEGATIVE (images in [0,1], taps behind a ReLU).  The entropy normalises relu(f)
+ * with 1 / ||f|| and sum(f) of the raw map, where the reference takes both of relu(f); the two agree on such maps only.
+ * nqa_adists_front_bytes: the workspace (0 for arguments nqa_adists_front refuses).  nqa_adists_front_grid: grid[4 k ..
+ * 4 k + 3] for k = 0..5 = blocks per image pair of tap k's statistics pass, the pool pass' tile rows TR and columns TC
+ * (0, 0 for k = 0 and 5), blocks per image of its entropy pass -- from the planning functions the launches use.
+ * Refused on the host, before any launch: NQA_E_ARG null pointer (each of the five tap pointers included), non-positive
+ * size, prec outside the four kernel-level modes, a tap of H * W * C elements (the image: H * W * 4 floats) reaching 2^31
+ * bytes; NQA_E_WORKSPACE a workspace under nqa_adists_front_bytes. */
+size_t nqa_adists_front_bytes(int B, const int *Hk, const int *Wk, int prec);
+int nqa_adists_front_grid(int B, const int *Hk, const int *Wk, int prec, int *grid);
+int nqa_adists_front(const float *x_nchw, const float *y_nchw, const void *const *taps, int B, const int *Hk,
+                     const int *Wk, int prec, void *workspace, size_t workspace_bytes, float *q, float *wgt, void *stream);
+
 /* ---- input preparation on the device (decoded uint8 frame -> metric input) ------------ */
 
 /* transforms.ToTensor / `torch.from_numpy(frame).permute(2,0,1).float() / 255.0` (prep.py:89,

@@ -68,6 +68,9 @@ _SIGNATURES = {
     "nqa_adists_chain_bytes": (_sz, [_i, _i, _i]),
     "nqa_adists_chain": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _vp, _sz, C.POINTER(_vp), _vp,
                               _vp, _vp]),
+    "nqa_adists_front_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), _i]),
+    "nqa_adists_front_grid": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i)]),
+    "nqa_adists_front": (_i, [_vp, _vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _sz, _vp, _vp, _vp]),
     "nqa_u8hwc_to_f32nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "nqa_resize_bilinear_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "nqa_u8_resize_bilinear_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -997,6 +997,49 @@ static void map_dims(const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], int m
   }
 }
 
+// The descriptors of the front part (statistics partials, entropy partials) for six taps of h[k] x w[k] x c[k]; doff and
+// eoff receive the doubles the two partial arrays hold.  make_plan and nqa_adists_front both size and launch by this.
+static void front_descs(int B, const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], const int c[NQA_NUM_TAPS], int prec,
+                        StageDesc &sd, EntDesc &ed, int ent_ppb[NQA_NUM_TAPS], long &doff, long &eoff) {
+  // statistics partials: stage 0 from the NCHW kernel, stages 1..5 from the NHWC kernel
+  doff = 0;
+  int coff = 0;
+  for (int k = 0; k < 6; ++k) {
+    const int hw = h[k] * w[k];
+    // taps 1..4 get their statistics inside the fused pool pass (items = pooled pixels)
+    int nblk;
+    if (k == 0)
+      nblk = cdiv(hw, stats_nchw_ppb(hw));
+    else if (k <= 4)
+      nblk = pool_stats_tiles((h[k] + 1) / 2, (w[k] + 1) / 2, c[k], prec, B, nullptr, nullptr);
+    else
+      nblk = cdiv(hw, stats_units_per_block(hw, c[k], prec, B));
+    sd.part_off[k] = doff;
+    sd.nblk[k] = nblk;
+    sd.hw[k] = hw;
+    sd.c[k] = c[k];
+    sd.coff[k] = coff;
+    doff += (long)B * sd.nblk[k] * c[k] * 5;
+    coff += c[k];
+  }
+  sd.nstage = 6;
+  sd.ctot = coff;
+  eoff = 0;
+  for (int k = 0; k < 6; ++k) {
+    const int hw = h[k] * w[k];
+    const int cpad = k == 0 ? 4 : c[k];
+    const int ppb = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, B);
+    ent_ppb[k] = ppb;
+    ed.part_off[k] = eoff;
+    ed.nblk[k] = cdiv(hw, ppb);
+    ed.c[k] = cpad;
+    ed.creal[k] = c[k];
+    ed.coff[k] = sd.coff[k];
+    eoff += (long)B * ed.nblk[k] * cpad;
+  }
+  ed.ctot = coff;
+}
+
 static APlan make_plan(int B, int H, int W, int prec) {
   APlan p;
   memset(&p, 0, sizeof(p));
@@ -1016,45 +1059,11 @@ static APlan make_plan(int B, int H, int W, int prec) {
   for (int k = 0; k < 5; ++k) p.taps[k] = take((size_t)2 * B * p.h[k + 1] * p.w[k + 1] * p.c[k + 1] * esz);
   p.img4x = take((size_t)B * H * W * 4 * 4);
   p.img4y = take((size_t)B * H * W * 4 * 4);
-  // statistics partials: stage 0 from the NCHW kernel, stages 1..5 from the NHWC kernel
-  long doff = 0;
-  int coff = 0;
-  for (int k = 0; k < 6; ++k) {
-    const int hw = p.h[k] * p.w[k];
-    // taps 1..4 get their statistics inside the fused pool pass (items = pooled pixels)
-    int nblk;
-    if (k == 0)
-      nblk = cdiv(hw, stats_nchw_ppb(hw));
-    else if (k <= 4)
-      nblk = pool_stats_tiles((p.h[k] + 1) / 2, (p.w[k] + 1) / 2, p.c[k], prec, B, nullptr, nullptr);
-    else
-      nblk = cdiv(hw, stats_units_per_block(hw, p.c[k], prec, B));
-    p.sd.part_off[k] = doff;
-    p.sd.nblk[k] = nblk;
-    p.sd.hw[k] = hw;
-    p.sd.c[k] = p.c[k];
-    p.sd.coff[k] = coff;
-    doff += (long)B * p.sd.nblk[k] * p.c[k] * 5;
-    coff += p.c[k];
-  }
-  p.sd.nstage = 6;
-  p.sd.ctot = coff;
+  long doff, eoff;
+  front_descs(B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
+  const int coff = p.sd.ctot;
   p.part = take((size_t)doff * 8);
   p.q = take((size_t)8 * B * coff * 4);
-  long eoff = 0;
-  for (int k = 0; k < 6; ++k) {
-    const int hw = p.h[k] * p.w[k];
-    const int cpad = k == 0 ? 4 : p.c[k];
-    const int ppb = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, B);
-    p.ent_ppb[k] = ppb;
-    p.ed.part_off[k] = eoff;
-    p.ed.nblk[k] = cdiv(hw, ppb);
-    p.ed.c[k] = cpad;
-    p.ed.creal[k] = p.c[k];
-    p.ed.coff[k] = p.sd.coff[k];
-    eoff += (long)B * p.ed.nblk[k] * cpad;
-  }
-  p.ed.ctot = coff;
   p.ent = take((size_t)eoff * 8);
   p.wgt = take((size_t)B * coff * 4);
   map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
@@ -1244,6 +1253,58 @@ static int launch_chain(const ChainMaps &m, int B, int H, int W, ChainAcc *acc /
   return NQA_OK;
 }
 
+// The front part of the forward behind the statistics sums: from the fp64 partial sums `part` of the six taps (left by
+// stats_nchw, pool_stats and stats_nhwc) to the per-channel scalars q, the entropies of the x maps and the channel
+// weights.  adists_run and nqa_adists_front both launch it through this function.  h, w, c: the six taps' dims (k = 0 the
+// image); taps[k - 1]: tap k, 2B images (x then y).  On return q[2] holds hsum, the folded per-channel entropy.
+static int launch_front(const float *x, const float *y, void *const *taps, int B, const int h[NQA_NUM_TAPS],
+                        const int w[NQA_NUM_TAPS], const int c[NQA_NUM_TAPS], int prec, const StageDesc &sd,
+                        const EntDesc &ed, const int ent_ppb[NQA_NUM_TAPS], const double *part,
+                        float *q /* [8][B][ctot] */, float *img4x, float *img4y, double *ent, float *wgt, hipStream_t st) {
+  const int ctot = sd.ctot, H = h[0], W = w[0];
+  int rc;
+  {
+    dim3 grid(cdiv(ctot, 256), B);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_prep_kernel<<<grid, 256, 0, st>>>(part, sd, q, B);
+    if ((rc = check_launch("adists_prep"))) return rc;
+  }
+  {
+    dim3 grid(cdiv(H * W, 256), B);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(x, img4x, H * W);
+    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(y, img4y, H * W);
+    if ((rc = check_launch("nchw3_to_nhwc4"))) return rc;
+  }
+  const size_t qst = (size_t)B * ctot;
+  // stage 0's q/wgt rows are indexed with channel < 3; the NHWC4 kernels read index 3 too, which
+  // is channel 0 of stage 1 in the concatenated vector -- harmless: its feature value is 0 (entropy
+  // term 0) and the window kernel masks c >= creal.
+  if ((rc = launch_entropy<PrecF32>(img4x, B, H * W, 4, ent_ppb[0], q + 0 * qst + sd.coff[0], q + 2 * qst + sd.coff[0],
+                                    ctot, ent + ed.part_off[0], st)))
+    return rc;
+  for (int k = 1; k < 6; ++k) {
+    const int hw = h[k] * w[k];
+    const float *invx = q + 0 * qst + sd.coff[k], *sumx = q + 2 * qst + sd.coff[k];
+    double *ep = ent + ed.part_off[k];
+    switch (storage_prec(prec)) {
+      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
+      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
+      default: rc = launch_entropy<PrecF16>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
+    }
+    if (rc) return rc;
+  }
+  {
+    // hsum reuses the q[2] (sum_x) rows: they are dead once the entropy kernels have run
+    float *hsum = q + 2 * qst;
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), B), 256, 0, st>>>(ent, ed, hsum);
+    adists_weights_kernel<<<B, 256, 0, st>>>(hsum, ed, wgt);
+    if ((rc = check_launch("adists_weights"))) return rc;
+  }
+  return NQA_OK;
+}
+
 static int adists_run(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
                       size_t ws_bytes, float *d_out, float *map_out, void *stream, float *s1_out = nullptr,
                       float *s2_out = nullptr) {
@@ -1294,46 +1355,9 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
   // below writes it: adists_prep_kernel reads it, hsum reuses rows of q, the chain's `ones` lives in bufB ----
   if (s1_out && (rc = finalize(part, p.sd, B, s1_out, s2_out, st))) return rc;
   // ---- per-channel scalars, stage-0 images as NHWC4, entropies, channel weights ----
-  {
-    dim3 grid(cdiv(ctot, 256), B);
-    TimedLaunch t(NQA_K_ADISTS, st);
-    adists_prep_kernel<<<grid, 256, 0, st>>>(part, p.sd, q, B);
-    if ((rc = check_launch("adists_prep"))) return rc;
-  }
-  float *img4x = reinterpret_cast<float *>(base + p.img4x), *img4y = reinterpret_cast<float *>(base + p.img4y);
-  {
-    dim3 grid(cdiv(H * W, 256), B);
-    TimedLaunch t(NQA_K_ADISTS, st);
-    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(x, img4x, H * W);
-    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(y, img4y, H * W);
-    if ((rc = check_launch("nchw3_to_nhwc4"))) return rc;
-  }
-  const size_t qst = (size_t)B * ctot;
-  // stage 0's q/wgt rows are indexed with channel < 3; the NHWC4 kernels read index 3 too, which
-  // is channel 0 of stage 1 in the concatenated vector -- harmless: its feature value is 0 (entropy
-  // term 0) and the window kernel masks c >= creal.
-  if ((rc = launch_entropy<PrecF32>(img4x, B, H * W, 4, p.ent_ppb[0], q + 0 * qst + p.sd.coff[0],
-                                    q + 2 * qst + p.sd.coff[0], ctot, ent + p.ed.part_off[0], st)))
+  if ((rc = launch_front(x, y, taps, B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, part, q,
+                         reinterpret_cast<float *>(base + p.img4x), reinterpret_cast<float *>(base + p.img4y), ent, wgt, st)))
     return rc;
-  for (int k = 1; k < 6; ++k) {
-    const int hw = p.h[k] * p.w[k];
-    const float *invx = q + 0 * qst + p.sd.coff[k], *sumx = q + 2 * qst + p.sd.coff[k];
-    double *ep = ent + p.ed.part_off[k];
-    switch (storage_prec(prec)) {
-      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], B, hw, p.c[k], p.ent_ppb[k], invx, sumx, ctot, ep, st); break;
-      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], B, hw, p.c[k], p.ent_ppb[k], invx, sumx, ctot, ep, st); break;
-      default: rc = launch_entropy<PrecF16>(taps[k - 1], B, hw, p.c[k], p.ent_ppb[k], invx, sumx, ctot, ep, st); break;
-    }
-    if (rc) return rc;
-  }
-  {
-    // hsum reuses the q[2] (sum_x) rows: they are dead once the entropy kernels have run
-    float *hsum = q + 2 * qst;
-    TimedLaunch t(NQA_K_ADISTS, st);
-    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), B), 256, 0, st>>>(ent, p.ed, hsum);
-    adists_weights_kernel<<<B, 256, 0, st>>>(hsum, p.ed, wgt);
-    if ((rc = check_launch("adists_weights"))) return rc;
-  }
   // ---- heavy pass: gamma / TW / SW maps per stage ----
   const Gauss *gp = checked_gauss("adists_forward");
   if (!gp) return NQA_E_LAUNCH;
@@ -1451,6 +1475,129 @@ int nqa_adists_chain(const float *const *gamma, const float *const *tw, const fl
   char *base = static_cast<char *>(ws);
   return launch_chain(cm, B, H, W, reinterpret_cast<ChainAcc *>(base + c.acc), reinterpret_cast<double *>(base + c.part),
                       reinterpret_cast<float *>(base + c.ones), d, map, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
+// The front part on its own (include/nqa.h): the statistics launches that nqa_adists_forward interleaves with its
+// pyramid (stats_nchw, pool_stats per tap 1..4, stats_nhwc on tap 5: the same launch functions with the same arguments),
+// then launch_front.  The taps' sizes are the caller's.  Workspace: pool_stats' discarded pooled maps, the two NHWC4
+// images, the statistics partials, the entropy partials.
+struct FrontPlan {
+  size_t pooled, img4x, img4y, part, ent, total;
+  StageDesc sd;
+  EntDesc ed;
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS], c[NQA_NUM_TAPS], ent_ppb[NQA_NUM_TAPS];
+};
+static int front_check(const char *who, int B, const int *Hk, const int *Wk, int prec) {
+  if (!Hk || !Wk) {
+    set_error("%s: null pointer", who);
+    return NQA_E_ARG;
+  }
+  if (B <= 0 || !prec_valid(prec)) {
+    set_error("%s: bad size or prec (B=%d prec=%d)", who, B, prec);
+    return NQA_E_ARG;
+  }
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    if (Hk[k] <= 0 || Wk[k] <= 0) {
+      set_error("%s: bad size or prec (tap %d: %d x %d)", who, k, Hk[k], Wk[k]);
+      return NQA_E_ARG;
+    }
+    // in-image offsets are 32-bit in places (the NHWC4 image of stage 0 counts as 4 float channels)
+    const long bytes = (long)Hk[k] * Wk[k] * (k == 0 ? 4 : kChns[k]) * (long)(k == 0 ? 4 : prec_elem_bytes(prec));
+    if (bytes >= (1L << 31)) {
+      set_error("%s: tap %d too large for 32-bit in-image byte offsets", who, k);
+      return NQA_E_ARG;
+    }
+  }
+  return NQA_OK;
+}
+static FrontPlan front_plan(int B, const int *Hk, const int *Wk, int prec) {
+  FrontPlan p;
+  memset(&p, 0, sizeof(p));
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    p.h[k] = Hk[k];
+    p.w[k] = Wk[k];
+    p.c[k] = k == 0 ? 3 : kChns[k];
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += align_up(bytes, 256);
+    return o;
+  };
+  size_t pooled = 0;  // 4 bytes per element: float, split16 records, or more than a 16-bit mode needs
+  for (int k = 1; k <= 4; ++k) {
+    const size_t n = (size_t)2 * B * ((p.h[k] + 1) / 2) * ((p.w[k] + 1) / 2) * p.c[k] * 4;
+    pooled = n > pooled ? n : pooled;
+  }
+  p.pooled = take(pooled);
+  p.img4x = take((size_t)B * p.h[0] * p.w[0] * 4 * 4);
+  p.img4y = take((size_t)B * p.h[0] * p.w[0] * 4 * 4);
+  long doff, eoff;
+  front_descs(B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
+  p.part = take((size_t)doff * 8);
+  p.ent = take((size_t)eoff * 8);
+  p.total = off;
+  return p;
+}
+
+extern "C" {
+
+size_t nqa_adists_front_bytes(int B, const int *Hk, const int *Wk, int prec) {
+  if (front_check("adists_front_bytes", B, Hk, Wk, prec)) return 0;
+  return front_plan(B, Hk, Wk, prec).total;
+}
+
+int nqa_adists_front_grid(int B, const int *Hk, const int *Wk, int prec, int *grid) {
+  if (!grid) {
+    set_error("adists_front_grid: null pointer");
+    return NQA_E_ARG;
+  }
+  if (int rc = front_check("adists_front_grid", B, Hk, Wk, prec)) return rc;
+  const FrontPlan p = front_plan(B, Hk, Wk, prec);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    int tr = 0, tc = 0;
+    if (k >= 1 && k <= 4) pool_stats_tiles((p.h[k] + 1) / 2, (p.w[k] + 1) / 2, p.c[k], prec, B, &tr, &tc);
+    grid[4 * k + 0] = p.sd.nblk[k];
+    grid[4 * k + 1] = tr;
+    grid[4 * k + 2] = tc;
+    grid[4 * k + 3] = p.ed.nblk[k];
+  }
+  return NQA_OK;
+}
+
+int nqa_adists_front(const float *x, const float *y, const void *const *taps, int B, const int *Hk, const int *Wk,
+                     int prec, void *ws, size_t ws_bytes, float *q, float *wgt, void *stream) {
+  if (!x || !y || !taps || !Hk || !Wk || !ws || !q || !wgt) {
+    set_error("adists_front: null pointer");
+    return NQA_E_ARG;
+  }
+  for (int k = 0; k < 5; ++k)
+    if (!taps[k]) {
+      set_error("adists_front: null pointer (tap %d)", k + 1);
+      return NQA_E_ARG;
+    }
+  if (int rc = front_check("adists_front", B, Hk, Wk, prec)) return rc;
+  const FrontPlan p = front_plan(B, Hk, Wk, prec);
+  if (ws_bytes < p.total) {
+    set_error("adists_front: workspace %zu < %zu bytes", ws_bytes, p.total);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char *base = static_cast<char *>(ws);
+  double *part = reinterpret_cast<double *>(base + p.part);
+  void *tp[5];
+  for (int k = 0; k < 5; ++k) tp[k] = const_cast<void *>(taps[k]);
+  int rc;
+  if ((rc = stats_nchw(x, y, B, 3, p.h[0] * p.w[0], part + p.sd.part_off[0], st))) return rc;
+  for (int k = 1; k <= 4; ++k)
+    if ((rc = pool_stats(tp[k - 1], B, p.h[k], p.w[k], p.c[k], prec, base + p.pooled, part + p.sd.part_off[k], st)))
+      return rc;
+  if ((rc = stats_nhwc(tp[4], B, p.h[5] * p.w[5], p.c[5], prec, part + p.sd.part_off[5], st))) return rc;
+  return launch_front(x, y, tp, B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, part, q,
+                      reinterpret_cast<float *>(base + p.img4x), reinterpret_cast<float *>(base + p.img4y),
+                      reinterpret_cast<double *>(base + p.ent), wgt, st);
 }
 
 }  // extern "C"

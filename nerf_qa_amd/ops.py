@@ -580,6 +580,76 @@ def adists_chain_into(gamma, tw, sw, h: int, w: int, ps_prod, d, map_out=None, w
           None if map_out is None else ptr(map_out), stream_ptr(dev))
 
 
+def _front_dims(x: torch.Tensor, y: torch.Tensor, taps, p: int):
+    """Every check of adists_front on its inputs but their device; (B, [H_k], [W_k]) for k = 0..5."""
+    if p not in PREC_DTYPE:
+        raise ValueError(f"adists_front: prec {p} is not one of the kernel-level modes")
+    if not isinstance(taps, (list, tuple)) or len(taps) != 5 or not all(torch.is_tensor(t) for t in taps):
+        raise ValueError("adists_front: taps must be a list of five tensors")
+    if not (torch.is_tensor(x) and torch.is_tensor(y)) or x.dim() != 4 or x.shape != y.shape or x.shape[1] != 3 \
+            or x.numel() == 0:
+        raise ValueError("adists_front: expected two non-empty (B,3,H,W) images of equal shape")
+    b = int(x.shape[0])
+    hs, ws = [int(x.shape[2])], [int(x.shape[3])]
+    for name, t in (("x", x), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"adists_front: {name} must be contiguous float32, got {t.dtype}"
+                             f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    for k, t in enumerate(taps):
+        if t.dim() != 4 or t.shape[0] != 2 * b or t.shape[3] != CHNS[k + 1] or t.numel() == 0 \
+                or t.dtype != PREC_DTYPE[p] or not t.is_contiguous():
+            raise ValueError(f"adists_front: tap {k + 1} must be contiguous {PREC_DTYPE[p]} ({2 * b}, H, W, {CHNS[k + 1]}), "
+                             f"got {t.dtype} {tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
+        hs.append(int(t.shape[1]))
+        ws.append(int(t.shape[2]))
+    return b, hs, ws
+
+
+def adists_front(x: torch.Tensor, y: torch.Tensor, taps: Sequence[torch.Tensor], prec, ws: Workspace | None = None):
+    """The front part of adists_forward as it launches it (include/nqa.h, nqa_adists_front): from the images (B,3,H,W)
+    float32 and the five tapped maps, each (2B, H_k, W_k, C_k) NHWC in prec's storage type with the x images first, to
+    (q (8,B,1475), wgt (B,1475)) float32.  q[2] holds the folded per-channel entropy hsum.  The taps' sizes are free."""
+    b = _front_dims(x, y, taps, prec_id(prec))[0]
+    dev = _need_cuda(x, y, *taps)
+    q = torch.empty((8, b, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    wgt = torch.empty((b, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    adists_front_into(x, y, taps, prec, q, wgt, ws)
+    return q, wgt
+
+
+def adists_front_into(x, y, taps, prec, q, wgt, ws: Workspace | None = None) -> None:
+    """adists_front into caller-owned contiguous float32 outputs of the shapes it would return (tests place them between
+    guard regions).  Every check of adists_front applies."""
+    p = prec_id(prec)
+    b, hs, wss = _front_dims(x, y, taps, p)
+    if not (torch.is_tensor(q) and torch.is_tensor(wgt)):
+        raise ValueError("adists_front: q and wgt must be tensors")
+    for name, t, sh in (("q", q, (8, b, TOTAL_CHNS)), ("wgt", wgt, (b, TOTAL_CHNS))):
+        if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"adists_front: {name} must be contiguous float32 {sh}, got {t.dtype} {tuple(t.shape)}")
+    dev = _need_cuda(x, y, *taps, q, wgt)
+    hk, wk = (C.c_int * 6)(*hs), (C.c_int * 6)(*wss)
+    nbytes = lib().nqa_adists_front_bytes(b, hk, wk, p)
+    if nbytes == 0:
+        raise _lib.NqaError(f"libnqa_hip: {lib().nqa_last_error().decode()}")
+    buf = (ws or Workspace()).get(nbytes, dev)
+    tp = (C.c_void_p * 5)(*[ptr(t) for t in taps])
+    _call(dev, lib().nqa_adists_front, ptr(x), ptr(y), tp, b, hk, wk, p, ptr(buf), buf.numel(), ptr(q), ptr(wgt),
+          stream_ptr(dev))
+
+
+def adists_front_grid(b: int, dims: Sequence, prec) -> list:
+    """[(statistics blocks, TR, TC, entropy blocks)] for k = 0..5 of adists_front on B = b pairs with the image and the
+    five taps of dims[k] = (H_k, W_k), from the library's own planning functions; TR, TC are the pool pass' tile (taps
+    1..4, zeros elsewhere)."""
+    if len(dims) != 6:
+        raise ValueError("adists_front_grid: dims must hold six (H, W) pairs")
+    hk, wk = (C.c_int * 6)(*[int(d[0]) for d in dims]), (C.c_int * 6)(*[int(d[1]) for d in dims])
+    g = (C.c_int * 24)()
+    check(lib().nqa_adists_front_grid(int(b), hk, wk, prec_id(prec), g))
+    return [tuple(g[4 * k:4 * k + 4]) for k in range(6)]
+
+
 # ---- input preparation (SURVEY.md section 8 f2) ---------------------------------------------------
 def u8hwc_to_f32nchw(frames: torch.Tensor, pil_roundtrip: bool = False) -> torch.Tensor:
     """ToTensor on the device: uint8 (n,H,W,3) -> float32 (n,3,H,W) / 255 (prep.py:89, data.py:80)."""
