@@ -149,7 +149,9 @@ __device__ inline unsigned long long stamp() {
 #define NQA_STAMP_ADD(seg, a, b)
 #endif
 
-template <int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW>
+// PAD8 (the 16x16x32 loop of conv3x3_igemm_tile): the halo rows lie HP = HW_ rounded up to 8 pixels apart, so that the M16
+// swizzle, which has period 8 pixels, is the same in every halo row; the pad cells are never fetched and never read.
+template <int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool PAD8 = false>
 struct ConvGeom {
   static constexpr int THREADS = 64 * WAVES_N * WAVES_M;
   static constexpr int BN = WAVES_N * WN_T * 32;      // output channels per block
@@ -157,7 +159,8 @@ struct ConvGeom {
   static constexpr int MP = WAVES_M * WM_T * 32;      // output pixels per block
   static constexpr int TH = MP / TW;                  // tile rows
   static constexpr int HW_ = TW + 2, HH_ = TH + 2;    // halo extent
-  static constexpr int NQ = HW_ * HH_;                // halo pixels
+  static constexpr int HP = PAD8 ? (HW_ + 7) / 8 * 8 : HW_;  // halo row pitch, pixels
+  static constexpr int NQ = HP * HH_;                 // halo cells
   static constexpr int A_ITEMS = NQ * 4;              // 16-byte chunks
   static constexpr int A_ITEMS_PAD = (A_ITEMS + 63) / 64 * 64;
   static constexpr int A_BYTES = A_ITEMS_PAD * 16;
@@ -169,6 +172,13 @@ struct ConvGeom {
   static constexpr int LDS_BYTES = 2 * (A_BYTES + W_BYTES);
   static_assert(BN % 64 == 0 && W_ITEMS % THREADS == 0 && MP % TW == 0, "bad conv geometry");
 };
+// The padded geometries against the 160 KB of a CU: one 8-wave block, or two 4-wave blocks side by side.
+static_assert(ConvGeom<2, 4, 4, 2, 32, true>::LDS_BYTES == 149504 && ConvGeom<2, 4, 4, 2, 16, true>::LDS_BYTES == 153600 &&
+                  ConvGeom<2, 4, 2, 4, 32, true>::LDS_BYTES <= 163840,
+              "8-wave M16 tiles: LDS budget");
+static_assert(ConvGeom<2, 2, 2, 2, 32, true>::LDS_BYTES == 79872 && ConvGeom<2, 2, 2, 2, 16, true>::LDS_BYTES == 79872 &&
+                  2 * 79872 <= 163840,
+              "4-wave M16 tiles must keep two blocks per CU");
 
 // LDS row swizzle: chunk c of row r sits at position c ^ lds_swz(r).  The 32x32x16 MFMA reads one
 // chunk of 32 consecutive rows per instruction (rows spread by (r>>2)&3); the 16x16x32 MFMA reads
@@ -197,7 +207,7 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
     int out_split, float floor_v, const int n, const int x0, const int y0, const int ct, char *const smem) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the LDS-DMA builtin exists in the device pass only
   typedef typename P::T T;
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;  // smem: the block's dynamic LDS, [A0][A1][W0][W1]
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW, M16> G;  // smem: the block's dynamic LDS, [A0][A1][W0][W1]
 
   const int tid = threadIdx.x, lane = tid & 63;
   // the wave index as a provably wave-uniform (SGPR) value: every LDS-DMA destination is then
@@ -224,9 +234,9 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
   for (int r = 0; r < G::A_ROUNDS; ++r) {
     const int i = r * G::THREADS + tid;
     const int q = i >> 2, c = (i & 3) ^ lds_swz<M16>(q);
-    const int hy = q / G::HW_, hx = q - hy * G::HW_;
+    const int hy = q / G::HP, hx = q - hy * G::HP;
     const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-    const bool ok = i < G::A_ITEMS && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+    const bool ok = i < G::A_ITEMS && hx < G::HW_ && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
     a_goff[r] = ok ? (unsigned)(((gy * W + gx) * Cin + c * P::CPC) * (int)sizeof(T)) : kOOB;
     if (!ok && i < G::A_ITEMS_PAD) {
       const u32x4 z = {0u, 0u, 0u, 0u};
@@ -252,15 +262,15 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
   // hipcc does not count buffer-to-LDS DMA in its s_waitcnt bookkeeping (and with
   // global_load_lds it degrades every LDS wait in the loop to lgkmcnt(0)), so the DMA is
   // retired by hand: dma_wait() before the barrier that publishes a stage.
-  auto issue = [&](int s) {
+  // (stage s = chunk cc, stage `sub` of its 3 * NTERM; first: sub == 0 -- the stage loop carries both as counters)
+  auto issue = [&](int s, int cc, bool first) {
 #ifndef NQA_ABLATE_NO_DMA
-    const int cc = s / (3 * NTERM);
     char *wdst = smem + 2 * G::A_BYTES + (s & 1) * G::W_BYTES + wave_base;
 #pragma unroll
     for (int r = 0; r < G::W_ROUNDS; ++r)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void_t *)(wdst + r * G::THREADS * 16), 16, w_goff[r],
                                                s * (G::SUB_STAGE_ITEMS * 16), 0, 0);
-    if (s - cc * (3 * NTERM) == 0) {
+    if (first) {
       char *adst = smem + (cc & 1) * G::A_BYTES + wave_base;
 #pragma unroll
       for (int r = 0; r < G::A_ROUNDS; ++r) {
@@ -310,21 +320,29 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
   // M16: the wave's WN_T x WM_T tiles of 32x32 as 2WN_T x 2WM_T tiles of 16x16 (4 accumulators each);
   // lane = (l15: row of the A fragment / column of the B fragment, c4: 16-byte k-chunk of the row)
   const int l15 = lane & 15, c4 = lane >> 4;
-  int w16_addr[2 * WN_T], q16[2 * WM_T];
+  // The stage loop does no per-fragment address arithmetic: a lane holds FOUR addresses for the whole tile, and every
+  // fragment of a stage is one of them plus a compile-time constant (a ds_read_b128 immediate) plus what is uniform over
+  // the stage (buffer parity, kernel row: one add per address per stage).
+  //   weights: fragment i (16 channels) of the wave is row (i & 3) * 16 + l15 of sub-slab wn * WN_T / 2 + (i >> 2); the
+  //     swizzle of that row depends on l15 alone, so i and the tap (kx * 4096) are constants beside w16_base.
+  //   pixels: fragment j (16 pixels) starts 16 * j pixels into the wave's part of the tile, i.e. a whole number of tile
+  //     rows (HP halo cells each) and 0 or 16 columns on: a multiple of 8 cells, like a kernel row (HP cells), so the
+  //     swizzle bit of cell q + kx is that of qb + kx: one base per tap column kx, the rest constants (a16_off).
+  int w16_base = 0, a16_base[3] = {0, 0, 0};
+  auto w16_off = [](int i) { return (i >> 2) * (G::SUB_STAGE_ITEMS * 16) + (i & 3) * 1024; };
+  auto a16_off = [](int j) { return ((j * 16 / TW) * G::HP + j * 16 % TW) * 64; };
   f32x4 acc16[2 * WN_T][2 * WM_T];
   if constexpr (M16) {
+    static_assert(WN_T % 2 == 0 && (TW == 16 || TW == 32) && G::HP % 8 == 0 && (WM_T * 32) % TW == 0,
+                  "the M16 loop's constant fragment offsets");
+    // ds_read immediates hold 16 bits: the last pixel fragment; the last weight fragment of the third tap
+    static_assert(((2 * WM_T - 1) * 16 / TW * G::HP + 16) * 64 < 65536 &&
+                      ((2 * WN_T - 1) >> 2) * (G::SUB_STAGE_ITEMS * 16) + 3 * 1024 + 2 * 4096 < 65536,
+                  "an M16 fragment offset does not fit a ds_read immediate");
+    w16_base = 2 * G::A_BYTES + wn * (WN_T / 2) * (G::SUB_STAGE_ITEMS * 16) + l15 * 64 + ((c4 ^ lds_swz<true>(l15)) << 4);
+    const int qb = (wm * WM_T * 32 / TW) * G::HP + l15;  // halo cell of the lane's pixel of fragment 0 at tap (0, 0)
 #pragma unroll
-    for (int i = 0; i < 2 * WN_T; ++i) {
-      const int cib = wn * WN_T * 32 + i * 16 + l15;
-      const int r64 = cib & 63;
-      w16_addr[i] = 2 * G::A_BYTES + (cib >> 6) * (G::SUB_STAGE_ITEMS * 16) + r64 * 64 + ((c4 ^ lds_swz<true>(r64)) << 4);
-    }
-#pragma unroll
-    for (int j = 0; j < 2 * WM_T; ++j) {
-      const int m = wm * WM_T * 32 + j * 16 + l15;
-      const int ty = m / TW, tx = m - ty * TW;
-      q16[j] = ty * G::HW_ + tx;
-    }
+    for (int kx = 0; kx < 3; ++kx) a16_base[kx] = (qb + kx) * 64 + ((c4 ^ lds_swz<true>(qb + kx)) << 4);
 #pragma unroll
     for (int i = 0; i < 2 * WN_T; ++i)
 #pragma unroll
@@ -334,15 +352,16 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
 #ifdef NQA_STAMPS
   unsigned long long seg_sum[4] = {0, 0, 0, 0};
 #endif
-  issue(0);
-  for (int s = 0; s < S; ++s) {
-    const int cc = s / (3 * NTERM), ky = (s - cc * (3 * NTERM)) / NTERM;
+  issue(0, 0, true);
+  for (int s = 0, cc = 0, sub = 0; s < S; ++s) {
+    const int ky = sub / NTERM;
+    const int sub_next = sub + 1 == 3 * NTERM ? 0 : sub + 1, cc_next = sub_next ? cc : cc + 1;
     NQA_STAMP(t0);
     dma_wait();       // this wave's DMA for stage s has landed
     NQA_STAMP(t1);
     __syncthreads();  // ... and everyone's; every wave has also finished reading stage s-1
     NQA_STAMP(t2);
-    if (s + 1 < S) issue(s + 1);
+    if (s + 1 < S) issue(s + 1, cc_next, sub_next == 0);
     NQA_STAMP(t3);
     NQA_STAMP_ADD(0, t0, t1);
     NQA_STAMP_ADD(1, t1, t2);
@@ -380,17 +399,19 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
       // wave's channel rows: step t = (kx, half) reads WN_T weight fragments, and at half 0 the
       // 2*WM_T pixel fragments of the tap, one step ahead of the MFMAs that use them.
       u32x4 af[2][WN_T], bf[2][2 * WM_T];
+      // the stage's four addresses: the uniform part (scalar) added once to each per-lane base
+      const int a_stage = (cc & 1) * G::A_BYTES + ky * (G::HP * 64);
+      const char *const wst = smem + (w16_base + (s & 1) * G::W_BYTES);
+      const char *const ast[3] = {smem + (a16_base[0] + a_stage), smem + (a16_base[1] + a_stage),
+                                  smem + (a16_base[2] + a_stage)};
       auto load16 = [&](int t) {
         const int kx = t >> 1, half = t & 1;
 #pragma unroll
         for (int i = 0; i < WN_T; ++i)
-          af[t & 1][i] = *reinterpret_cast<const u32x4 *>(wbuf + w16_addr[half * WN_T + i] + kx * 4096);
+          af[t & 1][i] = *reinterpret_cast<const u32x4 *>(wst + (w16_off(half * WN_T + i) + kx * 4096));
         if (half == 0) {
 #pragma unroll
-          for (int j = 0; j < 2 * WM_T; ++j) {
-            const int q = q16[j] + ky * G::HW_ + kx;
-            bf[kx & 1][j] = *reinterpret_cast<const u32x4 *>(abuf + q * 64 + ((c4 ^ lds_swz<true>(q)) << 4));
-          }
+          for (int j = 0; j < 2 * WM_T; ++j) bf[kx & 1][j] = *reinterpret_cast<const u32x4 *>(ast[kx] + a16_off(j));
         }
       };
       auto mma16 = [&](int t) {
@@ -479,6 +500,8 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
     }
     NQA_STAMP(t4);
     NQA_STAMP_ADD(3, t3, t4);
+    cc = cc_next;
+    sub = sub_next;
   }
 #ifdef NQA_STAMPS
   if (lane == 0) {
@@ -605,7 +628,7 @@ template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool
 __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_kernel(
     const typename P::T *__restrict__ in, const char *__restrict__ wpk, const float *__restrict__ bias,
     typename P::T *__restrict__ out, int H, int W, int Cin, int Cout, int tiles_x, int out_split, float floor_v) {
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW, M16> G;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tile_id = xcd_tile_order(blockIdx.x, gridDim.x);
   const int bx = tile_id % tiles_x, by = tile_id / tiles_x;
@@ -628,14 +651,14 @@ __global__ __launch_bounds__(64 * WAVES_N * WAVES_M) void conv3x3_igemm_mixed_ke
   extern __shared__ __attribute__((aligned(16))) char smem[];  // sized for the larger of the two geometries
   const int b = blockIdx.x;
   if (b < n_main) {
-    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32> G;
+    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32, M16> G;
     const int g = xcd_tile_order(b, n_main);
     const int slab = g / main_tiles, tile_id = g - slab * main_tiles;
     const int bx = tile_id % main_tx, by = tile_id / main_tx;
     conv3x3_igemm_tile<P, WAVES_N, WAVES_M, WN_T, WM_T, 32, M16, NTERM>(
         in, wpk, bias, out, H, W, Cin, Cout, out_split, floor_v, slab % N, bx * 32, by * G::TH, slab / N, smem);
   } else {
-    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16> G;
+    typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16, M16> G;
     const int e = b - n_main;
     const int slab = e / edge_ty, by = e - slab * edge_ty;
     conv3x3_igemm_tile<P, WAVES_N, WAVES_M, WN_T, WM_T, 16, M16, NTERM>(
@@ -2476,7 +2499,7 @@ template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, int TW, bool
           bool LOACC = false>
 static int launch_igemm(const void *in, int n, int H, int W, int cin, int cout, const char *wpk, const float *bias,
                         void *out, int out_split, hipStream_t st, float floor_v = 0.f) {
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW> G;
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, TW, M16> G;
   if (const int rc = lds_limit<conv3x3_igemm_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, TW, M16, NTERM, LOACC>>(G::LDS_BYTES, "conv3x3_igemm")) return rc;
   const int tiles_x = cdiv(W, TW), tiles_y = cdiv(H, G::TH);
   dim3 grid(tiles_x * tiles_y, n, cout / G::BN);
@@ -2508,8 +2531,8 @@ static bool use_mixed_grid(int n, int H, int W, int ctiles, int MP, int blocks_p
 template <typename P, int WAVES_N, int WAVES_M, int WN_T, int WM_T, bool M16 = (sizeof(typename P::T) == 2), int NTERM = 1>
 static int launch_igemm_mixed(const void *in, int n, int H, int W, int cin, int cout, const char *wpk, const float *bias,
                               void *out, int out_split, hipStream_t st) {
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32> GM;
-  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16> GE;
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 32, M16> GM;
+  typedef ConvGeom<WAVES_N, WAVES_M, WN_T, WM_T, 16, M16> GE;
   constexpr int LDS = GM::LDS_BYTES > GE::LDS_BYTES ? GM::LDS_BYTES : GE::LDS_BYTES;
   if (const int rc = lds_limit<conv3x3_igemm_mixed_kernel<P, WAVES_N, WAVES_M, WN_T, WM_T, M16, NTERM>>(LDS, "conv3x3_igemm_mixed")) return rc;
   const int main_tx = W / 32, main_tiles = main_tx * cdiv(H, GM::TH), edge_ty = cdiv(H, GE::TH);
