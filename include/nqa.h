@@ -165,6 +165,40 @@ int nqa_vgg_pyramid(const float *x_nchw, int n, int H, int W, const void *packed
 int nqa_dists_forward(const float *x_nchw, const float *y_nchw, int B, int H, int W, const void *packed_w, int prec,
                       void *workspace, size_t workspace_bytes, float *s1, float *s2, void *stream);
 
+/* DISTS of K renders against ONE reference, for R such groups (DISTS_pt.py:105-141 for the R * K pairs; the reference's
+ * scoring tables hold several rows per reference_folder, test2_prep.py:89,201,304,404, and score each row with a
+ * forward of its own): the reference frames go through the pyramid once per group, not once per render -- R + R * K
+ * images where nqa_dists_forward runs 2 * R * K.
+ *   ref      dev float32 NCHW (R,3,H,W); renders  dev float32 NCHW (R,K,3,H,W) contiguous, render k of group r at r * K + k.
+ *   s1, s2   dev float32 (R * K, 1475), pair p = r * K + k: what nqa_dists_forward writes for (ref[r], renders[r][k]) in
+ *            `prec`, up to the order of the fp64 partial sums (another split of the pixels into blocks).
+ * Inside, one NHWC batch of n = R + R * K images: the references first, render (r, k) at image R + r * K + k.  Every
+ * `prec` of nqa_dists_forward, the mixed modes included.  The statistics are nqa_group_stats.hip's kernels: a block
+ * keeps a strip of the reference's tap and walks the group's renders against it, so a tap is read (1 + K) / (2 K) times
+ * as often as by the pairwise kernels; one writer per partial sum, no atomics, bitwise repeatable.  The L2-pools run as
+ * launches of their own: this path has no fused pool + statistics pass and no fused stage-closing kernel.
+ * Workspace: nqa_dists_group_workspace_bytes (0 for arguments the forward refuses).
+ * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, more than 65535 pairs in one call
+ * (slice over R), unknown prec, a frame of H * W * 64 elements reaching 2^31 bytes (nqa_dists_forward's limit);
+ * NQA_E_WORKSPACE a short workspace. */
+size_t nqa_dists_group_workspace_bytes(int R, int K, int H, int W, int prec);
+int nqa_dists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W, const void *packed_w,
+                            int prec, void *workspace, size_t workspace_bytes, float *s1, float *s2, void *stream);
+
+/* ONE map's group statistics and their finalisation on their own, for tests and tools: the launch functions
+ * nqa_dists_forward_group enqueues for a tap (DISTS_pt.py:131-141), with the map's channels as the whole vector.
+ *   feat     dev, n = R + R * K maps of HW pixels, the R references first, render (r, k) at map R + r * K + k.
+ *            nchw = 1: float32 planes (n, C, HW), whatever prec is (the plane kernel, fp64 throughout).
+ *            nchw = 0: NHWC (n, HW, C) in prec's storage type (float for NQA_PREC_F32 / NQA_PREC_F32S), 16-byte aligned,
+ *            C a power-of-two number of 16-byte channel groups (C = 4 .. 1024 floats, 8 .. 2048 halves).
+ *   s1, s2   dev float32 (R * K, C).   scratch: dev, nqa_dists_group_stats_bytes bytes (0 for arguments the call refuses).
+ * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, more than 65535 pairs, prec
+ * outside the four kernel-level modes, a map of HW * C elements reaching 2^31 bytes; NQA_E_SHAPE an NHWC map whose C the
+ * kernel does not take; NQA_E_WORKSPACE a short scratch. */
+size_t nqa_dists_group_stats_bytes(int R, int K, int HW, int C, int prec, int nchw);
+int nqa_dists_group_stats(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
+                          size_t scratch_bytes, float *s1, float *s2, void *stream);
+
 /* The statistics alone on caller-provided float32 NCHW feature lists
  * (forward_from_feats, DISTS_pt.py:181-202).  fx[k], fy[k]: dev (B, C[k], Hk[k], Wk[k]).
  * scratch: dev, nqa_stats_scratch_bytes(B, total pixels...) bytes. */

@@ -590,6 +590,57 @@ class DISTS(torch.nn.Module):
         s1, s2 = self._similarities(x, y, require_grad)
         return self._weighted(s1, s2, batch_average)
 
+    def _group_similarities(self, ref, renders):
+        """(S1, S2), each (R*K, 1475), of renders (R,K,3,H,W) against ref (R,3,H,W) from one shared pyramid per group."""
+        r, k = int(ref.shape[0]), int(renders.shape[1])
+        dev = ref.device
+        prec = self.precision_for(ref.shape[-2], ref.shape[-1], dev)
+        s1, s2 = ops.dists_forward_group(ref, renders, self._packed_weights(dev, prec), prec, self._ws)
+        if self.precision != "auto" or prec == "f32s" or AUTO_FLAT_VAR <= 0.0:
+            return s1, s2
+        # `auto` on a fast rung: the flat-frame guard of _similarities, per pair.  The flatness is measured once per FRAME
+        # (R references, R * K renders; every sixteenth row), and a pair is flagged when either of its frames is flat;
+        # flagged pairs are rescored through the pairwise f32s forward.  (One host look at R * K flags per call, behind
+        # the group forward that is already enqueued.)
+        if torch.cuda.is_current_stream_capturing():
+            raise NqaError("DISTS(precision='auto') on a fast rung looks at the frames on the host (nearly flat frames are "
+                           "rescored in f32s) and cannot be captured into a hipGraph: name the precision "
+                           f"(precision={prec!r} is what this frame size calibrated to) or set NQA_AUTO_FLAT_VAR=0")
+        flat_ref = ref[:, :, ::16].float().var(dim=(2, 3)).mean(dim=1) < AUTO_FLAT_VAR               # (R,)
+        flat_ren = renders[:, :, :, ::16].float().var(dim=(3, 4)).mean(dim=2) < AUTO_FLAT_VAR        # (R, K)
+        idx = (flat_ref[:, None] | flat_ren).flatten().nonzero().flatten()
+        if idx.numel():
+            x = ref[torch.div(idx, k, rounding_mode="floor")].contiguous()
+            y = renders.flatten(0, 1)[idx].contiguous()
+            e1, e2 = ops.dists_forward(x, y, self._packed_weights(dev, "f32s"), "f32s", self._ws)
+            s1.index_copy_(0, idx, e1)
+            s2.index_copy_(0, idx, e2)
+        return s1, s2
+
+    def forward_group(self, ref, renders, batch_average=False):
+        """DISTS of K renders against ONE reference, for R such groups: ref (R,3,H,W), renders (R,K,3,H,W) -> scores
+        (R,K), scores[r, k] = forward(ref[r:r+1], renders[r, k:k+1]) (the reference's tables hold several rows per
+        reference_folder, test2_prep.py:89,201,304,404).  The reference frames go through the VGG pyramid once per group
+        instead of once per render.  Precision: the module's named one, or `auto`'s verdict for the frame size (nearly
+        flat pairs rescored in f32s as in forward).  alpha / beta receive gradients as in forward; the images do not:
+        ValueError for images that require grad (use forward(require_grad=True) per pair) and for shapes that do not
+        fit, NqaError for tensors off the GPU."""
+        if not (torch.is_tensor(ref) and torch.is_tensor(renders)) or ref.dim() != 4 or renders.dim() != 5 \
+                or ref.shape[1] != 3 or renders.shape[0] != ref.shape[0] or renders.shape[2:] != ref.shape[1:] \
+                or ref.numel() == 0 or renders.numel() == 0:
+            raise ValueError("forward_group expects references (R,3,H,W) and renders (R,K,3,H,W), got "
+                             f"{tuple(getattr(ref, 'shape', ()))} / {tuple(getattr(renders, 'shape', ()))}")
+        if torch.is_grad_enabled() and (ref.requires_grad or renders.requires_grad):
+            raise ValueError("forward_group does not differentiate through the shared pyramid: detach the images, or call "
+                             "forward(x, y, require_grad=True) per pair")
+        if not (ref.is_cuda and renders.is_cuda):
+            raise NqaError("nerf_qa_amd runs on the GPU only: got tensors on %s / %s (move inputs and the module to cuda; "
+                           "there is no CPU fallback)" % (ref.device, renders.device))
+        r, k = int(ref.shape[0]), int(renders.shape[1])
+        s1, s2 = self._group_similarities(ref, renders)
+        score = self._weighted(s1, s2, False).reshape(r, k)
+        return score.mean() if batch_average else score
+
     def forward_from_feats(self, feats0, feats1, batch_average=False):
         if torch.is_grad_enabled() and any(f.requires_grad for f in list(feats0) + list(feats1)):
             # the NR models' training loss (model_nr_v8.py:258-265): the same statistics kernel, with a HIP backward

@@ -46,6 +46,10 @@ _SIGNATURES = {
     "nqa_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nqa_vgg_pyramid": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, C.POINTER(_vp), _vp]),
     "nqa_dists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_dists_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_dists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_dists_group_stats_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "nqa_dists_group_stats": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "nqa_stats_scratch_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "nqa_dists_stats_nchw": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   _vp, _sz, _vp, _vp, _vp]),

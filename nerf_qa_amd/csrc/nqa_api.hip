@@ -726,6 +726,142 @@ int nqa_dists_forward(const float *x, const float *y, int B, int H, int W, const
   return finalize(part, p.d, B, s1, s2, st);
 }
 
+// ---- one reference against its K renders (nqa_group_stats.hip) ----
+// Statistics plan of R groups of K renders over `nstage` maps: the partial sums in finalize's layout for B = R * K pairs.
+// nchw[k]: map k is float planes (the plane kernel), else an NHWC tap in kprec[k].
+static StatsPlan group_stats_plan(int R, int K, const int *C, const int *HW, const bool *nchw, const int *kprec, int nstage) {
+  StatsPlan p;
+  memset(&p, 0, sizeof(p));
+  long off = 0;
+  int coff = 0;
+  for (int k = 0; k < nstage; ++k) {
+    p.d.part_off[k] = off;
+    p.d.nblk[k] = nchw[k] ? cdiv(HW[k], stats_nchw_ppb(HW[k])) : cdiv(HW[k], group_stats_units_per_block(HW[k], C[k], kprec[k], R));
+    p.d.hw[k] = HW[k];
+    p.d.c[k] = C[k];
+    p.d.coff[k] = coff;
+    off += (long)R * K * p.d.nblk[k] * C[k] * 5;
+    coff += C[k];
+  }
+  p.d.nstage = nstage;
+  p.d.ctot = coff;
+  p.doubles = (size_t)off;
+  return p;
+}
+// the image and the five taps of an H x W frame in mode `prec`
+static StatsPlan group_forward_plan(int R, int K, int H, int W, int prec) {
+  const PyrDims d = pyr_dims(H, W);
+  int C[6], HW[6], kprec[6];
+  bool nchw[6];
+  for (int k = 0; k < 6; ++k) {
+    C[k] = kChns[k];
+    HW[k] = k ? d.h[k - 1] * d.w[k - 1] : H * W;
+    kprec[k] = k ? stage_prec(prec, k - 1) : NQA_PREC_F32;
+    nchw[k] = k == 0;
+  }
+  return group_stats_plan(R, K, C, HW, nchw, kprec, 6);
+}
+// finalize folds one pair per grid row: R * K pairs must fit a grid's second dimension
+static const long kGroupMaxPairs = 65535;
+static bool bad_group(const char *who, int R, int K) {
+  if (R <= 0 || K <= 0) {
+    set_error("%s: non-positive size R=%d K=%d", who, R, K);
+    return true;
+  }
+  if ((long)R * K > kGroupMaxPairs) {
+    set_error("%s: R*K = %ld pairs, more than %ld in one call", who, (long)R * K, kGroupMaxPairs);
+    return true;
+  }
+  return false;
+}
+
+size_t nqa_dists_group_workspace_bytes(int R, int K, int H, int W, int prec) {
+  if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kGroupMaxPairs || !prec_valid_pyramid(prec)) return 0;
+  return 2 * act_bytes(R + R * K, H, W, prec) + align_up(group_forward_plan(R, K, H, W, prec).doubles * 8, 256);
+}
+
+int nqa_dists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W, const void *packed, int prec,
+                            void *ws, size_t ws_bytes, float *s1, float *s2, void *stream) {
+  if (!ref || !renders || !packed || !ws || !s1 || !s2) {
+    set_error("dists_forward_group: null pointer");
+    return NQA_E_ARG;
+  }
+  if (bad_group("dists_forward_group", R, K)) return NQA_E_ARG;
+  const int n = R + R * K;
+  if (bad_dims("dists_forward_group", n, H, W, prec, 64, true)) return NQA_E_ARG;
+  const size_t need = nqa_dists_group_workspace_bytes(R, K, H, W, prec);
+  if (ws_bytes < need) {
+    set_error("dists_forward_group: workspace %zu < %zu bytes", ws_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t ab = act_bytes(n, H, W, prec);
+  char *bufA = static_cast<char *>(ws), *bufB = bufA + ab;
+  double *part = reinterpret_cast<double *>(bufB + ab);
+  const StatsPlan p = group_forward_plan(R, K, H, W, prec);
+  int rc;
+  // feature 0 is the raw image (DISTS_pt.py:103): statistics straight from the inputs
+  if ((rc = group_stats_nchw(ref, renders, R, K, 3, H * W, part + p.d.part_off[0], st))) return rc;
+  // the references occupy images [0,R) of one NHWC batch, render (r, k) image R + r * K + k
+  rc = run_stages(ref, renders, R, bufA, bufB, n, H, W, packed, prec, nullptr,
+                  [&](int k, void *tap, int hk, int wk, int ck, void *) {
+                    const int kp = stage_prec(prec, k);  // (mixed mode: half taps up to the boundary, float ones behind)
+                    const char *rn = static_cast<const char *>(tap) + (size_t)R * hk * wk * ck * prec_elem_bytes(kp);
+                    return group_stats_nhwc(tap, rn, R, K, hk * wk, ck, kp, part + p.d.part_off[k + 1], st);
+                  },
+                  st);
+  if (rc) return rc;
+  return finalize(part, p.d, R * K, s1, s2, st);
+}
+
+size_t nqa_dists_group_stats_bytes(int R, int K, int HW, int C, int prec, int nchw) {
+  if (R <= 0 || K <= 0 || HW <= 0 || C <= 0 || (long)R * K > kGroupMaxPairs || !prec_valid(prec)) return 0;
+  if (!nchw && !group_stats_nhwc_ok(C, prec)) return 0;
+  const bool planes = nchw != 0;
+  return align_up(group_stats_plan(R, K, &C, &HW, &planes, &prec, 1).doubles * 8, 256);
+}
+
+int nqa_dists_group_stats(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
+                          size_t scratch_bytes, float *s1, float *s2, void *stream) {
+  if (!feat || !scratch || !s1 || !s2) {
+    set_error("dists_group_stats: null pointer");
+    return NQA_E_ARG;
+  }
+  if (bad_group("dists_group_stats", R, K)) return NQA_E_ARG;
+  if (HW <= 0 || C <= 0) {
+    set_error("dists_group_stats: non-positive size HW=%d C=%d", HW, C);
+    return NQA_E_ARG;
+  }
+  if (!prec_valid(prec)) {
+    set_error(is_mixed(prec) ? "dists_group_stats: takes no mixed mode (prec %d): pass the kernel precision of the map's own stage"
+                             : "dists_group_stats: unknown prec %d", prec);
+    return NQA_E_ARG;
+  }
+  const long eb = nchw ? 4 : (long)prec_elem_bytes(prec);  // (planes are float whatever prec is)
+  if ((long)HW * C * eb >= (1L << 31)) {
+    set_error("dists_group_stats: map too large (HW*%d channels*%d bytes >= 2^31)", C, (int)eb);
+    return NQA_E_ARG;
+  }
+  if (!nchw && !group_stats_nhwc_ok(C, prec)) {
+    set_error("dists_group_stats: no NHWC kernel for C=%d in prec %d (whole 16-byte groups, a power-of-two number of them)", C, prec);
+    return NQA_E_SHAPE;
+  }
+  const bool planes = nchw != 0;
+  const StatsPlan p = group_stats_plan(R, K, &C, &HW, &planes, &prec, 1);
+  if (scratch_bytes < p.doubles * 8) {
+    set_error("dists_group_stats: scratch %zu < %zu bytes", scratch_bytes, p.doubles * 8);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *part = static_cast<double *>(scratch);
+  const size_t map_bytes = (size_t)HW * C * eb;
+  const char *ren = static_cast<const char *>(feat) + (size_t)R * map_bytes;
+  const int rc = nchw ? group_stats_nchw(static_cast<const float *>(feat), reinterpret_cast<const float *>(ren), R, K, C, HW, part, st)
+                      : group_stats_nhwc(feat, ren, R, K, HW, C, prec, part, st);
+  if (rc) return rc;
+  return finalize(part, p.d, R * K, s1, s2, st);
+}
+
 size_t nqa_stats_scratch_bytes(int B, const int C[NQA_NUM_TAPS], const int Hk[NQA_NUM_TAPS],
                                const int Wk[NQA_NUM_TAPS]) {
   if (B <= 0 || !C || !Hk || !Wk) return 0;

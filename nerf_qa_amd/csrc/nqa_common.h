@@ -315,6 +315,12 @@ int pool_stats(const void *feat, int B, int H, int W, int C, int prec, void *poo
 int stats_nhwc(const void *feat, int B, int HW, int C, int prec, double *part, hipStream_t st);
 int stats_nchw(const float *fx, const float *fy, int B, int C, int HW, double *part, hipStream_t st);
 int finalize(const double *part, const StageDesc &d, int B, float *s1, float *s2, hipStream_t st);
+// ---- one reference against its K renders (nqa_group_stats.hip): R reference maps, then render (r, k) at r * K + k;
+// partial sums in finalize's layout with B := R * K, pair p = r * K + k ----
+int group_stats_units_per_block(int units, int C, int prec, int R);
+bool group_stats_nhwc_ok(int C, int prec);
+int group_stats_nhwc(const void *ref, const void *ren, int R, int K, int HW, int C, int prec, double *part, hipStream_t st);
+int group_stats_nchw(const float *ref, const float *ren, int R, int K, int C, int HW, double *part, hipStream_t st);
 // ---- backward of the NCHW statistics (nqa_stats_backward.hip; forward_from_feats under autograd) ----
 // per-plane fp64 coefficients {mx, my, a, b, ox, oy} from the forward's partials and dL/dS1, dL/dS2 (B, ctot);
 // tap k's planes (b, c) at record B * coff[k] + b * C[k] + c

@@ -283,6 +283,63 @@ def dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, 
     return s1, s2
 
 
+def _group_dims(ref: torch.Tensor, renders: torch.Tensor):
+    """(R, K, H, W) of a (R,3,H,W) reference batch and its (R,K,3,H,W) renders; ValueError where they do not fit."""
+    if ref.dim() != 4 or ref.shape[1] != 3 or renders.dim() != 5 or renders.shape[0] != ref.shape[0] \
+            or renders.shape[2:] != ref.shape[1:] or ref.numel() == 0 or renders.numel() == 0:
+        raise ValueError(f"expected references (R,3,H,W) and renders (R,K,3,H,W), got {tuple(ref.shape)} / "
+                         f"{tuple(renders.shape)}")
+    return int(ref.shape[0]), int(renders.shape[1]), int(ref.shape[2]), int(ref.shape[3])
+
+
+def dists_forward_group(ref: torch.Tensor, renders: torch.Tensor, packed: torch.Tensor, prec,
+                        ws: Workspace | None = None):
+    """(S1, S2), each float32 (R*K, 1475), of K renders against ONE reference for R such groups: ref (R,3,H,W), renders
+    (R,K,3,H,W), pair r * K + k = (ref[r], renders[r, k]).  The references go through the pyramid once per group
+    (include/nqa.h, nqa_dists_forward_group).  Groups are independent: a batch whose workspace would exceed
+    NQA_MAX_WORKSPACE_GB runs in equal slices over R."""
+    p = prec_id(prec)
+    dev = _need_cuda(ref, renders, packed)
+    r, k, h, w = _group_dims(ref, renders)
+    ref, renders = _f32c(ref), _f32c(renders)
+    mr = _max_pairs(lambda n: lib().nqa_dists_group_workspace_bytes(n, k, h, w, p), r)
+    mr = max(1, min(mr, 65535 // k))  # (pairs of one call: the library's limit)
+    if mr < r:
+        parts = [dists_forward_group(ref[i:i + mr], renders[i:i + mr], packed, prec, ws) for i in range(0, r, mr)]
+        return torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
+    s1 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    s2 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev)
+    nbytes = lib().nqa_dists_group_workspace_bytes(r, k, h, w, p)
+    buf = (ws or Workspace()).get(nbytes, dev)
+    _call(dev, lib().nqa_dists_forward_group, ptr(ref), ptr(renders), r, k, h, w, ptr(packed), p, ptr(buf), buf.numel(),
+          ptr(s1), ptr(s2), stream_ptr(dev))
+    return s1, s2
+
+
+def dists_group_stats(feat: torch.Tensor, r: int, k: int, prec, nchw: bool = False):
+    """(S1, S2), each float32 (r*k, C), of ONE map's group statistics as dists_forward_group launches them (include/nqa.h,
+    nqa_dists_group_stats).  feat holds n = r + r*k maps, the r references first, render (i, j) at map r + i*k + j:
+    nchw=True float32 planes (n, C, HW); else NHWC (n, HW, C) in prec's storage type."""
+    p = prec_id(prec)
+    dev = _need_cuda(feat)
+    r, k = int(r), int(k)
+    if p not in PREC_DTYPE:
+        raise ValueError(f"dists_group_stats: prec {p} is not one of the kernel-level modes")
+    want = torch.float32 if nchw else PREC_DTYPE[p]
+    if feat.dim() != 3 or r <= 0 or k <= 0 or feat.shape[0] != r + r * k or feat.numel() == 0 or feat.dtype != want \
+            or not feat.is_contiguous():
+        raise ValueError(f"dists_group_stats: expected contiguous {want} ({r + r * k}, "
+                         f"{'C, HW' if nchw else 'HW, C'}), got {feat.dtype} {tuple(feat.shape)}")
+    c, hw = (int(feat.shape[1]), int(feat.shape[2])) if nchw else (int(feat.shape[2]), int(feat.shape[1]))
+    s1 = torch.empty((r * k, c), dtype=torch.float32, device=dev)
+    s2 = torch.empty((r * k, c), dtype=torch.float32, device=dev)
+    nbytes = lib().nqa_dists_group_stats_bytes(r, k, hw, c, p, int(nchw))
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_dists_group_stats, ptr(feat), r, k, hw, c, p, int(nchw), ptr(scratch), nbytes, ptr(s1), ptr(s2),
+          stream_ptr(dev))
+    return s1, s2
+
+
 def _feats_args(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor]):
     """Two lists of six NCHW maps -> (device, float32 contiguous maps 0 and 1, B, the C / H / W / pointer arrays)."""
     if len(feats0) != 6 or len(feats1) != 6:

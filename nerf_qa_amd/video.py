@@ -11,7 +11,7 @@ BATCHES of the DataLoader (:181), not of frames -- reproduced as written.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Iterable, Optional
+from typing import Callable, Dict, Iterable, List, Optional
 
 import numpy as np
 import torch
@@ -136,6 +136,49 @@ def score_video(ref: torch.Tensor, render: torch.Tensor, dists_model: Optional[t
     if return_frame_scores:
         out["_frame_scores"] = frames
     return out
+
+
+@torch.no_grad()
+def score_videos(ref: torch.Tensor, renders, dists_model: torch.nn.Module, batch_size: int = 8, group=None,
+                 policy: Optional[str] = None, keep_aspect_ratio: bool = False, suffix: str = "",
+                 with_frame_bias: bool = True, return_frame_scores: bool = False) -> List[Dict[str, object]]:
+    """DISTS of K rendered videos of ONE scene against its reference video (the rows of the reference's tables that share
+    a reference_folder, test2_prep.py:89,201,304,404): `ref` as score_video takes it, `renders` a (K,N,...) tensor or a
+    list of K tensors of ref's shape.  Returns a list of K column dicts, entry k what
+    score_video(ref, renders[k], dists_model, ...) returns -- but every batch of reference frames goes through the VGG
+    pyramid ONCE for the K renders (DISTS.forward_group) instead of once per render.  Frames are taken in batches of
+    `batch_size` reference frames (each with its K renders); under a process group the frame ranges shard as in
+    score_video and ONE all-gather moves the (N, K) score table."""
+    rens = list(renders.unbind(0)) if torch.is_tensor(renders) else list(renders)
+    if not rens:
+        raise ValueError("score_videos: no renders")
+    for k, t in enumerate(rens):
+        if not torch.is_tensor(t) or t.shape != ref.shape:
+            raise ValueError(f"score_videos: render {k} differs from ref in shape: {tuple(getattr(t, 'shape', ()))} vs "
+                             f"{tuple(ref.shape)}")
+    n, kk = ref.shape[0], len(rens)
+    if getattr(dists_model, "precision", None) == "auto" and policy is None:  # one precision mode per video (score_video)
+        sharding.agree_precision(dists_model, int(ref.shape[-2]), int(ref.shape[-1]), ref.device, group)
+
+    def batch(lo, hi):
+        a, bs = ref[lo:hi], [t[lo:hi] for t in rens]
+        if policy is not None:
+            a = prep.prepare_frames(a, policy, keep_aspect_ratio=keep_aspect_ratio)
+            bs = [prep.prepare_frames(b, policy, keep_aspect_ratio=keep_aspect_ratio) for b in bs]
+        return dists_model.forward_group(a, torch.stack(bs, dim=1), batch_average=False)
+
+    table = sharding.score_frames_sharded(batch, n, batch_size, ref.device, group, columns=kk).cpu().numpy().reshape(n, kk)
+    outs = []
+    for k in range(kk):
+        s = np.ascontiguousarray(table[:, k])
+        out: Dict[str, object] = dict(video_columns("DISTS", s, suffix))
+        if with_frame_bias:
+            out["frame_count"] = -(-n // batch_size)  # len(DataLoader): batches, as the reference counts them
+            out["frame_bias_dists"] = to_str(frame_bias(s))
+        if return_frame_scores:
+            out["_frame_scores"] = {"DISTS": s}
+        outs.append(out)
+    return outs
 
 
 # the order test2_prep.py:183-193 assigns the first pass's columns in

@@ -1,0 +1,177 @@
+"""The group statistics kernels on their own (nqa_group_stats.hip through nqa_dists_group_stats / ops.dists_group_stats):
+one reference map against its K renders, R groups, finalised to S1 / S2.
+
+Yardstick: S1 / S2 from a float64 evaluation of DISTS_pt.py:131-141 on the very values the kernel reads (the stored
+floats or halves).  The bound is the error of the SAME formula evaluated in float32 numpy against that float64 result,
+floored at 2^-22 (S1 and S2 are at most 1: four float ulps of the result): a kernel that accumulates in fp64 must not be
+worse than the reference's own arithmetic.  Both figures are printed.
+
+Shapes: the partial-sum plan of group_stats_units_per_block gives a thread 4 strip items at small maps (strips shorter
+than one pass of the block at HW = 1, a ragged last block at 35 / 299 / 77, up to 97 blocks per map at 1551) and up to
+its 16 registers' worth at large ones -- (1, 2, 6007, 512) and (1, 2, 24589, 512) reach 7 / 16 items in float and 4 / 16
+in f16, with a ragged last block whose threads hold different item counts.  The plane kernel: one pixel, one ragged
+block, and 4097 pixels = two blocks with one pixel in the second.
+"""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+FLOOR = 2.0 ** -22
+NHWC_SHAPES = [(1, 1, 1, 64), (2, 3, 35, 64), (1, 5, 299, 128), (3, 2, 1551, 256), (2, 4, 77, 512),
+               (1, 2, 6007, 512), (1, 2, 24589, 512)]
+NCHW_HW = [1, 35, 4097]
+STORAGE = {"f32": torch.float32, "f16": torch.float16}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _maps(n, hw, c, seed, dtype):
+    """Non-negative ReLU-like maps (n, HW, C) with channel-dependent mean and spread; every seventh channel exactly dead in
+    all maps, every eleventh dead in the references' position 0 only.  Returned in the storage type."""
+    g = torch.Generator().manual_seed(seed)
+    scale = 0.05 + 2.0 * torch.rand(c, generator=g)
+    shift = torch.rand(c, generator=g) - 0.3
+    v = ((torch.randn(n, hw, c, generator=g) + shift) * scale).clamp_(min=0)
+    v[:, :, ::7] = 0
+    v[0, :, 3::11] = 0
+    return v.to(dtype)
+
+
+def _group_maps(R, K, hw, c, seed, dtype):
+    """n = R + R K maps: the renders are their reference plus noise, blurred along the pixels, or independent."""
+    ref = _maps(R, hw, c, seed, torch.float32)
+    other = _maps(R * K, hw, c, seed + 1, torch.float32)
+    ren = torch.empty(R, K, hw, c)
+    for r in range(R):
+        for k in range(K):
+            kind = (r + k) % 3
+            if kind == 0:
+                ren[r, k] = (ref[r] + 0.1 * other[r * K + k]).clamp_(min=0) * (ref[r] > 0)
+            elif kind == 1:
+                ren[r, k] = 0.5 * (ref[r] + ref[r].roll(1, 0))
+            else:
+                ren[r, k] = other[r * K + k]
+    return torch.cat([ref, ren.flatten(0, 1)]).to(dtype).contiguous()
+
+
+def _s_ref(x, y, np_dtype):
+    """DISTS_pt.py:131-141 for maps (pairs, HW, C) in numpy arithmetic of `np_dtype`."""
+    x, y = x.astype(np_dtype), y.astype(np_dtype)
+    c1 = c2 = np_dtype(1e-6)
+    two = np_dtype(2)
+    xm, ym = x.mean(1, keepdims=True, dtype=np_dtype), y.mean(1, keepdims=True, dtype=np_dtype)
+    s1 = (two * xm * ym + c1) / (xm ** 2 + ym ** 2 + c1)
+    xv = ((x - xm) ** 2).mean(1, keepdims=True, dtype=np_dtype)
+    yv = ((y - ym) ** 2).mean(1, keepdims=True, dtype=np_dtype)
+    cov = (x * y).mean(1, keepdims=True, dtype=np_dtype) - xm * ym
+    s2 = (two * cov + c2) / (xv + yv + c2)
+    return s1[:, 0], s2[:, 0]
+
+
+def _yardstick(feat_nhwc, R, K):
+    """(float64 S1, S2, the float32 replay's max error) for stored maps (n, HW, C)."""
+    v = feat_nhwc.float().numpy()
+    x = np.repeat(v[:R], K, axis=0)
+    y = v[R:]
+    w1, w2 = _s_ref(x, y, np.float64)
+    f1, f2 = _s_ref(x, y, np.float32)
+    assert f1.dtype == np.float32 and f2.dtype == np.float32
+    replay = max(np.abs(f1 - w1).max(), np.abs(f2 - w2).max())
+    return w1, w2, float(replay)
+
+
+@pytest.mark.parametrize("storage", list(STORAGE))
+@pytest.mark.parametrize("shape", NHWC_SHAPES, ids=lambda s: "R%dK%d_hw%d_c%d" % s)
+def test_nhwc_kernel_against_float64(shape, storage, dev):
+    from nerf_qa_amd import ops
+    R, K, hw, c = shape
+    feat = _group_maps(R, K, hw, c, 1000 + hw + c, STORAGE[storage])
+    w1, w2, replay = _yardstick(feat, R, K)
+    s1, s2 = ops.dists_group_stats(feat.to(dev), R, K, storage)
+    assert s1.shape == s2.shape == (R * K, c) and s1.dtype == torch.float32
+    e1 = np.abs(s1.cpu().numpy() - w1).max()
+    e2 = np.abs(s2.cpu().numpy() - w2).max()
+    bound = max(replay, FLOOR)
+    print(f"\ngroup_stats nhwc {shape} [{storage}] |dS1|={e1:.2e} |dS2|={e2:.2e} float32 replay={replay:.2e} bound={bound:.2e}")
+    assert np.isfinite(s1.cpu().numpy()).all() and np.isfinite(s2.cpu().numpy()).all()
+    assert max(e1, e2) <= bound
+    # the same kernel under "f32s" (float taps) and, for halves, nothing else to alias
+    if storage == "f32":
+        t1, t2 = ops.dists_group_stats(feat.to(dev), R, K, "f32s")
+        assert torch.equal(t1, s1) and torch.equal(t2, s2)
+
+
+@pytest.mark.parametrize("hw", NCHW_HW)
+def test_plane_kernel_against_float64(hw, dev):
+    from nerf_qa_amd import ops
+    R, K, c = 2, 3, 3
+    g = torch.Generator().manual_seed(77 + hw)
+    ref = torch.rand(R, hw, c, generator=g)
+    ren = (ref[:, None] + 0.1 * torch.randn(R, K, hw, c, generator=g)).clamp_(0, 1)
+    ren[0, 1] = torch.rand(hw, c, generator=g)
+    ref[1, :, 2] = 0  # an exactly dead plane against live renders ...
+    ren[1, :, :, 1] = 0  # ... and dead renders against a live reference
+    ref[0, :, 0] = 0
+    ren[0, :, :, 0] = 0  # ... and a plane dead in both
+    feat = torch.cat([ref, ren.flatten(0, 1)]).contiguous()
+    w1, w2, replay = _yardstick(feat, R, K)
+    planes = feat.transpose(1, 2).contiguous().to(dev)  # (n, C, HW)
+    for prec in ("f32", "f16"):  # planes are float whatever prec says
+        s1, s2 = ops.dists_group_stats(planes, R, K, prec, nchw=True)
+        e1, e2 = np.abs(s1.cpu().numpy() - w1).max(), np.abs(s2.cpu().numpy() - w2).max()
+        bound = max(replay, FLOOR)
+        print(f"\ngroup_stats planes hw={hw} [{prec}] |dS1|={e1:.2e} |dS2|={e2:.2e} float32 replay={replay:.2e} bound={bound:.2e}")
+        assert s1.shape == (R * K, c) and max(e1, e2) <= bound
+    assert s1[0, 0].item() == 1.0 and s2[0, 0].item() == 1.0
+
+
+@pytest.mark.parametrize("case", [("f32", False, 2, 4, 77, 512), ("f16", False, 3, 3, 1551, 256), ("f32", False, 1, 4, 6007, 512),
+                                  ("f32", True, 2, 4, 4097, 3), ("f32", True, 1, 3, 35, 3)],
+                         ids=lambda c: "%s_%s_R%dK%d_hw%d_c%d" % (c[0], "planes" if c[1] else "nhwc", *c[2:]))
+def test_exact_properties(case, dev):
+    """A render identical to its reference: S1 = S2 = 1.0 exactly.  Duplicated renders: bit-equal rows.  Permuted renders:
+    permuted rows, bit for bit.  Two calls: bit-equal."""
+    from nerf_qa_amd import ops
+    storage, nchw, R, K, hw, c = case
+    feat = _group_maps(R, K, hw, c, 5 + hw, STORAGE[storage])
+    if nchw:
+        feat = feat.clamp(0, 1)
+    ref, ren = feat[:R], feat[R:].view(R, K, hw, c).clone()
+    ren[:, 0] = ref           # identical to the reference
+    ren[:, K - 1] = ren[:, 1]  # a duplicate
+
+    def run(rn):
+        f = torch.cat([ref, rn.flatten(0, 1)]).contiguous()
+        if nchw:
+            f = f.transpose(1, 2).contiguous()
+        s1, s2 = ops.dists_group_stats(f.to(dev), R, K, storage, nchw=nchw)
+        return s1.view(R, K, c), s2.view(R, K, c)
+
+    s1, s2 = run(ren)
+    live = (ref.float().abs().amax(dim=1) > 0).to(dev)  # (R, C)
+    assert live.any() and not live.all()
+    assert (s1[:, 0][live] == 1.0).all() and (s2[:, 0][live] == 1.0).all()
+    assert (s1[:, 0] == 1.0).all() and (s2[:, 0] == 1.0).all()  # (dead in both: (0 + c) / (0 + c))
+    assert torch.equal(s1[:, K - 1], s1[:, 1]) and torch.equal(s2[:, K - 1], s2[:, 1])
+    assert not torch.equal(s2[:, 1], s2[:, 0])
+    t1, t2 = run(ren)
+    assert torch.equal(t1, s1) and torch.equal(t2, s2)
+    perm = torch.roll(torch.arange(K), 1)
+    if K > 2:
+        perm[[0, 1]] = perm[[1, 0]]
+    p1, p2 = run(ren[:, perm])
+    assert torch.equal(p1, s1[:, perm.to(dev)]) and torch.equal(p2, s2[:, perm.to(dev)])
+    # a group's rows do not depend on the other groups either
+    if R > 1:
+        f = torch.cat([ref[1:2], ren[1]]).contiguous()
+        if nchw:
+            f = f.transpose(1, 2).contiguous()
+        o1, o2 = ops.dists_group_stats(f.to(dev), 1, K, storage, nchw=nchw)
+        if nchw or R * hw < 2048:  # (the NHWC strip length follows R * HW: the same split only while it stays at 4 items)
+            assert torch.equal(o1, s1[1]) and torch.equal(o2, s2[1])
