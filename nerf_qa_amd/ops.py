@@ -104,28 +104,38 @@ def conv1_1(x: torch.Tensor, packed: torch.Tensor, prec) -> torch.Tensor:
     return out
 
 
-def conv1_fused(x: torch.Tensor, packed: torch.Tensor, prec) -> torch.Tensor:
+def _out_or_empty(out, shape, dtype, dev: torch.device) -> torch.Tensor:
+    """A caller-owned output (tests pre-fill it, so that a store the kernel skipped shows) or a fresh torch.empty."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    _need_cuda(out)
+    assert out.device == dev and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()
+    return out
+
+
+def conv1_fused(x: torch.Tensor, packed: torch.Tensor, prec, out: torch.Tensor | None = None) -> torch.Tensor:
     """relu1_2 (NHWC) straight from the image: conv1_1 + conv1_2 in one kernel (16-bit modes and "f32s": float out; a
-    mixed mode: two-term weights, half out, only where the pyramid fuses stage 1 -- NqaError for W < 16)."""
+    mixed mode: two-term weights, half out, only where the pyramid fuses stage 1 -- NqaError for W < 16).  out: a
+    contiguous tensor of the result's shape and dtype to write into instead of a new one."""
     p = prec_id(prec)
     dev = _need_cuda(x, packed)
     x = _f32c(x)
     n, c, h, w = x.shape
     assert c == 3
-    out = torch.empty((n, h, w, 64), dtype=_stage_dtype(p, 0), device=dev)
+    out = _out_or_empty(out, (n, h, w, 64), _stage_dtype(p, 0), dev)
     _call(dev, lib().nqa_conv1_fused, ptr(x), n, h, w, ptr(packed), p, ptr(out), stream_ptr(dev))
     return out
 
 
-def conv3x3_relu(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec) -> torch.Tensor:
+def conv3x3_relu(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec, out: torch.Tensor | None = None) -> torch.Tensor:
     """One VGG conv layer, NHWC.  "f32s": split16 in; float out for TAP_LAYERS, split16 out otherwise.  A mixed mode:
-    half in and out where the layer's stage is a 16-bit one, the f32s formats behind it."""
+    half in and out where the layer's stage is a 16-bit one, the f32s formats behind it.  out: as conv1_fused's."""
     p = prec_id(prec)
     dev = _need_cuda(inp, packed)
     assert inp.dtype == _stage_dtype(p, CONV_STAGE[layer]) and inp.is_contiguous()
     n, h, w, c = inp.shape
     assert c == CONV_CIN[layer]
-    out = torch.empty((n, h, w, CONV_COUT[layer]), dtype=inp.dtype, device=dev)
+    out = _out_or_empty(out, (n, h, w, CONV_COUT[layer]), inp.dtype, dev)
     _call(dev, lib().nqa_conv3x3_relu, ptr(inp), n, h, w, layer, ptr(packed), p, ptr(out), stream_ptr(dev))
     return out
 
@@ -152,11 +162,13 @@ def l2pool_f16_to_split16(inp: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def conv_pool_stats(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec):
+def conv_pool_stats(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec, pooled: torch.Tensor | None = None,
+                    sums: torch.Tensor | None = None):
     """The stage-closing conv `layer` + ReLU + L2-pool + statistics sums in ONE kernel (include/nqa.h,
     nqa_conv_pool_stats): `inp` is the 2B-image NHWC batch of the layer's input (x images then y images); returns
     (pooled (2B, ceil(H/2), ceil(W/2), Cout) in the next stage's input dtype, sums float64 (B, Cout, 5) = sum x, sum y,
-    sum x^2, sum y^2, sum xy over the tap's pixels).  Raises NqaError where no fused form exists (only conv2_2 so far)."""
+    sum x^2, sum y^2, sum xy over the tap's pixels).  Raises NqaError where no fused form exists (only conv2_2 so far).  pooled, sums:
+    contiguous tensors of those shapes and dtypes to write into instead of new ones."""
     p = prec_id(prec)
     dev = _need_cuda(inp, packed)
     assert inp.is_contiguous() and inp.shape[0] % 2 == 0
@@ -164,9 +176,9 @@ def conv_pool_stats(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec):
     assert c == CONV_CIN[layer]
     b = n // 2
     cout = CONV_COUT[layer]
-    pooled = torch.empty((n, (h + 1) // 2, (w + 1) // 2, cout), dtype=PREC_DTYPE[_lib.stage_prec(p, CONV_STAGE[layer] + 1)]
-                         if p in _lib.MIXED_STAGES else inp.dtype, device=dev)
-    sums = torch.empty((b, cout, 5), dtype=torch.float64, device=dev)
+    pooled = _out_or_empty(pooled, (n, (h + 1) // 2, (w + 1) // 2, cout),
+                           PREC_DTYPE[_lib.stage_prec(p, CONV_STAGE[layer] + 1)] if p in _lib.MIXED_STAGES else inp.dtype, dev)
+    sums = _out_or_empty(sums, (b, cout, 5), torch.float64, dev)
     nbytes = lib().nqa_conv_pool_workspace_bytes(b, h, w, layer)
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
     _call(dev, lib().nqa_conv_pool_stats, ptr(inp), b, h, w, layer, ptr(packed), p, ptr(pooled), ptr(sums), ptr(ws), ws.numel(),
@@ -174,16 +186,18 @@ def conv_pool_stats(inp: torch.Tensor, layer: int, packed: torch.Tensor, prec):
     return pooled, sums
 
 
-def conv1_pool_stats(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec):
+def conv1_pool_stats(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, pooled: torch.Tensor | None = None,
+                     sums: torch.Tensor | None = None):
     """Stage 1 + L2-pool + tap-1 statistics in ONE kernel from the raw frames (include/nqa.h, nqa_conv1_pool_stats):
-    x, y (B,3,H,W) float32 -> (pooled relu1_2 (2B, ceil(H/2), ceil(W/2), 64) f16 NHWC, x images first; sums float64 (B, 64, 5))."""
+    x, y (B,3,H,W) float32 -> (pooled relu1_2 (2B, ceil(H/2), ceil(W/2), 64) f16 NHWC, x images first; sums float64 (B, 64, 5)).
+    pooled, sums: as conv_pool_stats'."""
     p = prec_id(prec)
     dev = _need_cuda(x, y, packed)
     x, y = _f32c(x), _f32c(y)
     b, c, h, w = x.shape
     assert c == 3 and y.shape == x.shape
-    pooled = torch.empty((2 * b, (h + 1) // 2, (w + 1) // 2, 64), dtype=torch.float16, device=dev)
-    sums = torch.empty((b, 64, 5), dtype=torch.float64, device=dev)
+    pooled = _out_or_empty(pooled, (2 * b, (h + 1) // 2, (w + 1) // 2, 64), torch.float16, dev)
+    sums = _out_or_empty(sums, (b, 64, 5), torch.float64, dev)
     nbytes = lib().nqa_conv_pool_workspace_bytes(b, h, w, 1)
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
     _call(dev, lib().nqa_conv1_pool_stats, ptr(x), ptr(y), b, h, w, ptr(packed), p, ptr(pooled), ptr(sums), ptr(ws), ws.numel(),

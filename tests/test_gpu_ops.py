@@ -95,8 +95,10 @@ def test_conv1_fused(stage1, prec, shape, np_convs, packed, dev):
 def test_f32s_stage1_fused(shape, np_convs, packed, dev):
     """f32s stage 1 in one kernel (conv1_regw_split_kernel: conv1_1 on MFMA with three-term products feeding a three-term
     conv1_2 through LDS, 4 x 32 tiles) == the two convolutions in float64, to float32-class accuracy, at ragged sizes
-    (partial tiles in both directions, frames smaller than a tile, more tiles than CUs), and == the round-2 pair of
-    kernels (first-forms bit of nqa_set_conv_variant) to the rounding of another summation order."""
+    (partial tiles in both directions, frames smaller than a tile), and == the round-2 pair of kernels (first-forms bit
+    of nqa_set_conv_variant) to the rounding of another summation order.  The largest shape, 1 x 130 x 95, is 99 tiles: on
+    a 256-CU device no block owns more than one, so the kernel's tile ring never wraps here; blocks that walk several
+    tiles are held to the same bar by tests/test_gpu_conv_persistent.py."""
     from nerf_qa_amd import ops
     x = _rand(shape, 77)
     mean = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float64).view(1, 3, 1, 1)
