@@ -199,6 +199,38 @@ size_t nqa_dists_group_stats_bytes(int R, int K, int HW, int C, int prec, int nc
 int nqa_dists_group_stats(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
                           size_t scratch_bytes, float *s1, float *s2, void *stream);
 
+/* The PAIR path's two statistics passes on their own, for tests and tools: the launch functions nqa_dists_forward and
+ * nqa_adists_forward enqueue for a tapped map, unchanged, and one fold of their per-block fp64 partials.
+ *   nqa_pool_stats   L2pooling.forward (DISTS_pt.py:22-25) and the five sums behind DISTS_pt.py:131-139 of ONE tap in one
+ *           pass (pool_stats_kernel): what the forwards run on taps 1..4 wherever no conv kernel closes the tap itself.
+ *   nqa_pool_stats_f16_to_split16   the same pass behind a mixed mode's last 16-bit stage: half in, split16 records out
+ *           (as nqa_l2pool_f16_to_split16), C a multiple of 16.
+ *   nqa_stats_nhwc   the sums alone (stats_nhwc_kernel): what the forwards run on the last tap, relu5_3.
+ *   feat     dev NHWC, 2B maps (2B, H, W, C) or (2B, HW, C): the B x maps, then the B y maps, in prec's storage type (float
+ *            for NQA_PREC_F32 / NQA_PREC_F32S), 16-byte aligned; C a power-of-two number of 16-byte channel groups, at most
+ *            256 of them (C = 4 .. 1024 floats, 8 .. 2048 halves; NQA_PREC_F32S writes split16 and needs C % 16 == 0).
+ *   pooled   dev (2B, ceil(H/2), ceil(W/2), C) as nqa_l2pool writes it for `prec` (split16 in NQA_PREC_F32S), bit for bit.
+ *   sums     dev double (B, C, 5) = {sum x, sum y, sum x^2, sum y^2, sum xy} over the H * W stored values of pair b's maps,
+ *            per channel: per-thread shifted float moments, fp64 from the block reduction on (nqa_moments.h).
+ *   ws       dev, nqa_pool_stats_workspace_bytes / nqa_stats_nhwc_workspace_bytes bytes (the per-block partials, B * blocks
+ *            * C * 5 doubles; 0 for arguments the call refuses; the split16 form takes NQA_PREC_F16's).
+ * nqa_pool_stats_grid: out[0..4] = tile rows TR, tile columns TC, tiles across the pooled map, tiles per pair, blocks of
+ * the launch, from the launcher's own planning function.  nqa_stats_nhwc_grid: out[0..2] = pixels per block, blocks per
+ * pair, pixels a block takes side by side.  Both are host-only and touch no device.
+ * Refused on the host, before any launch, with a message naming the function: NQA_E_ARG null pointer, non-positive size,
+ * a mixed or unknown prec, more than 65535 pairs, a map of H * W * C elements reaching 2^31 bytes; NQA_E_SHAPE a C the
+ * kernels do not take; NQA_E_WORKSPACE a short workspace. */
+size_t nqa_pool_stats_workspace_bytes(int B, int H, int W, int C, int prec);
+size_t nqa_stats_nhwc_workspace_bytes(int B, int HW, int C, int prec);
+int nqa_pool_stats_grid(int B, int H, int W, int C, int prec, int out[5]);
+int nqa_stats_nhwc_grid(int B, int HW, int C, int prec, int out[3]);
+int nqa_pool_stats(const void *feat, int B, int H, int W, int C, int prec, void *pooled, double *sums, void *ws,
+                   size_t ws_bytes, void *stream);
+int nqa_pool_stats_f16_to_split16(const void *feat_f16, int B, int H, int W, int C, void *pooled_split16, double *sums,
+                                  void *ws, size_t ws_bytes, void *stream);
+int nqa_stats_nhwc(const void *feat, int B, int HW, int C, int prec, double *sums, void *ws, size_t ws_bytes,
+                   void *stream);
+
 /* The statistics alone on caller-provided float32 NCHW feature lists
  * (forward_from_feats, DISTS_pt.py:181-202).  fx[k], fy[k]: dev (B, C[k], Hk[k], Wk[k]).
  * scratch: dev, nqa_stats_scratch_bytes(B, total pixels...) bytes. */

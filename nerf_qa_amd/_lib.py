@@ -50,6 +50,13 @@ _SIGNATURES = {
     "nqa_dists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
     "nqa_dists_group_stats_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "nqa_dists_group_stats": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_pool_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_stats_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "nqa_pool_stats_grid": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "nqa_stats_nhwc_grid": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
+    "nqa_pool_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nqa_pool_stats_f16_to_split16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nqa_stats_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "nqa_stats_scratch_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "nqa_dists_stats_nchw": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   _vp, _sz, _vp, _vp, _vp]),

@@ -1028,6 +1028,138 @@ int nqa_conv_pool_stats(const void *in, int B, int H, int W, int layer, const vo
   return check_launch("part_reduce");
 }
 
+// ---- the pair path's pool + statistics pass and its last-tap statistics pass as single operators (tests, tools; the
+// forwards call the launchers directly).  The launchers run unchanged; part_reduce_kernel folds their partials. ----
+static const int kPairStatsMaxPairs = 65535;  // (stats_nhwc_kernel's grid.y)
+// every host-side check the three entries share; HW: the pixels of one input map
+static int pair_stats_bad(const char *who, int B, int H, int W, int C, int prec, bool split16_out) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) {
+    set_error("%s: non-positive size B=%d H=%d W=%d C=%d", who, B, H, W, C);
+    return NQA_E_ARG;
+  }
+  if (!prec_valid(prec)) {
+    set_error(is_mixed(prec) ? "%s: takes no mixed mode (prec %d): pass the kernel precision of the map's own stage"
+                             : "%s: unknown prec %d", who, prec);
+    return NQA_E_ARG;
+  }
+  if (B > kPairStatsMaxPairs) {
+    set_error("%s: B = %d pairs, at most %d in one call", who, B, kPairStatsMaxPairs);
+    return NQA_E_ARG;
+  }
+  const long eb = (long)prec_elem_bytes(prec);
+  if ((long)H * W > ((1L << 31) - 1) / ((long)C * eb)) {  // (no product of all four: that could overflow)
+    set_error("%s: map too large (H*W*%d channels*%d bytes >= 2^31)", who, C, (int)eb);
+    return NQA_E_ARG;
+  }
+  const int cpc = (int)(16 / eb), G = C / cpc;  // a thread owns one 16-byte channel group; 256 / G pixels side by side
+  if (C % cpc || G > 256 || (G & (G - 1)) || (split16_out && C % 16)) {
+    set_error("%s: no kernel for C=%d in prec %d (whole 16-byte channel groups, a power-of-two number of them up to 256%s)",
+              who, C, prec, split16_out ? ", whole 16-channel split16 records" : "");
+    return NQA_E_SHAPE;
+  }
+  return NQA_OK;
+}
+static int pool_stats_plan(int B, int H, int W, int C, int prec, int *tr, int *tc) {
+  return pool_stats_tiles((H + 1) / 2, (W + 1) / 2, C, prec, B, tr, tc);
+}
+
+size_t nqa_pool_stats_workspace_bytes(int B, int H, int W, int C, int prec) {
+  if (pair_stats_bad("pool_stats_workspace_bytes", B, H, W, C, prec, prec == NQA_PREC_F32S)) return 0;
+  return align_up((size_t)B * pool_stats_plan(B, H, W, C, prec, nullptr, nullptr) * C * 5 * sizeof(double), 256);
+}
+size_t nqa_stats_nhwc_workspace_bytes(int B, int HW, int C, int prec) {
+  if (pair_stats_bad("stats_nhwc_workspace_bytes", B, HW, 1, C, prec, false)) return 0;
+  return align_up((size_t)B * cdiv(HW, stats_units_per_block(HW, C, prec, B)) * C * 5 * sizeof(double), 256);
+}
+
+int nqa_pool_stats_grid(int B, int H, int W, int C, int prec, int out[5]) {
+  if (!out) {
+    set_error("pool_stats_grid: null pointer");
+    return NQA_E_ARG;
+  }
+  const int rc = pair_stats_bad("pool_stats_grid", B, H, W, C, prec, prec == NQA_PREC_F32S);
+  if (rc) return rc;
+  int TR, TC;
+  const int nblk = pool_stats_plan(B, H, W, C, prec, &TR, &TC);
+  out[0] = TR;
+  out[1] = TC;
+  out[2] = cdiv((W + 1) / 2, TC);
+  out[3] = nblk;
+  out[4] = nblk * B;
+  return NQA_OK;
+}
+int nqa_stats_nhwc_grid(int B, int HW, int C, int prec, int out[3]) {
+  if (!out) {
+    set_error("stats_nhwc_grid: null pointer");
+    return NQA_E_ARG;
+  }
+  const int rc = pair_stats_bad("stats_nhwc_grid", B, HW, 1, C, prec, false);
+  if (rc) return rc;
+  out[0] = stats_units_per_block(HW, C, prec, B);
+  out[1] = cdiv(HW, out[0]);
+  out[2] = 256 / (C / (int)(16 / prec_elem_bytes(prec)));
+  return NQA_OK;
+}
+
+static int fold_partials(const double *part, int B, int nblk, int C, double *sums, hipStream_t st) {
+  const long total = (long)B * C * 5;
+  part_reduce_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(part, nblk, C, sums, total);
+  return check_launch("part_reduce");
+}
+static int pool_stats_entry(const char *who, const void *feat, int B, int H, int W, int C, int prec, bool to_split16,
+                            void *pooled, double *sums, void *ws, size_t ws_bytes, void *stream) {
+  if (!feat || !pooled || !sums || !ws) {
+    set_error("%s: null pointer", who);
+    return NQA_E_ARG;
+  }
+  int rc = pair_stats_bad(who, B, H, W, C, prec, to_split16 || prec == NQA_PREC_F32S);
+  if (rc) return rc;
+  const int nblk = pool_stats_plan(B, H, W, C, prec, nullptr, nullptr);
+  if ((long)nblk * B > 0x7fffffffL) {
+    set_error("%s: %d tiles x %d pairs do not fit the launch grid", who, nblk, B);
+    return NQA_E_SHAPE;
+  }
+  const size_t need = (size_t)B * nblk * C * 5 * sizeof(double);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *part = static_cast<double *>(ws);
+  rc = to_split16 ? pool_stats_to_split16(feat, B, H, W, C, pooled, part, st) : pool_stats(feat, B, H, W, C, prec, pooled, part, st);
+  if (rc) return rc;
+  return fold_partials(part, B, nblk, C, sums, st);
+}
+
+int nqa_pool_stats(const void *feat, int B, int H, int W, int C, int prec, void *pooled, double *sums, void *ws,
+                   size_t ws_bytes, void *stream) {
+  return pool_stats_entry("pool_stats", feat, B, H, W, C, prec, false, pooled, sums, ws, ws_bytes, stream);
+}
+int nqa_pool_stats_f16_to_split16(const void *feat_f16, int B, int H, int W, int C, void *pooled_split16, double *sums,
+                                  void *ws, size_t ws_bytes, void *stream) {
+  return pool_stats_entry("pool_stats_f16_to_split16", feat_f16, B, H, W, C, NQA_PREC_F16, true, pooled_split16, sums, ws,
+                          ws_bytes, stream);
+}
+int nqa_stats_nhwc(const void *feat, int B, int HW, int C, int prec, double *sums, void *ws, size_t ws_bytes,
+                   void *stream) {
+  if (!feat || !sums || !ws) {
+    set_error("stats_nhwc: null pointer");
+    return NQA_E_ARG;
+  }
+  int rc = pair_stats_bad("stats_nhwc", B, HW, 1, C, prec, false);
+  if (rc) return rc;
+  const int nblk = cdiv(HW, stats_units_per_block(HW, C, prec, B));
+  const size_t need = (size_t)B * nblk * C * 5 * sizeof(double);
+  if (ws_bytes < need) {
+    set_error("stats_nhwc: workspace %zu < %zu bytes", ws_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *part = static_cast<double *>(ws);
+  if ((rc = stats_nhwc(feat, B, HW, C, prec, part, st))) return rc;
+  return fold_partials(part, B, nblk, C, sums, st);
+}
+
 int nqa_dists_score(const float *s1, const float *s2, const float *alpha, const float *beta, int B, float *out,
                     void *stream) {
   if (!s1 || !s2 || !alpha || !beta || !out || B <= 0) {

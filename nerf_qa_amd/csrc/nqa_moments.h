@@ -41,7 +41,10 @@ struct ShiftedMoments {  // N channels held as N/2 float pairs, so every update 
       case 1: return ay + nn * q;
       case 2: return (double)s2x[e2][k] + 2.0 * p * ax + nn * p * p;
       case 3: return (double)s2y[e2][k] + 2.0 * q * ay + nn * q * q;
-      default: return (double)sxy[e2][k] + q * ax + p * ay + nn * p * q;
+      // the two cross terms are summed FIRST: each product of two floats is exact in fp64, so their sum rounds once,
+      // the same way with x and y exchanged, and for y == x it is 2 p ax exactly -- sum xy is then sum x^2 bit for bit
+      // (added one after the other to sxy, the last bit depended on which image was called x)
+      default: return (double)sxy[e2][k] + (q * ax + p * ay) + nn * p * q;
     }
   }
 };

@@ -205,6 +205,72 @@ def conv1_pool_stats(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, pre
     return pooled, sums
 
 
+def _pair_maps(who: str, feat: torch.Tensor, b: int, p: int, dims: int) -> None:
+    if p not in PREC_DTYPE:
+        raise ValueError(f"{who}: prec {p} is not one of the kernel-level modes")
+    if feat.dim() != dims or int(b) <= 0 or feat.shape[0] != 2 * int(b) or feat.numel() == 0 or feat.dtype != PREC_DTYPE[p] \
+            or not feat.is_contiguous():
+        raise ValueError(f"{who}: expected contiguous {PREC_DTYPE[p]} ({2 * int(b)}, {'H, W' if dims == 4 else 'HW'}, C), "
+                         f"the x maps then the y maps, got {feat.dtype} {tuple(feat.shape)}")
+
+
+def pool_stats(feat: torch.Tensor, b: int, prec, pooled: torch.Tensor | None = None, sums: torch.Tensor | None = None,
+               to_split16: bool = False):
+    """L2-pool + the five statistics sums of ONE tap in one pass, as the pair forwards launch it (include/nqa.h,
+    nqa_pool_stats): feat (2b, H, W, C) NHWC in prec's storage type, the b x maps then the b y maps -> (pooled (2b,
+    ceil(H/2), ceil(W/2), C) as l2pool writes it -- split16 records in a float32 tensor for "f32s" -- and sums float64
+    (b, C, 5) = sum x, sum y, sum x^2, sum y^2, sum xy).  to_split16: the mixed modes' boundary form (prec "f16": half in,
+    split16 records out).  pooled, sums: as conv_pool_stats'."""
+    p = prec_id(prec)
+    dev = _need_cuda(feat)
+    _pair_maps("pool_stats", feat, b, p, 4)
+    if to_split16 and p != _lib.PREC_F16:
+        raise ValueError("pool_stats: to_split16 is the f16 -> split16 boundary form (prec 'f16')")
+    n, h, w, c = feat.shape
+    b = int(b)
+    pooled = _out_or_empty(pooled, (n, (h + 1) // 2, (w + 1) // 2, c), torch.float32 if to_split16 else feat.dtype, dev)
+    sums = _out_or_empty(sums, (b, c, 5), torch.float64, dev)
+    nbytes = lib().nqa_pool_stats_workspace_bytes(b, h, w, c, p)
+    ws = torch.full((max(nbytes, 256),), 0xFF, dtype=torch.uint8, device=dev)  # (a block that never ran leaves NaN sums)
+    if to_split16:
+        _call(dev, lib().nqa_pool_stats_f16_to_split16, ptr(feat), b, h, w, c, ptr(pooled), ptr(sums), ptr(ws), nbytes,
+              stream_ptr(dev))
+    else:
+        _call(dev, lib().nqa_pool_stats, ptr(feat), b, h, w, c, p, ptr(pooled), ptr(sums), ptr(ws), nbytes, stream_ptr(dev))
+    return pooled, sums
+
+
+def stats_nhwc(feat: torch.Tensor, b: int, prec, sums: torch.Tensor | None = None) -> torch.Tensor:
+    """The five statistics sums of the last tap as the pair forwards launch them (include/nqa.h, nqa_stats_nhwc): feat
+    (2b, HW, C) NHWC in prec's storage type, the b x maps then the b y maps -> sums float64 (b, C, 5).  sums: as
+    conv_pool_stats'."""
+    p = prec_id(prec)
+    dev = _need_cuda(feat)
+    _pair_maps("stats_nhwc", feat, b, p, 3)
+    _, hw, c = feat.shape
+    b = int(b)
+    sums = _out_or_empty(sums, (b, c, 5), torch.float64, dev)
+    nbytes = lib().nqa_stats_nhwc_workspace_bytes(b, hw, c, p)
+    ws = torch.full((max(nbytes, 256),), 0xFF, dtype=torch.uint8, device=dev)  # (a block that never ran leaves NaN sums)
+    _call(dev, lib().nqa_stats_nhwc, ptr(feat), b, hw, c, p, ptr(sums), ptr(ws), nbytes, stream_ptr(dev))
+    return sums
+
+
+def pool_stats_grid(b: int, h: int, w: int, c: int, prec) -> tuple:
+    """(TR, TC, tiles across, tiles per pair, blocks of the launch) of pool_stats for these arguments, from the launcher's
+    own planning function (no device is touched)."""
+    g = (C.c_int * 5)()
+    check(lib().nqa_pool_stats_grid(int(b), int(h), int(w), int(c), prec_id(prec), g))
+    return tuple(g)
+
+
+def stats_nhwc_grid(b: int, hw: int, c: int, prec) -> tuple:
+    """(pixels per block, blocks per pair, pixels a block takes side by side) of stats_nhwc for these arguments."""
+    g = (C.c_int * 3)()
+    check(lib().nqa_stats_nhwc_grid(int(b), int(hw), int(c), prec_id(prec), g))
+    return tuple(g)
+
+
 def nhwc_to_nchw_f32(inp: torch.Tensor, prec) -> torch.Tensor:
     p = prec_id(prec)
     dev = _need_cuda(inp)
