@@ -16,6 +16,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "nqa_regw.h"
 #include "nqa_stages.h"
 
 namespace nqa {
@@ -459,7 +460,6 @@ __device__ inline void win_row(const float (&x)[kWin], const float (&y)[kWin], W
 //   * the 42 taps of a wave are ds_read_b32 at immediate offsets from one address register.
 // The arithmetic (horizontal sums, 21-row register ring, vertical sums, T / S / gamma, channel reduction) is
 // the kernel above, instruction for instruction.
-typedef __attribute__((address_space(3))) void lds_void_a_t;
 
 template <typename P, int C>
 __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
       char *slot = smem_w + (r % R) * ROWB;
 #pragma unroll
       for (int i = 0; i < NPW; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(pimg[i] ? ry : rx, (lds_void_a_t *)(slot + pdst[i]), 16,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(pimg[i] ? ry : rx, (lds_void_t *)(slot + pdst[i]), 16,
                                                  voff[i] + (unsigned)(cb * SZ), (unsigned)r * row_stride, 0, 0);
     };
     // every wave has finished reading the previous channel block's last rows before their slots are refilled

@@ -80,6 +80,11 @@ struct PrecBF16 {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
                                                    0, 0);
   }
+  // the 16x16x32 shape (one chunk pair -> K = 32 of a 16 x 16 tile)
+  __device__ static inline f32x4 mma16(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
+                                                   0, 0);
+  }
 };
 struct PrecF16 {
   typedef _Float16 T;
@@ -93,6 +98,10 @@ struct PrecF16 {
   __device__ static inline T from_f(float v) { return (T)v; }
   __device__ static inline f32x16 mma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
+                                                  0);
+  }
+  __device__ static inline f32x4 mma16(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
                                                   0);
   }
 };

@@ -24,6 +24,7 @@
 // f32s: split-f16 products on split16 activations; 16-bit: v_mfma_f32_16x16x32).
 
 #include "nqa_common.h"
+#include "nqa_regw.h"
 
 namespace nqa {
 
@@ -47,8 +48,6 @@ __global__ __launch_bounds__(256) void conv1_1_kernel(const float *__restrict__ 
   const int n = blockIdx.y;
   const bool live = pix < HW;
   const int py = live ? pix / W : 0, px = live ? pix - py * W : 0;
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
   float in[27];
   const float *xi = x + (size_t)n * 3 * HW;
 #pragma unroll
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(256) void conv1_1_kernel(const float *__restrict__ 
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         float v = 0.f;
-        if (ok) v = (xi[(size_t)c * HW + gy * W + gx] - mean[c]) / sd[c];
+        if (ok) v = (xi[(size_t)c * HW + gy * W + gx] - kMean[c]) / kStd[c];
         in[(ky * 3 + kx) * 3 + c] = v;
       }
     }
@@ -131,7 +130,6 @@ __global__ __launch_bounds__(256) void conv1_1_kernel(const float *__restrict__ 
 // Both LDS images are filled by LDS-DMA (buffer_load_dwordx4 ... lds: per-lane source
 // offset, wave-linear destination), double-buffered, so the loop has ONE barrier per
 // stage: vmcnt(0) + barrier retires stage s while stage s+1 is already in flight.
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 #ifdef NQA_STAMPS  // diagnostic build: per-segment shader-cycle sums of the stage loop (never shipped)
 __device__ unsigned long long g_stamps[8];
@@ -180,15 +178,6 @@ static_assert(ConvGeom<2, 2, 2, 2, 32, true>::LDS_BYTES == 79872 && ConvGeom<2, 
                   2 * 79872 <= 163840,
               "4-wave M16 tiles must keep two blocks per CU");
 
-// LDS row swizzle: chunk c of row r sits at position c ^ lds_swz(r).  The 32x32x16 MFMA reads one
-// chunk of 32 consecutive rows per instruction (rows spread by (r>>2)&3); the 16x16x32 MFMA reads
-// all four chunks of 16 consecutive rows (chunk = lane>>4), which is conflict-free from any base
-// row with 2*((r>>2)&1) (found by exhaustive search over the ds_read_b128 lane groups).
-template <bool M16>
-__host__ __device__ inline int lds_swz(int r) {
-  return M16 ? ((r >> 2) & 1) * 2 : (r >> 2) & 3;
-}
-
 // M16: 16-bit modes on v_mfma_f32_16x16x32 (the chip holds a higher clock on it than on 32x32x16
 // at equal cycles per FLOP); weights of those layers are packed with the matching swizzle.
 // NTERM = 2 (f16 activations, NQA_PREC_F32M's layers 1..6): the weights come as f16 (hi, lo) pairs, packed as TWO
@@ -228,7 +217,6 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
   // ---- LDS-DMA plan: halo tile.  Buffer loads with the image as the buffer: an out-of-image
   // halo pixel gets an out-of-range offset, so the DMA transfers nothing for it (or zeros);
   // those LDS cells are zeroed once below and stay zero -- that is the conv's zero padding.
-  const unsigned kOOB = 0x80000000u;
   unsigned a_goff[G::A_ROUNDS];
 #pragma unroll
   for (int r = 0; r < G::A_ROUNDS; ++r) {
@@ -421,12 +409,7 @@ __device__ __forceinline__ void conv3x3_igemm_tile(
 #pragma unroll
           for (int j = 0; j < 2 * WM_T; ++j) {
             f32x4 &c = acc16[half * WN_T + i][j];
-            if constexpr (P::ID == NQA_PREC_BF16)
-              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[t & 1][i]),
-                                                          __builtin_bit_cast(bf16x8, bf[kx & 1][j]), c, 0, 0, 0);
-            else
-              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[t & 1][i]),
-                                                         __builtin_bit_cast(f16x8, bf[kx & 1][j]), c, 0, 0, 0);
+            c = P::mma16(af[t & 1][i], bf[kx & 1][j], c);
           }
       };
       load16(0);
@@ -712,20 +695,10 @@ __global__ __launch_bounds__(512) void conv3x3_regw_kernel(const typename P::T *
   const int l15 = lane & 15, c4 = lane >> 4;
   const int cg = wave % NG, ph = wave / NG;
 
-  // ---- this block's tiles: XCD x owns tiles [T*x/8, T*(x+1)/8), dealt round-robin to its blocks ----
-  const int nblk = gridDim.x, nx = nblk < 8 ? nblk : 8;  // (a grid of fewer than 8 blocks has fewer classes)
-  const int xcd = blockIdx.x % nx, jb = blockIdx.x / nx;
-  const int blk_per_xcd = (nblk - xcd + nx - 1) / nx;  // blocks with id = xcd (mod nx)
-  const int t_lo = (int)((long)total_tiles * xcd / nx), t_hi = (int)((long)total_tiles * (xcd + 1) / nx);
-  const int my_tiles = t_lo + jb < t_hi ? (t_hi - t_lo - jb - 1) / blk_per_xcd + 1 : 0;
+  const TileRun run(total_tiles);  // this block's tiles, XCD-aware
+  const int my_tiles = run.count;
   if (my_tiles == 0) return;  // (block-uniform)
-  auto tile_coords = [&](int it, int &n, int &x0, int &y0) {
-    const int t = t_lo + jb + it * blk_per_xcd;
-    n = t / (tiles_x * tiles_y);
-    const int t2 = t - n * (tiles_x * tiles_y), by = t2 / tiles_x;
-    x0 = (t2 - by * tiles_x) * TW;
-    y0 = by * TH;
-  };
+  auto tile_coords = [&](int it, int &n, int &x0, int &y0) { run.coords<TH, TW>(it, tiles_x, tiles_y, n, x0, y0); };
 
   // ---- weights: 2 tiles of 16 channels x 18 k-steps, straight into registers ----
   u32x4 wf[2][18];
@@ -733,6 +706,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw_kernel(const typename P::T *
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int ks = 0; ks < 18; ++ks)
+      // (load_wfrag<18>(wreg, cg, i, ks, lane) of nqa_regw.h, written out: through the helper this kernel's code changes)
       wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)cg * 2 + i) * 18 + ks) * 64 + lane) * 16);
   float bia[2][4];
 #pragma unroll
@@ -746,19 +720,15 @@ __global__ __launch_bounds__(512) void conv3x3_regw_kernel(const typename P::T *
   int p_hy[3], p_hx[3], p_c[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const int j = r * 512 + tid, q = j >> 2;
-    p_hy[r] = q < NQ ? q / HWD : -100000;  // items past the patch: never inside any image
-    p_hx[r] = q - (q / HWD) * HWD;
-    // the chunk swizzle goes by the pixel's COLUMN in the patch, not by its linear index: equally conflict-free
-    // (a row of the patch only shifts the phase of the pattern), and a tap's LDS address is then one per-lane
-    // constant per kx plus compile-time offsets -- no address arithmetic in the k loop (see tap_base below)
-    p_c[r] = (j & 3) ^ lds_swz<true>(p_hx[r]);
+    const HaloItem hi = halo_item<NQ, HWD>(r * 512 + tid);
+    p_hy[r] = hi.hy;
+    p_hx[r] = hi.hx;
+    p_c[r] = hi.c;
   }
   // per-lane byte offset of this lane's fragment of patch column l15 + kx (any patch row, 16-pixel group 0)
   int tap_base[3];
 #pragma unroll
-  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = (l15 + kx) * 64 + ((c4 ^ lds_swz<true>(l15 + kx)) << 4);
-  const unsigned kOOB = 0x80000000u;
+  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = tap_offset(l15 + kx, c4);
   const unsigned img_in_bytes = (unsigned)H * (unsigned)W * 64u * (unsigned)sizeof(T);
   const unsigned img_out_bytes = (unsigned)H * (unsigned)W * (unsigned)COUT * (unsigned)sizeof(T);
   auto issue_halo = [&](int it, int slot_idx) {
@@ -829,12 +799,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw_kernel(const typename P::T *
         for (int g = 0; g < GPP; ++g)
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            if constexpr (P::ID == NQA_PREC_BF16)
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[i][ks]),
-                                                                  __builtin_bit_cast(bf16x8, bf[ks & 1][g]), acc[i][g], 0, 0, 0);
-            else
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[i][ks]),
-                                                                 __builtin_bit_cast(f16x8, bf[ks & 1][g]), acc[i][g], 0, 0, 0);
+            acc[i][g] = P::mma16(wf[i][ks], bf[ks & 1][g], acc[i][g]);
           }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -899,20 +864,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_kernel(const typename 
   const int l15 = lane & 15, c4 = lane >> 4;
   const int nct = Cout / BC;
 
-  const int nblk = gridDim.x, nx = nblk < 8 ? nblk : 8;
-  const int xcd = blockIdx.x % nx, jb = blockIdx.x / nx;
-  const int blk_per_xcd = (nblk - xcd + nx - 1) / nx;
-  const int t_lo = (int)((long)total_tiles * xcd / nx), t_hi = (int)((long)total_tiles * (xcd + 1) / nx);
-  const int my_tiles = t_lo + jb < t_hi ? (t_hi - t_lo - jb - 1) / blk_per_xcd + 1 : 0;
+  const TileRun run(total_tiles);  // this block's tiles, XCD-aware
+  const int my_tiles = run.count;
   if (my_tiles == 0) return;  // (block-uniform)
   auto tile_coords = [&](int it, int &n, int &x0, int &y0, int &ct) {
-    const int t = t_lo + jb + it * blk_per_xcd;
+    const int t = run.first + it * run.stride;
     ct = t % nct;  // channel tile fastest: the blocks of one pixel tile are neighbours in time and place
-    const int tp = t / nct;
-    n = tp / (tiles_x * tiles_y);
-    const int t2 = tp - n * (tiles_x * tiles_y), by = t2 / tiles_x;
-    x0 = (t2 - by * tiles_x) * TW;
-    y0 = by * TH;
+    TileRun::decode<TH, TW>(t / nct, tiles_x, tiles_y, n, x0, y0);
   };
 
   // ---- weights: 2 tiles of 16 channels x 36 k-steps; the channel tile of this block's first tile (re-loaded if a
@@ -927,7 +885,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_kernel(const typename 
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
-        wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)g * 2 + i) * NKS + ks) * 64 + lane) * 16);
+        wf[i][ks] = load_wfrag<NKS>(wreg, g, i, ks, lane);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -940,15 +898,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_kernel(const typename 
   int p_hy[4], p_hx[4], p_c[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int j = r * 256 + tid, q = j >> 2;
-    p_hy[r] = q < NQ ? q / HWD : -100000;
-    p_hx[r] = q - (q / HWD) * HWD;
-    p_c[r] = (j & 3) ^ lds_swz<true>(p_hx[r]);  // swizzled by the patch COLUMN (see conv3x3_regw_kernel)
+    const HaloItem hi = halo_item<NQ, HWD>(r * 256 + tid);
+    p_hy[r] = hi.hy;
+    p_hx[r] = hi.hx;
+    p_c[r] = hi.c;
   }
   int tap_base[3];  // per-lane byte offset of the fragment of patch column l15 + kx
 #pragma unroll
-  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = (l15 + kx) * 64 + ((c4 ^ lds_swz<true>(l15 + kx)) << 4);
-  const unsigned kOOB = 0x80000000u;
+  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = tap_offset(l15 + kx, c4);
   const unsigned img_in_bytes = (unsigned)H * (unsigned)W * (unsigned)CIN * (unsigned)sizeof(T);
   const unsigned img_out_bytes = (unsigned)H * (unsigned)W * (unsigned)Cout * (unsigned)sizeof(T);
   auto issue_halo = [&](int it, int slot_idx) {
@@ -1025,12 +982,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_kernel(const typename 
         for (int g = 0; g < GPP; ++g)
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            if constexpr (P::ID == NQA_PREC_BF16)
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[i][ks]),
-                                                                  __builtin_bit_cast(bf16x8, bf[ks % (PF + 1)][g]), acc[i][g], 0, 0, 0);
-            else
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[i][ks]),
-                                                                 __builtin_bit_cast(f16x8, bf[ks % (PF + 1)][g]), acc[i][g], 0, 0, 0);
+            acc[i][g] = P::mma16(wf[i][ks], bf[ks % (PF + 1)][g], acc[i][g]);
           }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1114,14 +1066,11 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
   const int HW = H * W;
   const float w1inv = NTERM == 2 ? w1inv_p[0] : 1.f;
 
-  const int nblk = gridDim.x, nx = nblk < 8 ? nblk : 8;
-  const int xcd = blockIdx.x % nx, jb = blockIdx.x / nx;
-  const int blk_per_xcd = (nblk - xcd + nx - 1) / nx;
-  const int t_lo = (int)((long)total_tiles * xcd / nx), t_hi = (int)((long)total_tiles * (xcd + 1) / nx);
-  const int my_tiles = t_lo + jb < t_hi ? (t_hi - t_lo - jb - 1) / blk_per_xcd + 1 : 0;
+  const TileRun run(total_tiles);  // this block's tiles, XCD-aware
+  const int my_tiles = run.count;
   if (my_tiles == 0) return;  // (block-uniform)
-  auto tile_coords = [&](int it, int &n, int &x0, int &y0) {
-    const int t = t_lo + jb + it * blk_per_xcd;
+  auto tile_coords = [&](int it, int &n, int &x0, int &y0) {  // (written out: TileRun::coords changes this kernel's code)
+    const int t = run.first + it * run.stride;
     n = t / (tiles_x * tiles_y);
     const int t2 = t - n * (tiles_x * tiles_y), by = t2 / tiles_x;
     x0 = (t2 - by * tiles_x) * TW;
@@ -1133,8 +1082,7 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int ks = 0; ks < 18; ++ks)
-      wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)cg * 2 + i) * 18 + ks) * 64 + lane) * 16);
+    for (int ks = 0; ks < 18; ++ks) wf[i][ks] = load_wfrag<18>(wreg, cg, i, ks, lane);
   float bia[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -1156,8 +1104,6 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
   // loads: 2 350 us).  The DMA is retired by hand with a counted vmcnt, as everywhere else in this file.
   const int r_row = tid / 36, r_col = tid - r_row * 36;
   const bool r_mine = tid < 12 * 36;
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
   bool r_ok = false;
   auto raw_fetch = [&](int it) {
     r_ok = false;
@@ -1172,7 +1118,7 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
       const float *img = n < B ? x + (size_t)n * 3 * HW : y + (size_t)(n - B) * 3 * HW;
       const __amdgpu_buffer_rsrc_t rsrc =
           __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(img), 0, 3u * (unsigned)HW * 4u, 0x00020000);
-      const unsigned off = r_ok ? (unsigned)((gy * W + gx) * 4) : 0x80000000u;
+      const unsigned off = r_ok ? (unsigned)((gy * W + gx) * 4) : kOOB;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t *)(smem + STG_OFF + c * 2048 + wave * 256), 4, off,
@@ -1192,7 +1138,7 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float raw = *reinterpret_cast<const float *>(smem + STG_OFF + (c * 512 + tid) * 4);
-        v[c] = P::from_f(r_ok ? (raw - mean[c]) / sd[c] : 0.f);
+        v[c] = P::from_f(r_ok ? (raw - kMean[c]) / kStd[c] : 0.f);
       }
       v[3] = P::from_f(0.f);
       *reinterpret_cast<t4 *>(smem + RAW_OFF + buf * RAW_BYTES + (r_row * RAWP + r_col) * 8) = v;
@@ -1238,10 +1184,7 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
 #pragma unroll
           for (int u = 0; u < NU; ++u) {
             if (wave + 8 * u < NGRP) {  // (wave-uniform)
-              if constexpr (P::ID == NQA_PREC_BF16)
-                a1[u][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr), __builtin_bit_cast(bf16x8, bfr[u]), a1[u][i], 0, 0, 0);
-              else
-                a1[u][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wfr), __builtin_bit_cast(f16x8, bfr[u]), a1[u][i], 0, 0, 0);
+              a1[u][i] = P::mma16(wfr, bfr[u], a1[u][i]);
             }
           }
         }
@@ -1265,7 +1208,6 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
     }
   };
 
-  const unsigned kOOB = 0x80000000u;
   const unsigned img_out_bytes = (unsigned)H * (unsigned)W * (unsigned)COUT * (unsigned)sizeof(T);
   // Pipeline per tile k: raw pixels fetched at tile k-2 (start) and committed to raw patch k&1 (end of k-2),
   // conv1_1 -> halo image k&1 at tile k-1, conv1_2 at tile k.  ONE barrier per tile: behind it halo k (written
@@ -1316,12 +1258,7 @@ __global__ __launch_bounds__(512) void conv1_regw_kernel(const float *__restrict
         for (int g = 0; g < GPP; ++g)
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            if constexpr (P::ID == NQA_PREC_BF16)
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[i][ks]),
-                                                                  __builtin_bit_cast(bf16x8, bf[ks % NSET][g]), acc[i][g], 0, 0, 0);
-            else
-              acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[i][ks]),
-                                                                 __builtin_bit_cast(f16x8, bf[ks % NSET][g]), acc[i][g], 0, 0, 0);
+            acc[i][g] = P::mma16(wf[i][ks], bf[ks % NSET][g], acc[i][g]);
           }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1452,27 +1389,17 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
   const int HW = H * W;
   const float w1inv = w1inv_p[0];
 
-  const int nblk = gridDim.x, nx = nblk < 8 ? nblk : 8;
-  const int xcd = blockIdx.x % nx, jb = blockIdx.x / nx;
-  const int blk_per_xcd = (nblk - xcd + nx - 1) / nx;
-  const int t_lo = (int)((long)total_tiles * xcd / nx), t_hi = (int)((long)total_tiles * (xcd + 1) / nx);
-  const int my_tiles = t_lo + jb < t_hi ? (t_hi - t_lo - jb - 1) / blk_per_xcd + 1 : 0;
+  const TileRun run(total_tiles);  // this block's tiles, XCD-aware
+  const int my_tiles = run.count;
   if (my_tiles == 0) return;  // (block-uniform)
-  auto tile_coords = [&](int it, int &n, int &x0, int &y0) {
-    const int t = t_lo + jb + it * blk_per_xcd;
-    n = t / (tiles_x * tiles_y);
-    const int t2 = t - n * (tiles_x * tiles_y), by = t2 / tiles_x;
-    x0 = (t2 - by * tiles_x) * TW;
-    y0 = by * TH;
-  };
+  auto tile_coords = [&](int it, int &n, int &x0, int &y0) { run.coords<TH, TW>(it, tiles_x, tiles_y, n, x0, y0); };
 
   // ---- one-time: conv1_2 (hi, lo) fragments into registers; conv1_1 fragments, bias1 and zeroed raw patches into LDS ----
   u32x4 wf[2][18];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int ks = 0; ks < 18; ++ks)
-      wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)cg * 2 + i) * 18 + ks) * 64 + lane) * 16);
+    for (int ks = 0; ks < 18; ++ks) wf[i][ks] = load_wfrag<18>(wreg, cg, i, ks, lane);
   const float winv2 = bias2[COUT];
 #pragma unroll
   for (int r = 0; r < 2; ++r)  // 8 KB = 512 x 16 B per term
@@ -1487,8 +1414,6 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
   // into a staging area and are normalised a phase later (see conv1_regw_kernel) ----
   const int r_row = tid / 36, r_col = tid - r_row * 36;
   const bool r_mine = tid < 8 * 36;
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
   bool r_ok = false;
   auto raw_fetch = [&](int it) {
     r_ok = false;
@@ -1500,7 +1425,7 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
       const float *img = n < B ? x + (size_t)n * 3 * HW : y + (size_t)(n - B) * 3 * HW;
       const __amdgpu_buffer_rsrc_t rsrc =
           __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(img), 0, 3u * (unsigned)HW * 4u, 0x00020000);
-      const unsigned off = r_ok ? (unsigned)((gy * W + gx) * 4) : 0x80000000u;
+      const unsigned off = r_ok ? (unsigned)((gy * W + gx) * 4) : kOOB;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t *)(smem + STG_OFF + c * (STG_T * 4) + wave * 256), 4,
@@ -1518,7 +1443,7 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float raw = *reinterpret_cast<const float *>(smem + STG_OFF + (c * STG_T + tid) * 4);
-        const float v = r_ok ? (raw - mean[c]) / sd[c] : 0.f;
+        const float v = r_ok ? (raw - kMean[c]) / kStd[c] : 0.f;
         hi[c] = (_Float16)v;
         lo[c] = (_Float16)(v - (float)hi[c]);
       }
@@ -1597,7 +1522,6 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
     }
   };
 
-  const unsigned kOOB = 0x80000000u;
   const unsigned img_out_bytes = (unsigned)H * (unsigned)W * (unsigned)COUT * 4u;
   __syncthreads();  // zeroed patches, conv1_1 fragments and bias are in LDS
   raw_fetch(0);
@@ -1612,55 +1536,12 @@ __global__ __launch_bounds__(512) void conv1_regw_split_kernel(const float *__re
     const char *slot = smem + (it & 1) * SLOT;
     const __amdgpu_buffer_rsrc_t orsrc =
         __builtin_amdgcn_make_buffer_rsrc(out + (size_t)n * H * W * COUT, 0, img_out_bytes, 0x00020000);
-    // BOTH rows of the wave in one k loop (round 4): a step = one halo row hr (0..3 below the wave's first output row) x
-    // one column tap kx x one 32-channel chunk; its four fragments (hi, lo x two 16-column groups) feed output row
-    // r = hr - ky for every kernel row ky that exists -- 6 MFMAs in the first and last halo row, 12 in the middle two.
-    // 24 steps and 96 fragment reads per tile instead of 36 and 144: with four waves of a CU in conv1_2 at once the
-    // row-at-a-time form asked the LDS for 128 clocks of reads per 96 clocks of MFMA.
-    u32x4 bh[2][GPP], bl[2][GPP];
-    auto load_s = [&](const int (&q0)[GPP], int s, u32x4(&h)[GPP], u32x4(&l)[GPP]) {
-      const int cc = s / 12, hr = (s - cc * 12) / 3, kx = s - cc * 12 - hr * 3;
-#pragma unroll
-      for (int g = 0; g < GPP; ++g) {
-        h[g] = *reinterpret_cast<const u32x4 *>(slot + q0[g] + (cc * CH_BYTES + (hr * HWD + kx) * PITCH));
-        l[g] = *reinterpret_cast<const u32x4 *>(slot + q0[g] + (cc * CH_BYTES + (hr * HWD + kx) * PITCH + LO));
-      }
-    };
     int q0[GPP];  // byte offset of this lane's hi fragment at halo row ph * RW, tap kx = 0, chunk 0, per 16-pixel group
 #pragma unroll
     for (int g = 0; g < GPP; ++g) q0[g] = ((ph * RW) * HWD + g * 16 + l15) * PITCH + (c4 << 4);
     asm volatile("" : "+v"(q0[0]), "+v"(q0[1]));
-    // hi*hi | the two cross terms w_lo*a_hi + w_hi*a_lo (2^-11 of the first: one accumulator, they are added in the end
-    // anyway), per group and output row -- 32 registers; a third set spilled
-    f32x4 acc[2][GPP][RW];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int g = 0; g < GPP; ++g)
-#pragma unroll
-        for (int r = 0; r < RW; ++r) acc[i][g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    constexpr int NSTEP = 2 * (RW + 2) * 3;
-    load_s(q0, 0, bh[0], bl[0]);
-#pragma unroll
-    for (int s2 = 0; s2 < NSTEP; ++s2) {
-      if (s2 + 1 < NSTEP) load_s(q0, s2 + 1, bh[(s2 + 1) & 1], bl[(s2 + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      const int cc = s2 / 12, hr = (s2 - cc * 12) / 3, kx = s2 - cc * 12 - hr * 3;
-#pragma unroll
-      for (int r = 0; r < RW; ++r) {
-        const int ky = hr - r;
-        if (ky < 0 || ky > 2) continue;
-        const int ks = cc * 9 + ky * 3 + kx;
-#pragma unroll
-        for (int term = 0; term < 3; ++term)  // (a cross accumulator's two MFMAs are a term apart: never back to back)
-#pragma unroll
-          for (int g = 0; g < GPP; ++g)
-            acc[term ? 1 : 0][g][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                __builtin_bit_cast(f16x8, wf[term == 1 ? 1 : 0][ks]),
-                __builtin_bit_cast(f16x8, term == 2 ? bl[s2 & 1][g] : bh[s2 & 1][g]), acc[term ? 1 : 0][g][r], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    f32x4 acc[2][GPP][RW];  // hi*hi | the two cross terms, per group and output row
+    split3_kloop<RW, GPP, HWD, PITCH, CH_BYTES, LO>(slot, q0, wf, acc);
 #pragma unroll
     for (int r = 0; r < RW; ++r)
 #pragma unroll
@@ -1758,7 +1639,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw_split_kernel(const char *__r
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int ks = 0; ks < 18; ++ks)
-      wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)cgg * 2 + i) * 18 + ks) * 64 + lane) * 16);
+      wf[i][ks] = load_wfrag<18>(wreg, cgg, i, ks, lane);
   const f32x4 bia = *reinterpret_cast<const f32x4 *>(bias + cgg * 16 + 4 * c4);
   const float winv = bias[cout];
 
@@ -1774,7 +1655,6 @@ __global__ __launch_bounds__(512) void conv3x3_regw_split_kernel(const char *__r
     const bool live = j < ITEMS && part < 8;
     plan[r] = live ? ((hy & 15) | (hx << 4) | ((cc * 128 + piece * 16) << 10) | (1 << 19)) : 0;
   }
-  const unsigned kOOB = 0x80000000u;
   const unsigned img_in_bytes = (unsigned)H * (unsigned)W * (unsigned)(CIN * 4);
   const unsigned img_out_bytes = (unsigned)H * (unsigned)W * (unsigned)cout * 4u;
   auto issue_halo = [&](int it, int slot_idx) {
@@ -1815,48 +1695,12 @@ __global__ __launch_bounds__(512) void conv3x3_regw_split_kernel(const char *__r
     const char *slot = smem + (it & 1) * SLOT;
     const __amdgpu_buffer_rsrc_t orsrc =
         __builtin_amdgcn_make_buffer_rsrc(out + (size_t)n * H * W * cout * 4, 0, img_out_bytes, 0x00020000);
-    u32x4 bh[2][GPP], bl[2][GPP];
-    auto load_s = [&](const int (&q0)[GPP], int s, u32x4(&h)[GPP], u32x4(&l)[GPP]) {
-      const int cc = s / 12, hr = (s - cc * 12) / 3, kx = s - cc * 12 - hr * 3;
-#pragma unroll
-      for (int g = 0; g < GPP; ++g) {
-        h[g] = *reinterpret_cast<const u32x4 *>(slot + q0[g] + (cc * CH_BYTES + (hr * HWD + kx) * PITCH));
-        l[g] = *reinterpret_cast<const u32x4 *>(slot + q0[g] + (cc * CH_BYTES + (hr * HWD + kx) * PITCH + LO));
-      }
-    };
     int q0[GPP];
 #pragma unroll
     for (int g = 0; g < GPP; ++g) q0[g] = ((ph * RW) * HWD + g * 16 + l15) * PITCH + (c4 << 4);
     asm volatile("" : "+v"(q0[0]), "+v"(q0[1]));
     f32x4 acc[2][GPP][RW];  // hi*hi | the two cross terms, per group and output row
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int g = 0; g < GPP; ++g)
-#pragma unroll
-        for (int r = 0; r < RW; ++r) acc[i][g][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    constexpr int NSTEP = 2 * (RW + 2) * 3;
-    load_s(q0, 0, bh[0], bl[0]);
-#pragma unroll
-    for (int s2 = 0; s2 < NSTEP; ++s2) {
-      if (s2 + 1 < NSTEP) load_s(q0, s2 + 1, bh[(s2 + 1) & 1], bl[(s2 + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      const int cc = s2 / 12, hr = (s2 - cc * 12) / 3, kx = s2 - cc * 12 - hr * 3;
-#pragma unroll
-      for (int r = 0; r < RW; ++r) {
-        const int ky = hr - r;
-        if (ky < 0 || ky > 2) continue;
-        const int ks = cc * 9 + ky * 3 + kx;
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-          for (int g = 0; g < GPP; ++g)
-            acc[term ? 1 : 0][g][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                __builtin_bit_cast(f16x8, wf[term == 1 ? 1 : 0][ks]),
-                __builtin_bit_cast(f16x8, term == 2 ? bl[s2 & 1][g] : bh[s2 & 1][g]), acc[term ? 1 : 0][g][r], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    split3_kloop<RW, GPP, HWD, PITCH, CH_BYTES, LO>(slot, q0, wf, acc);
     // descale, bias, ReLU; channels c = 16 cgg + 4 c4 .. + 3 of a pixel's split16 record: hi halves at
     // (c >> 4) * 64 + ((c >> 3) & 1) * 16 + (c & 7) * 2, lo halves 32 bytes behind (store_split4)
     const unsigned rec_off = (unsigned)(cgg * 64 + (c4 >> 1) * 16 + (c4 & 1) * 8);
@@ -1959,8 +1803,8 @@ __global__ __launch_bounds__(512) void conv1_fused_kernel(const float *__restric
   };
 
   // ---- P1 pieces: a wave owns column tiles pt = w4 and w4+4 (< 7) of its group's halo patch ----
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
+  // (a local copy of the constants: read from namespace scope they change this kernel's register allocation)
+  const float mean[3] = {kMean[0], kMean[1], kMean[2]}, sd[3] = {kStd[0], kStd[1], kStd[2]};
   int r_plan[7];  // item -> (row << 16 | col << 2 | c) of a 4x36x3 raw sub-patch, -1 = none
 #pragma unroll
   for (int r = 0; r < 7; ++r) {
@@ -2244,8 +2088,6 @@ __global__ __launch_bounds__(256) void conv1_tile_kernel(const float *__restrict
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       w1f[ky][i] = *reinterpret_cast<const u32x4 *>(w1m + ((ky * 64 + i * 32 + l31) * 2 + h) * 16);
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
   int r_plan[7], r_off[7];  // item -> (row << 16 | col << 2 | c) of a 4x36x3 raw sub-patch, -1 = none
 #pragma unroll
   for (int r = 0; r < 7; ++r) {
@@ -2291,7 +2133,7 @@ __global__ __launch_bounds__(256) void conv1_tile_kernel(const float *__restrict
 #pragma unroll
       for (int r = 0; r < 7; ++r) {
         const int row = r_plan[r] >> 16, col = (r_plan[r] >> 2) & 0x3FFF, c = r_plan[r] & 3;
-        const float mu = c == 0 ? mean[0] : c == 1 ? mean[1] : mean[2], sg = c == 0 ? sd[0] : c == 1 ? sd[1] : sd[2];
+        const float mu = c == 0 ? kMean[0] : c == 1 ? kMean[1] : kMean[2], sg = c == 0 ? kStd[0] : c == 1 ? kStd[1] : kStd[2];
         const float v = (okm[u] >> r) & 1u ? (rv[u][r] - mu) / sg : 0.f;
         if (r_plan[r] >= 0) *reinterpret_cast<T *>(raw + (row * F::RAW_W + col) * 8 + c * 2) = P::from_f(v);
       }

@@ -20,17 +20,9 @@
 #include <type_traits>
 
 #include "nqa_common.h"
+#include "nqa_regw.h"
 
 namespace nqa {
-
-typedef __attribute__((address_space(3))) void lds_void_q;
-
-__device__ static inline float dpp1_row_shr1(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xF, 0xF, true));
-}
-__device__ static inline float dpp1_row_shl1(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xF, 0xF, true));
-}
 
 struct S1Geom {
   static constexpr int TH = 4, TW = 32, HWD = TW + 2, NQI = (TH + 2) * HWD;  // 204 halo pixels per image
@@ -85,14 +77,9 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
   const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
   const int strips = (W + 15) >> 4;      // 16-column strips (the seam planes' index)
 
-  // ---- this block's run of units, in [pair][strip pair][row] order (see nqa_conv_pool.hip) ----
-  const int nblk = gridDim.x;
-  int run;
-  {
-    const int qq = nblk >> 3, rr = nblk & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    run = nblk < 8 ? (int)blockIdx.x : (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + local;
-  }
-  const int u_lo = (int)((long)total_units * run / nblk), u_hi = (int)((long)total_units * (run + 1) / nblk);
+  // ---- this block's run of units, in [pair][strip pair][row] order (unit_run, nqa_regw.h) ----
+  int u_lo, u_hi;
+  unit_run(total_units, u_lo, u_hi);
   if (u_lo >= u_hi) return;  // (block-uniform)
   const bool warm0 = (u_lo % rows) != 0;  // the run starts inside a strip: one warm-up unit (the tile above), outputs dropped
   const int nsteps = (u_hi - u_lo) + (warm0 ? 1 : 0);
@@ -132,6 +119,7 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
+        // (load_wfrag<NKS>(wreg, cg, i, ks, lane) of nqa_regw.h, written out: through the helper this kernel's code changes)
         wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)cg * 2 + i) * NKS + ks) * 64 + lane) * 16);
     f32x4 bia[NI];  // the bias is the accumulators' initial value
 #pragma unroll
@@ -214,10 +202,7 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
 
   // ---- raw pixels: 2 images x 8 x 36 per unit; chunk c = round * 4 + wave holds 64 pixels of ONE image (5 chunks per
   // image, 288 of their 320 slots live), so a DMA instruction has one image = one buffer resource ----
-  const float mean[3] = {0.485f, 0.456f, 0.406f};
-  const float sd[3] = {0.229f, 0.224f, 0.225f};
-  const float isd[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
-  const unsigned kOOB = 0x80000000u;
+  const float isd[3] = {1.f / kStd[0], 1.f / kStd[1], 1.f / kStd[2]};
   int r_img[3], r_row[3], r_col[3];
   bool r_live[3], r_ok[3] = {false, false, false};
 #pragma unroll
@@ -242,7 +227,7 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
 #pragma unroll
       for (int c3 = 0; c3 < 3; ++c3)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc, (lds_void_q *)(smem + G::STG_OFF + (c3 * G::STG_SLOTS + (r * 4 + w4) * 64) * 4), 4, off, c3 * HW * 4, 0, 0);
+            rsrc, (lds_void_t *)(smem + G::STG_OFF + (c3 * G::STG_SLOTS + (r * 4 + w4) * 64) * 4), 4, off, c3 * HW * 4, 0, 0);
     }
   };
   auto raw_commit = [&](int buf) {  // staging -> normalised f16 raw patch `buf` (the caller has waited for the DMA)
@@ -254,7 +239,7 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
         for (int c3 = 0; c3 < 3; ++c3) {
           const float raw = *reinterpret_cast<const float *>(smem + G::STG_OFF + (c3 * G::STG_SLOTS + (r * 4 + w4) * 64 + lane) * 4);
           // (x - mean) / std as a multiplication by 1 / std with one residual correction: 4 instructions instead of ~10
-          const float d = raw - mean[c3], q0 = d * isd[c3], q1 = fmaf(fmaf(-q0, sd[c3], d), isd[c3], q0);
+          const float d = raw - kMean[c3], q0 = d * isd[c3], q1 = fmaf(fmaf(-q0, kStd[c3], d), isd[c3], q0);
           v[c3] = (_Float16)(r_ok[r] ? q1 : 0.f);
         }
         v[3] = (_Float16)0.f;
@@ -365,7 +350,7 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
     typedef __attribute__((address_space(3))) const volatile u32x4 lds_cv4;
     u32x4 pc[NI];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) pc[i] = *reinterpret_cast<lds_cv4 *>((lds_void_q *)(xb + buf * G::SLOT + i * 16));
+    for (int i = 0; i < NI; ++i) pc[i] = *reinterpret_cast<lds_cv4 *>((lds_void_t *)(xb + buf * G::SLOT + i * 16));
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -419,8 +404,8 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
           const float m = RAGGED ? v[i][g][e] * vmask : v[i][g][e];
           const float sq = m * m;
           const float u = U[i][g][e] + sq;
-          const float a = u + dpp1_row_shr1(u);
-          const float pv = a + dpp1_row_shl1(a);
+          const float a = u + dpp_row_shr1(u);
+          const float pv = a + dpp_row_shl1(a);
           seamv[g][e] = is15 ? u : pv;
           outh[g][e] = (_Float16)__builtin_amdgcn_sqrtf(fmaf(pv, 0.0625f, 1e-12f));
           U[i][g][e] = sq;

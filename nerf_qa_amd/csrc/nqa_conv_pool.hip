@@ -26,19 +26,9 @@
 // A-DISTS needs the taps themselves and keeps the unfused kernels.
 
 #include "nqa_common.h"
+#include "nqa_regw.h"
 
 namespace nqa {
-
-typedef __attribute__((address_space(3))) void lds_void_p;
-
-__device__ __host__ static inline int swz16(int r) { return ((r >> 2) & 1) * 2; }  // (lds_swz<true> of nqa_conv.hip)
-
-__device__ static inline float dpp_row_shr1(float v) {  // lane l of each 16-lane row reads lane l-1; lane 0 reads 0
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xF, 0xF, true));
-}
-__device__ static inline float dpp_row_shl1(float v) {  // lane l reads lane l+1; lane 15 reads 0
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xF, 0xF, true));
-}
 
 struct PoolGeom {
   static constexpr int CIN = 128, NCC = 4, NKS = NCC * 9, TH = 4, TWI = 16;
@@ -72,15 +62,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
   const int nct = Cout / BC;
   const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
 
-  // ---- this block's run of units: contiguous in [pair][channel tile][strip][row] order; the blocks that share an XCD
-  // (ids equal mod 8) own adjacent runs, i.e. neighbouring strips, whose two shared halo columns then hit one L2 ----
-  const int nblk = gridDim.x;
-  int run;
-  {
-    const int qq = nblk >> 3, rr = nblk & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    run = nblk < 8 ? (int)blockIdx.x : (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + local;
-  }
-  const int u_lo = (int)((long)total_units * run / nblk), u_hi = (int)((long)total_units * (run + 1) / nblk);
+  // ---- this block's run of units: contiguous in [pair][channel tile][strip][row] order (unit_run, nqa_regw.h) ----
+  int u_lo, u_hi;
+  unit_run(total_units, u_lo, u_hi);
   if (u_lo >= u_hi) return;  // (block-uniform)
   // a run that starts inside a strip first recomputes the LAST TWO rows of the tile above (its row 3 is the pool's row
   // -1 of the first real tile): a warm-up step whose outputs and sums are dropped
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < G::NKS; ++ks)
-        wf[i][ks] = *reinterpret_cast<const u32x4 *>(wreg + ((((size_t)g * 2 + i) * G::NKS + ks) * 64 + lane) * 16);
+        wf[i][ks] = load_wfrag<G::NKS>(wreg, g, i, ks, lane);
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -129,12 +113,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
     p_hy[r] = live ? hy : -100000;
     p_hx[r] = col >= G::YCOL ? col - G::YCOL : col;
     p_img[r] = col >= G::YCOL ? pair_off : 0u;
-    p_c[r] = (j & 3) ^ swz16(col);
+    p_c[r] = (j & 3) ^ lds_swz<true>(col);
   }
   int tap_base[3];
 #pragma unroll
-  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = (l15 + kx) * 64 + ((c4 ^ swz16(l15 + kx)) << 4);
-  const unsigned kOOB = 0x80000000u;
+  for (int kx = 0; kx < 3; ++kx) tap_base[kx] = tap_offset(l15 + kx, c4);
   auto issue_halo = [&](int step, int slot_idx) {
     char *slot = smem + slot_idx * G::SLOT;
     const bool real = step < nsteps;
@@ -150,7 +133,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
       const unsigned off = ok ? p_img[r] + (unsigned)(((gy * W + gx) * G::CIN + p_c[r] * 8) * 2) : kOOB;
 #pragma unroll
       for (int cc = 0; cc < G::NCC; ++cc)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_p *)(slot + cc * G::CH_BYTES + r * 4096 + wave * 1024), 16,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t *)(slot + cc * G::CH_BYTES + r * 4096 + wave * 1024), 16,
                                                  off, cc * 64, 0, 0);
       if (real && !ok && p_hy[r] >= 0) {
         const u32x4 z = {0u, 0u, 0u, 0u};

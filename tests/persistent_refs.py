@@ -5,7 +5,7 @@ everything here.
 
 (a) A schedule model: the host grid rules (launch_regw, launch_regw128 with its `grid -= 8` trimming, launch_regw_split
     with its streams, launch_conv1_regw / launch_conv1_regw_split, launch_conv_pool) and the kernels' own tile split
-    (t_lo, t_hi, blk_per_xcd, my_tiles; the pool kernel's contiguous runs), restated in integer arithmetic.  It only
+    (TileRun and unit_run of csrc/nqa_regw.h; conv3x3_regw_split_kernel's streams), restated in integer arithmetic.  It only
     chooses batch sizes, proves that a case reaches its regime and names the block and step behind a failing pixel.  It
     is never a reference for values.
 (b) Exact-integer operands as in tests/test_gpu_conv_igemm_addr.py: activations in {0, 1, 2}, weights in {-1, 0, 1}, a

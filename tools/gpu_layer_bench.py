@@ -35,6 +35,7 @@ def time_layer(a, layer, reps):
 a = (torch.rand(N, dims[2][0], dims[2][1], 256, device=dev) - 0.5).clamp_min(0).to(DT)
 time_layer(a, 5, 300 if which == "256" else 40)
 res = {v: [] for v in VARIANTS}
+ms = {v: [] for v in VARIANTS}
 tot = {v: [0.0, 0.0] for v in VARIANTS}
 for layer in range(1, 13):
     h, w = dims[ops.CONV_STAGE[layer]]
@@ -53,7 +54,9 @@ for layer in range(1, 13):
             best[v] = min(best[v], time_layer(a, layer, 10 if which == "256" else 3))
     for v in VARIANTS:
         res[v].append(f"L{layer}:{fl / best[v] / 1e9:.0f}")
+        ms[v].append(f"L{layer}:{best[v]:.4f}")
         tot[v][0] += best[v]
         tot[v][1] += fl
 for v in VARIANTS:
     print(f"variant {v} {which}: total {tot[v][0]:.3f} ms, {tot[v][1] / tot[v][0] / 1e9:.0f} TF | " + " ".join(res[v]), flush=True)
+    print(f"variant {v} {which}: best ms per layer | " + " ".join(ms[v]), flush=True)
