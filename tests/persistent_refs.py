@@ -24,6 +24,7 @@ CU_COUNTS = (8, 64, 104, 256, 304)
 H, W = 37, 70                 # ragged under the 8 x 32 and the 4 x 32 tile, and under the pool kernel's 4 x 16 unit
 S1_H, S1_W = 150, 130         # stage-1 frames
 INT_LAYERS = (1, 2, 3, 4)
+IGEMM_INT_LAYERS = (7, 8)     # conv4_1, conv4_2: the same construction, for tests/test_gpu_conv_float_exact.py
 SPARSE_LAYER = 3
 SPARSE_TERMS = 31
 PART_BLOCKS = 256             # NQA_FUSED_PART_BLOCKS: the fused kernel's grid never exceeds its partial rows
@@ -202,10 +203,10 @@ def pool_owner(img_pair: int, ct: int, sx: int, ty: int, b_pairs: int, h: int, w
 # ---- (b), (c) integer operands --------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def int_convs():
-    """The synthetic VGG weights with layers 1..4 in {-1, 0, 1} and a bias in {-3 .. 3}."""
+    """The synthetic VGG weights with layers 1..4 (and conv4_1, conv4_2) in {-1, 0, 1} and a bias in {-3 .. 3}."""
     from nerf_qa_amd import ops, synth
     convs = list(synth.vgg16_weights(1234))
-    for layer in INT_LAYERS:
+    for layer in INT_LAYERS + IGEMM_INT_LAYERS:
         cout, cin = ops.CONV_COUT[layer], ops.CONV_CIN[layer]
         w = np.floor(synth.uniform(900 + layer, cout * cin * 9) * 3.0).clip(0, 2).astype(np.float32) - 1.0
         b = np.floor(synth.uniform(950 + layer, cout) * 7.0).clip(0, 6).astype(np.float32) - 3.0

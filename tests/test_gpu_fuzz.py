@@ -108,7 +108,11 @@ OP_CASES = [(int(l), int(n), int(h), int(w)) for l, n, h, w in zip(
 @pytest.mark.parametrize("prec", ["f16", "bf16", "f32", "f32s"])
 @pytest.mark.parametrize("layer,n,h,w", OP_CASES, ids=[f"L{c[0]}-{c[1]}x{c[2]}x{c[3]}" for c in OP_CASES])
 def test_random_conv_layer(layer, n, h, w, prec, np_convs):
-    """One conv layer at a random ragged size (every tile variant: 16- and 32-wide, 4- and 8-wave) vs F.conv2d."""
+    """One conv layer at a random ragged size vs F.conv2d: the 16- and 32-wide forms of the 64-channel and the 4-wave
+    tile, the register-weights kernels and, under conv variant 2, the 8-wave 128 ch x 512 px tile.  The 8-wave 256 x 256
+    tile is NOT reached: launch_conv asks for `blocks_big >= 192`, and n <= 3 at up to 40 x 70 gives at most 90.  It is
+    held bit for bit by tests/test_gpu_conv_igemm_addr.py (f16, f16w), tests/test_gpu_conv_float_exact.py (f32, bf16) and
+    tests/test_gpu_conv_split_exact.py (f32s), whose batches of 20 open that gate."""
     import torch.nn.functional as F
     from nerf_qa_amd import ops, synth
     dev = torch.device("cuda:0")
