@@ -293,6 +293,52 @@ int nqa_adists_dists_forward(const float *x_nchw, const float *y_nchw, int B, in
                              int prec, void *workspace, size_t workspace_bytes, float *d, float *s1, float *s2,
                              float *map, void *stream);
 
+/* A-DISTS of K renders against ONE reference, for R such groups (ADISTS.forward, ADISTS.py:137-197, for the R * K pairs;
+ * the reference's scoring loops pass x = ref, prep.py:186, and its tables hold several rows per reference_folder,
+ * test2_prep.py:89,201,304,404).  A-DISTS is asymmetric: the texture-probability chain (compute_prob, ADISTS.py:71-100),
+ * the entropy channel weights (:127-135,150-161) and gamma come from x alone, so here they are computed once per
+ * reference, not once per render, and the reference frames go through the pyramid once per group -- R + R * K images
+ * where nqa_adists_forward runs 2 * R * K.
+ *   ref      dev float32 NCHW (R,3,H,W); renders  dev float32 NCHW (R,K,3,H,W) contiguous, render k of group r at r * K + k
+ *            (the layout and pair index p = r * K + k of nqa_dists_forward_group).
+ *   d        dev float32 (R * K): what nqa_adists_forward writes for (ref[r], renders[r][k]) in `prec`, up to the order
+ *            of the fp64 partial sums of the statistics (the group statistics kernels split the pixels into other blocks)
+ *            and of the entropy sums.
+ *   s1, s2   both null, or both dev float32 (R * K, 1475): what nqa_adists_dists_forward writes, by the same
+ *            finalisation launch on the same partial sums.
+ * Inside, one NHWC batch of n = R + R * K images: the references first, render (r, k) at image R + r * K + k, all five
+ * taps kept.  The statistics are nqa_group_stats.hip's kernels and the L2-pools run as launches of their own, as in
+ * nqa_dists_forward_group; the NHWC4 conversion, the six entropy passes, their fold and the weights kernel run on the R
+ * references; the window pass runs per pair in the group instances of its kernels (pair p reads x and the channel
+ * weights of reference p / K, writes tw / sw of its own, and the k = 0 pair writes the reference's gamma; a pair's
+ * arithmetic is the pairwise kernel's); the probability chain runs per reference, and chain_final_group_kernel takes
+ * the K renders' sums against each reference's ps_prod.  No atomics on any sum: bitwise repeatable.
+ * Every `prec` nqa_adists_forward takes; the mixed modes are refused as there.  There is no as_map form.
+ * Workspace: nqa_adists_group_workspace_bytes (0 for arguments the forward refuses).
+ * Refused on the host, before any launch: NQA_E_ARG null pointer (s1 / s2 excepted), only one of s1 / s2 given,
+ * non-positive size, more than 65535 pairs in one call (slice over R), unknown or mixed prec, a frame of H * W * 64
+ * elements reaching 2^31 bytes (nqa_adists_forward's limit); NQA_E_WORKSPACE a short workspace. */
+size_t nqa_adists_group_workspace_bytes(int R, int K, int H, int W, int prec);
+int nqa_adists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W,
+                             const void *packed_w, int prec, void *workspace, size_t workspace_bytes,
+                             float *d, float *s1, float *s2, void *stream);
+
+/* The window pass and the back part of nqa_adists_forward_group on their own, for tests and tools, through the launch
+ * functions the group forward uses.
+ *   nqa_adists_window_stage_group   nqa_adists_window_stage for R * K pairs: fx the R references' maps, fy the R * K
+ *           renders' (pair r * K + k), q [8][R*K][C] per pair, wgt [R][C] per reference; gamma (R, H-20, W-20) per
+ *           reference, tw / sw (R*K, H-20, W-20) per pair (the global branch: R and R * K values).  Dispatch, strip and
+ *           refusals as nqa_adists_window_stage, with R <= 0, K <= 0 or more than 65535 pairs NQA_E_ARG.
+ *   nqa_adists_chain_group          nqa_adists_chain for R * K pairs: gamma[k] and ps_prod[k] (R, mh[k], mw[k]), tw[k] and
+ *           sw[k] (R*K, mh[k], mw[k]), d (R*K).  No map.  Workspace nqa_adists_chain_group_bytes(R, K, H, W) (0 for
+ *           sizes it refuses); refusals as nqa_adists_chain plus the group's. */
+int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
+                                  const float *q, const float *wgt, int strip, float *gamma, float *tw, float *sw,
+                                  void *stream);
+size_t nqa_adists_chain_group_bytes(int R, int K, int H, int W);
+int nqa_adists_chain_group(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K, int H,
+                           int W, void *workspace, size_t workspace_bytes, float *const *ps_prod, float *d, void *stream);
+
 /* ONE stage of nqa_adists_forward's heavy pass on its own, for tests and tools: the launch that turns a tap pair into
  * the stage's three channel-reduced maps, exactly as nqa_adists_forward enqueues it (the same launch functions, with the
  * stage's channels as the whole channel vector: ctot = C, offset 0).  No workspace.

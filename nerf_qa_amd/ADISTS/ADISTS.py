@@ -199,6 +199,36 @@ class ADISTS(torch.nn.Module):
             return 1 - d.mean()
         return 1 - d
 
+    def _group_checks(self, ref, renders, who="forward_group"):
+        """The argument checks of forward_group (pair.score_group shares them); returns (R, K, H, W)."""
+        from .._lib import NqaError
+        if not (torch.is_tensor(ref) and torch.is_tensor(renders)) or ref.dim() != 4 or renders.dim() != 5 \
+                or ref.shape[1] != 3 or renders.shape[0] != ref.shape[0] or renders.shape[2:] != ref.shape[1:] \
+                or ref.numel() == 0 or renders.numel() == 0:
+            raise ValueError(f"{who} expects references (R,3,H,W) and renders (R,K,3,H,W), got "
+                             f"{tuple(getattr(ref, 'shape', ()))} / {tuple(getattr(renders, 'shape', ()))}")
+        if torch.is_grad_enabled() and (ref.requires_grad or renders.requires_grad):
+            raise ValueError(f"{who} does not differentiate through the shared pyramid: detach the images, or call "
+                             "forward(x, y, as_loss=True) per pair")
+        if not (ref.is_cuda and renders.is_cuda):
+            raise NqaError("nerf_qa_amd runs on the GPU only: got tensors on %s / %s (move inputs and the module to cuda; "
+                           "there is no CPU fallback)" % (ref.device, renders.device))
+        return int(ref.shape[0]), int(renders.shape[1]), int(ref.shape[2]), int(ref.shape[3])
+
+    def forward_group(self, ref, renders, as_loss=False):
+        """A-DISTS of K renders against ONE reference, for R such groups: ref (R,3,H,W), renders (R,K,3,H,W) -> (R,K) of
+        1 - D, entry [r, k] = forward(ref[r:r+1], renders[r, k:k+1], as_loss=False), or the scalar 1 - mean(D) with
+        as_loss=True (the reference's tables hold several rows per reference_folder, test2_prep.py:89,201,304,404, and
+        prep.py:186 passes x = ref).  Everything A-DISTS takes from x alone -- the reference's pyramid, its entropy
+        weights and its texture-probability chain -- runs once per reference instead of once per render.  Precision:
+        precision_for(H, W), as in forward.  The images receive no gradient: ValueError for images that require grad
+        (use forward(as_loss=True) per pair) and for shapes that do not fit, NqaError for tensors off the GPU."""
+        r, k, h, w = self._group_checks(ref, renders)
+        prec = self.precision_for(h, w)
+        with torch.no_grad():
+            d = ops.adists_forward_group(ref, renders, self._packed_weights(ref.device, prec), prec, self._ws)
+        return 1 - d.mean() if as_loss else (1 - d).reshape(r, k)
+
 
 def prepare_image(image, resize=True):
     """PIL image -> float32 (1,3,H,W) in [0,1]; ADISTS.py:200-204 (short side to 256, aspect ratio kept)."""

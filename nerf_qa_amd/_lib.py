@@ -73,6 +73,12 @@ _SIGNATURES = {
     "nqa_adists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp]),
     "nqa_adists_forward_map": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
     "nqa_adists_dists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "nqa_adists_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_adists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "nqa_adists_window_stage_group": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "nqa_adists_chain_group_bytes": (_sz, [_i, _i, _i, _i]),
+    "nqa_adists_chain_group": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz,
+                                    C.POINTER(_vp), _vp, _vp]),
     "nqa_adists_window_stage": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "nqa_adists_window_grid": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "nqa_adists_chain_dims": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -73,6 +73,40 @@ __global__ __launch_bounds__(256) void adists_prep_kernel(const double *__restri
   q[7 * st + o] = (float)(s[4] * inv - mx * my);
 }
 
+// The same scalars for the group forward, one WAVE per (pair, channel): the group statistics kernels cut a tap into
+// strips that fit a block's registers (up to 8100 blocks per pair for relu1_2 at 1080p, where the pairwise passes leave
+// at most ~1000), and one thread walking them alone took 2.8 ms of a 21 ms call.
+// The lanes stride over the blocks and a shuffle tree adds them, the order of plane_moments / finalize_kernel.
+__global__ __launch_bounds__(256) void adists_prep_group_kernel(const double *__restrict__ part, StageDesc d,
+                                                                float *__restrict__ q /* [8][B][ctot] */, int B) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int gc = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (gc >= d.ctot) return;
+  int k = 0;
+  while (k + 1 < d.nstage && gc >= d.coff[k + 1]) ++k;
+  const int c = gc - d.coff[k];
+  const double *p = part + d.part_off[k] + ((size_t)b * d.nblk[k] * d.c[k] + c) * 5;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int blk = lane; blk < d.nblk[k]; blk += 64)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) s[j] += p[(size_t)blk * d.c[k] * 5 + j];
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_down(s[j], off, 64);
+  if (lane != 0) return;
+  const double inv = 1.0 / (double)d.hw[k];
+  const double mx = s[0] * inv, my = s[1] * inv;
+  const size_t o = (size_t)b * d.ctot + gc, st = (size_t)B * d.ctot;
+  q[0 * st + o] = (float)(1.0 / fmax(sqrt(s[2]), 1e-12));
+  q[1 * st + o] = (float)(1.0 / fmax(sqrt(s[3]), 1e-12));
+  q[2 * st + o] = (float)s[0];
+  q[3 * st + o] = (float)mx;
+  q[4 * st + o] = (float)my;
+  q[5 * st + o] = (float)(s[2] * inv - mx * mx);
+  q[6 * st + o] = (float)(s[3] * inv - my * my);
+  q[7 * st + o] = (float)(s[4] * inv - mx * my);
+}
+
 // ---------------------------------------------------------------------------------
 // Spatial entropy of the x maps (ADISTS.py:127-133): p = relu(f)*inv; p /= sum(p)+c0;
 // H = -sum p log2(p + c0).  Partial sums per block, part[(b*nblk+blk)*C + c].
@@ -264,111 +298,28 @@ __device__ inline void wave_sum3(float &a, float &b, float &c) {
 #endif
 }
 
+// The GROUP forms of the three window kernels and of the global branch (nqa_adists_forward_group): K renders per
+// reference, pair b = r * K + k.  Pair b reads its x maps from reference image xi = b / K and its channel weights from
+// row xi, its y maps and its q rows from pair b; tw / sw are written per pair, gamma -- a function of x alone -- once per
+// reference, by the k = 0 pair, at image xi.  The pairwise kernels are the same bodies with xi = b, every pair writing
+// its gamma.  The arithmetic of a pair is the same in both.
 template <typename P, int C>  // C (64..512) is a template parameter so tap strides fold into load immediates
 __global__ __launch_bounds__(256, 2) void adists_window_lanes_kernel(
     const typename P::T *__restrict__ fx, const typename P::T *__restrict__ fy, int H, int W,
     const float *__restrict__ q, int B, int ctot, int coff, const float *__restrict__ wgt, Gauss gw,
     float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw) {
-  typedef typename P::T T;
-  // the wave index as a provably uniform value, so the row pointers and loop bounds stay scalar
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.z;
-  const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
-  const int ox = blockIdx.x * 4 + wave;  // 4 adjacent columns per block: their neighbour loads overlap in L1
-  if (ox >= Wo) return;
-  const int oy0 = blockIdx.y * 64;
-  const int nout = min(64, Ho - oy0);
-  const int nrows = nout + kWin - 1;
-  const size_t st = (size_t)B * ctot, qo = (size_t)b * ctot + coff;
-  float acc_g = 0.f, acc_t = 0.f, acc_s = 0.f;  // lane l: output row oy0 + l
-  for (int cb = 0; cb < C; cb += 64) {
-    const int c = cb + lane;
-    const float ix = q[0 * st + qo + c], iy = q[1 * st + qo + c], wc = wgt[qo + c];
-    const T *px = fx + ((size_t)(b * H + oy0) * W + ox) * C + cb;  // wave-uniform; the lane is added per load
-    const T *py = fy + ((size_t)(b * H + oy0) * W + ox) * C + cb;
-    // ring of the last 21 rows' horizontal sums, slot = grp*7 + sub (a dynamically indexed ring -- a switch
-    // over 21 slots -- makes hipcc shuttle all of it through AGPRs every row, so the row loop is unrolled).
-    // The five running sums travel as two float pairs + one float so that the 2 x 21 taps per
-    // (pixel, channel) are packed v_pk_fma_f32 / v_pk_mul_f32: 4 + 3 instructions per tap pair.
-    f32x2 r01[3][7], r23[3][7];
-    float r4[3][7];
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-      for (int u = 0; u < 7; ++u) {
-        r01[g][u] = r23[g][u] = (f32x2){0.f, 0.f};
-        r4[g][u] = 0.f;
-      }
-    // 21 rows per trip, fully unrolled: the ring slot (grp*7 + sub) of every row body is a compile-time
-    // constant, so a row's sums drop into their slot without selects and the vertical tap weights are
-    // immediates of the kernel-argument window (no table loads)
-    for (int rr0 = 0; rr0 < nrows; rr0 += 21) {
-#pragma unroll
-      for (int grp = 0; grp < 3; ++grp)
-#pragma unroll
-      for (int sub = 0; sub < 7; ++sub) {
-        const int rr = rr0 + grp * 7 + sub;
-        if (rr < nrows) {
-          // all 42 loads go out back to back before any arithmetic (left to itself hipcc pairs each
-          // load with its use and pays the memory latency 21 times per row)
-          T xr[kWin], yr[kWin];
-#pragma unroll
-          for (int j = 0; j < kWin; ++j) {
-            xr[j] = px[(size_t)j * C + lane];
-            yr[j] = py[(size_t)j * C + lane];
-          }
-          px += (size_t)W * C;
-          py += (size_t)W * C;
-          __builtin_amdgcn_sched_barrier(0);
-          f32x2 h01 = {0.f, 0.f}, h23 = {0.f, 0.f};
-          float h4 = 0.f;
-#pragma unroll
-          for (int j = 0; j < kWin; ++j) {
-            const f32x2 v = {P::to_f(xr[j]), P::to_f(yr[j])};
-            const f32x2 gv = gw.g[j] * v;
-            h01 += gv;
-            h23 = gv * v + h23;
-            h4 = fmaf(gv[0], v[1], h4);
-          }
-          r01[grp][sub] = h01;
-          r23[grp][sub] = h23;
-          r4[grp][sub] = h4;
-          if (rr >= kWin - 1) {
-            f32x2 m01 = {0.f, 0.f}, m23 = {0.f, 0.f};
-            float m4 = 0.f;
-#pragma unroll
-            for (int g = 0; g < 3; ++g)
-#pragma unroll
-              for (int u = 0; u < 7; ++u) {
-                const float wv = gw.g[(kWin - 1 - (grp * 7 + sub) + g * 7 + u) % kWin];  // slot (g,u) at this phase
-                m01 = wv * r01[g][u] + m01;
-                m23 = wv * r23[g][u] + m23;
-                m4 = fmaf(wv, r4[g][u], m4);
-              }
-            const float m0 = m01[0], m1 = m01[1], m2 = m23[0], m3 = m23[1];
-            const float gterm = div_nr(m2 - m0 * m0, m0 + 1e-12f);
-            const float mx = ix * m0, my = iy * m1;
-            const float vx = ix * ix * m2 - mx * mx, vy = iy * iy * m3 - my * my;
-            const float cov = ix * iy * m4 - mx * my;
-            const float tt = wc * div_nr(2.f * mx * my + 1e-6f, mx * mx + my * my + 1e-6f);
-            const float ss = wc * div_nr(2.f * cov + 1e-6f, vx + vy + 1e-6f);
-            const float gs = wave_sum(gterm), ts = wave_sum(tt), sss = wave_sum(ss);
-            if (lane == rr - (kWin - 1)) {
-              acc_g += gs;
-              acc_t += ts;
-              acc_s += sss;
-            }
-          }
-        }
-      }
-    }
-  }
-  if (lane < nout) {
-    const size_t o = ((size_t)b * Ho + oy0 + lane) * Wo + ox;
-    gamma[o] = acc_g / (float)C;
-    tw[o] = acc_t;
-    sw[o] = acc_s;
-  }
+#define NQA_LANES_GROUP 0
+#include "nqa_window_lanes_body.h"
+#undef NQA_LANES_GROUP
+}
+template <typename P, int C>
+__global__ __launch_bounds__(256, 2) void adists_window_lanes_group_kernel(
+    const typename P::T *__restrict__ fx, const typename P::T *__restrict__ fy, int H, int W,
+    const float *__restrict__ q, int B, int ctot, int coff, const float *__restrict__ wgt, Gauss gw,
+    float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw, int K) {
+#define NQA_LANES_GROUP 1
+#include "nqa_window_lanes_body.h"
+#undef NQA_LANES_GROUP
 }
 
 // gaussian(21, 7) as ADISTS.py:102-104 builds it (float32(exp(.)) / float32 sum), as compile-time constants:
@@ -461,11 +412,11 @@ __device__ inline void win_row(const float (&x)[kWin], const float (&y)[kWin], W
 // The arithmetic (horizontal sums, 21-row register ring, vertical sums, T / S / gamma, channel reduction) is
 // the kernel above, instruction for instruction.
 
-template <typename P, int C>
-__global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
+template <typename P, int C, bool GRP>  // (GRP: the group form, see adists_window_lanes_kernel)
+__device__ __forceinline__ void window_lds_body(
     const typename P::T *__restrict__ fx, const typename P::T *__restrict__ fy, int H, int W,
     const float *__restrict__ q, int B, int ctot, int coff, const float *__restrict__ wgt, Gauss gw,
-    float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw, int nbx, int nby, int strip) {
+    float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw, int nbx, int nby, int strip, int K) {
 #if defined(__HIP_DEVICE_COMPILE__)
   (void)gw;  // the taps are the compile-time constants kG (checked against make_gauss() on the host)
   typedef typename P::T T;
@@ -486,6 +437,8 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
     id = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + local;
   }
   const int bx = id % nbx, by = (id / nbx) % nby, b = id / (nbx * nby);
+  const int xi = GRP ? b / K : b;
+  const bool lead = !GRP || b - xi * K == 0;
   const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
   const int ox0 = bx * 4, ox = ox0 + wave;
   const bool live_col = ox < Wo;            // a dead column computes on clamped pixels and stores nothing
@@ -497,7 +450,7 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
   const size_t st = (size_t)B * ctot, qo = (size_t)b * ctot + coff;
   const unsigned img_bytes = (unsigned)H * (unsigned)W * (unsigned)C * (unsigned)SZ;
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T *>(fx + (size_t)b * H * W * C), 0, img_bytes, 0x00020000);
+      const_cast<T *>(fx + (size_t)xi * H * W * C), 0, img_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<T *>(fy + (size_t)b * H * W * C), 0, img_bytes, 0x00020000);
   // this wave's DMA pieces: piece p = i*4 + wave covers pixels [pidx*PPP, +PPP) of image p / PPI
@@ -525,13 +478,14 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
       const int r = (orow & ~63) + lane;
       if (live_col && r <= orow) {
         const size_t o = ((size_t)b * Ho + oy0 + r) * Wo + ox;
+        const size_t og = GRP ? ((size_t)xi * Ho + oy0 + r) * Wo + ox : o;
         float fg = acc_g, ft = acc_t, fs = acc_s;
         if (cb > 0) {
-          fg += gamma[o];
+          if (lead) fg += gamma[og];
           ft += tw[o];
           fs += sw[o];
         }
-        gamma[o] = cb + 64 >= C ? fg / (float)C : fg;
+        if (lead) gamma[og] = cb + 64 >= C ? fg / (float)C : fg;
         tw[o] = ft;
         sw[o] = fs;
       }
@@ -542,7 +496,7 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
     float *const chan = reinterpret_cast<float *>(smem_w + R * ROWB) + wave * 192 + lane;
     chan[0] = q[0 * st + qo + c];
     chan[64] = q[1 * st + qo + c];
-    chan[128] = wgt[qo + c];
+    chan[128] = wgt[(size_t)xi * ctot + coff + c];
     auto issue_row = [&](int r) {
       char *slot = smem_w + (r % R) * ROWB;
 #pragma unroll
@@ -603,18 +557,36 @@ __global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
 #endif
 }
 
+template <typename P, int C>
+__global__ __launch_bounds__(256, 3) void adists_window_lds_kernel(
+    const typename P::T *__restrict__ fx, const typename P::T *__restrict__ fy, int H, int W,
+    const float *__restrict__ q, int B, int ctot, int coff, const float *__restrict__ wgt, Gauss gw,
+    float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw, int nbx, int nby, int strip) {
+  window_lds_body<P, C, false>(fx, fy, H, W, q, B, ctot, coff, wgt, gw, gamma, tw, sw, nbx, nby, strip, 1);
+}
+template <typename P, int C>
+__global__ __launch_bounds__(256, 3) void adists_window_lds_group_kernel(
+    const typename P::T *__restrict__ fx, const typename P::T *__restrict__ fy, int H, int W,
+    const float *__restrict__ q, int B, int ctot, int coff, const float *__restrict__ wgt, Gauss gw,
+    float *__restrict__ gamma, float *__restrict__ tw, float *__restrict__ sw, int nbx, int nby, int strip, int K) {
+  window_lds_body<P, C, true>(fx, fy, H, W, q, B, ctot, coff, wgt, gw, gamma, tw, sw, nbx, nby, strip, K);
+}
+
 // The windowed pass of stage 0 (the raw image: 3 float planes, NCHW) in the same shape as the lanes
 // kernel above, with lanes = 64 adjacent output COLUMNS of one plane: every tap load is a coalesced
 // row segment at an immediate offset from one row pointer, the ring and the packed tap arithmetic
 // are identical, nothing is reduced across lanes, and the three channels are accumulated into the
 // maps one after the other by the same lane (plain read-modify-write, no atomics).
-__global__ __launch_bounds__(256, 2) void adists_window_planar_kernel(
+template <bool GRP>  // (GRP: the group form, see adists_window_lanes_kernel)
+__device__ __forceinline__ void window_planar_body(
     const float *__restrict__ x, const float *__restrict__ y, int H, int W, const float *__restrict__ q, int B,
     int ctot, int coff, const float *__restrict__ wgt, Gauss gw, float *__restrict__ gamma, float *__restrict__ tw,
-    float *__restrict__ sw) {
+    float *__restrict__ sw, int K) {
   (void)gw;  // taps = the compile-time constants kG
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.z;
+  const int xi = GRP ? b / K : b;
+  const bool lead = !GRP || b - xi * K == 0;
   const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
   const int ox0 = blockIdx.x * 256 + wave * 64;
   if (ox0 >= Wo) return;
@@ -626,9 +598,12 @@ __global__ __launch_bounds__(256, 2) void adists_window_planar_kernel(
   const int nrows = nout + kWin - 1;
   const size_t st = (size_t)B * ctot, qo = (size_t)b * ctot + coff;
   const size_t o0 = ((size_t)b * Ho + oy0) * Wo + ox;
+  // the group form reaches gamma through a column pointer of its own (reference xi's map); with the pairwise form's
+  // `gamma[o]` it needs 185 VGPRs, with this one 168: three waves per SIMD like the pairwise kernel, and no scratch
+  float *const gq = gamma + ((size_t)xi * Ho + oy0) * Wo + ox;
   for (int c = 0; c < 3; ++c) {
-    const float ix = q[0 * st + qo + c], iy = q[1 * st + qo + c], wc = wgt[qo + c];
-    const float *px = x + ((size_t)(b * 3 + c) * H + oy0) * W + oxc;
+    const float ix = q[0 * st + qo + c], iy = q[1 * st + qo + c], wc = wgt[(size_t)xi * ctot + coff + c];
+    const float *px = x + ((size_t)(xi * 3 + c) * H + oy0) * W + oxc;
     const float *py = y + ((size_t)(b * 3 + c) * H + oy0) * W + oxc;
     WinRing rg;
 #pragma unroll
@@ -649,13 +624,22 @@ __global__ __launch_bounds__(256, 2) void adists_window_planar_kernel(
       win_row<SLOT>(xr, yr, rg, full, ix, iy, wc, gterm, tt, ss);                     \
       if (full && live) {                                                             \
         const size_t o = o0 + (size_t)(rr - (kWin - 1)) * Wo;                         \
+        if constexpr (GRP) {                                                          \
+          if (lead) {                                                                 \
+            float *const gp = gq + (size_t)(rr - (kWin - 1)) * Wo;                    \
+            const float gsum = c == 0 ? gterm : *gp + gterm;                          \
+            *gp = c == 2 ? gsum / 3.f : gsum;                                         \
+          }                                                                           \
+        }                                                                             \
         if (c == 0) {                                                                 \
-          gamma[o] = gterm;                                                           \
+          if constexpr (!GRP) gamma[o] = gterm;                                       \
           tw[o] = tt;                                                                 \
           sw[o] = ss;                                                                 \
         } else {                                                                      \
-          const float gsum = gamma[o] + gterm;                                        \
-          gamma[o] = c == 2 ? gsum / 3.f : gsum;                                      \
+          if constexpr (!GRP) {                                                       \
+            const float gsum = gamma[o] + gterm;                                      \
+            gamma[o] = c == 2 ? gsum / 3.f : gsum;                                    \
+          }                                                                           \
           tw[o] += tt;                                                                \
           sw[o] += ss;                                                                \
         }                                                                             \
@@ -672,18 +656,33 @@ __global__ __launch_bounds__(256, 2) void adists_window_planar_kernel(
   }
 }
 
+__global__ __launch_bounds__(256, 2) void adists_window_planar_kernel(
+    const float *__restrict__ x, const float *__restrict__ y, int H, int W, const float *__restrict__ q, int B,
+    int ctot, int coff, const float *__restrict__ wgt, Gauss gw, float *__restrict__ gamma, float *__restrict__ tw,
+    float *__restrict__ sw) {
+  window_planar_body<false>(x, y, H, W, q, B, ctot, coff, wgt, gw, gamma, tw, sw, 1);
+}
+__global__ __launch_bounds__(256, 3) void adists_window_planar_group_kernel(
+    const float *__restrict__ x, const float *__restrict__ y, int H, int W, const float *__restrict__ q, int B,
+    int ctot, int coff, const float *__restrict__ wgt, Gauss gw, float *__restrict__ gamma, float *__restrict__ tw,
+    float *__restrict__ sw, int K) {
+  window_planar_body<true>(x, y, H, W, q, B, ctot, coff, wgt, gw, gamma, tw, sw, K);
+}
+
 // Global branch of one stage (maps smaller than the window; ADISTS.py:91-97,176-180): one
 // block per image pair, from the per-channel global statistics.  Outputs 1x1 "maps".
-__global__ __launch_bounds__(256) void adists_global_kernel(const float *__restrict__ q, int B, int ctot, int coff,
-                                                            int creal, const float *__restrict__ wgt,
-                                                            float *__restrict__ gamma, float *__restrict__ tw,
-                                                            float *__restrict__ sw) {
+template <bool GRP>  // (GRP: the group form, see adists_window_lanes_kernel)
+__device__ __forceinline__ void global_body(const float *__restrict__ q, int B, int ctot, int coff, int creal,
+                                            const float *__restrict__ wgt, float *__restrict__ gamma,
+                                            float *__restrict__ tw, float *__restrict__ sw, int K) {
   __shared__ double red[3][256];
   const int b = blockIdx.x, tid = threadIdx.x;
+  const int xi = GRP ? b / K : b;
+  const bool lead = !GRP || b - xi * K == 0;
   const size_t st = (size_t)B * ctot, qo = (size_t)b * ctot + coff;
   double g = 0, t = 0, s = 0;
   for (int c = tid; c < creal; c += 256) {
-    const float ix = q[0 * st + qo + c], iy = q[1 * st + qo + c], w = wgt[qo + c];
+    const float ix = q[0 * st + qo + c], iy = q[1 * st + qo + c], w = wgt[(size_t)xi * ctot + coff + c];
     const float rmx = q[3 * st + qo + c], rmy = q[4 * st + qo + c];
     const float rvx = q[5 * st + qo + c], rvy = q[6 * st + qo + c], rcov = q[7 * st + qo + c];
     g += (double)(rvx / (rmx + 1e-12f));
@@ -702,10 +701,23 @@ __global__ __launch_bounds__(256) void adists_global_kernel(const float *__restr
     __syncthreads();
   }
   if (tid == 0) {
-    gamma[b] = (float)(red[0][0] / creal);
+    if (lead) gamma[xi] = (float)(red[0][0] / creal);
     tw[b] = (float)red[1][0];
     sw[b] = (float)red[2][0];
   }
+}
+
+__global__ __launch_bounds__(256) void adists_global_kernel(const float *__restrict__ q, int B, int ctot, int coff,
+                                                            int creal, const float *__restrict__ wgt,
+                                                            float *__restrict__ gamma, float *__restrict__ tw,
+                                                            float *__restrict__ sw) {
+  global_body<false>(q, B, ctot, coff, creal, wgt, gamma, tw, sw, 1);
+}
+__global__ __launch_bounds__(256) void adists_global_group_kernel(const float *__restrict__ q, int B, int ctot, int coff,
+                                                                  int creal, const float *__restrict__ wgt,
+                                                                  float *__restrict__ gamma, float *__restrict__ tw,
+                                                                  float *__restrict__ sw, int K) {
+  global_body<true>(q, B, ctot, coff, creal, wgt, gamma, tw, sw, K);
 }
 
 // ---------------------------------------------------------------------------------
@@ -889,6 +901,60 @@ __global__ void chain_global_kernel(const float *__restrict__ gamma, const float
   const float ps = sigmoid_ref(gamma[b]) * prev[(size_t)b * hpwp];
   psprod[b] = ps;
   acc[b].dsum = (double)((1.f - ps) * tw[b] + ps * sw[b]);
+}
+
+// The group forms of the two kernels above (nqa_adists_forward_group): gamma, prev, psprod and `acc` are per REFERENCE
+// (blockIdx.y = r), tw / sw and the D partials per pair r * K + k.  An element's ps_prod is computed and stored once;
+// the K renders' sums are then taken against the stored values, each in chain_final_kernel's grid-stride order and with
+// its block reduction, so a pair's partial is the pairwise kernel's bit for bit.  For that the element's term is written
+// with explicit roundings, in the form hipcc contracts the pairwise kernels' `(1 - ps) * tw + ps * sw` to (ISA read:
+// chain_final_kernel tw * (1 - ps), then one fma with sw * ps; chain_global_kernel the same with 1 - ps itself
+// contracted to fma(-prev, sigmoid, 1)) -- left to the compiler the group kernels took the other product first and a
+// pair's D could differ in its last bit.  tests/test_gpu_adists_group_stage.py holds the two forms together.
+__global__ __launch_bounds__(256) void chain_final_group_kernel(const float *__restrict__ gamma, int h, int w,
+                                                                const float *__restrict__ prev, int hp, int wp,
+                                                                const float *__restrict__ tw, const float *__restrict__ sw,
+                                                                float *psprod, const ChainAcc *acc, int K,
+                                                                double *__restrict__ cp /* [R * K][gridDim.x] */) {
+  __shared__ double red[256];
+  const int r = blockIdx.y, n = h * w, tid = threadIdx.x;
+  float mean, sd;
+  zscore(acc[r], n, mean, sd);
+  const float lo = __uint_as_float(acc[r].pp_min), hi = __uint_as_float(acc[r].pp_max);
+  float *ps_r = psprod + (size_t)r * n;
+  for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) {
+    const float pp = pp_value(gamma + (size_t)r * n, acc[r], n, prev + (size_t)r * hp * wp, hp, wp, h, w, i, mean, sd);
+    ps_r[i] = (pp - lo) / (hi - lo + 1e-12f);
+  }
+  for (int k = 0; k < K; ++k) {
+    const size_t b = (size_t)r * K + k;
+    double d = 0.0;
+    for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) {
+      const float ps = ps_r[i];  // this thread's own store above
+      d += (double)fmaf(sw[b * n + i], ps, __fmul_rn(tw[b * n + i], 1.f - ps));
+    }
+    __syncthreads();
+    red[tid] = d;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+      if (tid < off) red[tid] += red[tid + off];
+      __syncthreads();
+    }
+    if (tid == 0) cp[b * gridDim.x + blockIdx.x] = red[0];
+  }
+}
+
+// one thread per pair; gamma, prev, psprod per reference, `acc` (the D sums) per pair
+__global__ void chain_global_group_kernel(const float *__restrict__ gamma, const float *__restrict__ prev, int hpwp,
+                                          const float *__restrict__ tw, const float *__restrict__ sw,
+                                          float *__restrict__ psprod, ChainAcc *acc, int B, int K) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int r = b / K;
+  const float sg = sigmoid_ref(gamma[r]), pv = prev[(size_t)r * hpwp];
+  const float ps = __fmul_rn(pv, sg);
+  if (b - r * K == 0) psprod[r] = ps;
+  acc[b].dsum = (double)fmaf(ps, sw[b], __fmul_rn(tw[b], fmaf(-pv, sg, 1.f)));
 }
 
 __global__ void ones_kernel(float *p, int n) {
@@ -1085,12 +1151,18 @@ static int launch_entropy(const void *feat, int B, int HW, int C, int ppb, const
   return check_launch("entropy");
 }
 
+// The window launchers below take K = 0 for B independent pairs (x and y hold B images each), or K > 0 for the group
+// forms: B = R * K pairs, x holds the R references, wgt R rows, gamma R maps (adists_window_lanes_kernel).
 static int launch_window_planar(const float *x, const float *y, int B, int H, int W, const float *q, int ctot, int coff,
-                                const float *wgt, const Gauss &g, float *gamma, float *tw, float *sw, hipStream_t st) {
+                                const float *wgt, const Gauss &g, float *gamma, float *tw, float *sw, hipStream_t st,
+                                int K = 0) {
   const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
   dim3 grid(cdiv(Wo, 256), cdiv(Ho, 64), B);
   TimedLaunch t(NQA_K_ADISTS, st);
-  adists_window_planar_kernel<<<grid, 256, 0, st>>>(x, y, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw);
+  if (K > 0)
+    adists_window_planar_group_kernel<<<grid, 256, 0, st>>>(x, y, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw, K);
+  else
+    adists_window_planar_kernel<<<grid, 256, 0, st>>>(x, y, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw);
   return check_launch("adists_window_planar");
 }
 
@@ -1117,7 +1189,7 @@ static bool window_uses_lds(size_t tap_elem_bytes) { return tap_elem_bytes == 4 
 template <typename P>
 static int launch_window_lanes(const void *fx, const void *fy, int B, int H, int W, int C, const float *q, int ctot,
                                int coff, const float *wgt, const Gauss &g, float *gamma, float *tw, float *sw,
-                               hipStream_t st, int strip_req = 0) {
+                               hipStream_t st, int strip_req = 0, int K = 0) {
   const int Ho = H - (kWin - 1), Wo = W - (kWin - 1);
   const typename P::T *px = reinterpret_cast<const typename P::T *>(fx), *py = reinterpret_cast<const typename P::T *>(fy);
   // the shipped form for float taps (f32 / f32s): taps shared through LDS, XCD-aware column order.  16-bit taps
@@ -1135,8 +1207,12 @@ static int launch_window_lanes(const void *fx, const void *fy, int B, int H, int
     }
     TimedLaunch t(NQA_K_ADISTS, st);
 #define NQA_WIN(CC)                                                                                                  \
-  adists_window_lds_kernel<P, CC><<<(unsigned)nblk, 256, LDS, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, \
-                                                                    tw, sw, nbx, nby, strip)
+  if (K > 0)                                                                                                         \
+    adists_window_lds_group_kernel<P, CC><<<(unsigned)nblk, 256, LDS, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, \
+                                                                            gamma, tw, sw, nbx, nby, strip, K);     \
+  else                                                                                                               \
+    adists_window_lds_kernel<P, CC><<<(unsigned)nblk, 256, LDS, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, \
+                                                                      tw, sw, nbx, nby, strip)
     switch (C) {
       case 64: NQA_WIN(64); break;
       case 128: NQA_WIN(128); break;
@@ -1150,20 +1226,29 @@ static int launch_window_lanes(const void *fx, const void *fy, int B, int H, int
   }
   dim3 grid(cdiv(Wo, 4), cdiv(Ho, 64), B);
   TimedLaunch t(NQA_K_ADISTS, st);
+#define NQA_LANES(CC)                                                                                                   \
+  if (K > 0)                                                                                                            \
+    adists_window_lanes_group_kernel<P, CC><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw, K); \
+  else                                                                                                                  \
+    adists_window_lanes_kernel<P, CC><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw)
   switch (C) {
-    case 64: adists_window_lanes_kernel<P, 64><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw); break;
-    case 128: adists_window_lanes_kernel<P, 128><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw); break;
-    case 256: adists_window_lanes_kernel<P, 256><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw); break;
-    case 512: adists_window_lanes_kernel<P, 512><<<grid, 256, 0, st>>>(px, py, H, W, q, B, ctot, coff, wgt, g, gamma, tw, sw); break;
+    case 64: NQA_LANES(64); break;
+    case 128: NQA_LANES(128); break;
+    case 256: NQA_LANES(256); break;
+    case 512: NQA_LANES(512); break;
     default: set_error("adists_window_lanes: unsupported channel count %d", C); return NQA_E_SHAPE;
   }
+#undef NQA_LANES
   return check_launch("adists_window_lanes");
 }
 
 static int launch_global(const float *q, int B, int ctot, int coff, int creal, const float *wgt, float *gamma,
-                         float *tw, float *sw, hipStream_t st) {
+                         float *tw, float *sw, hipStream_t st, int K = 0) {
   TimedLaunch t(NQA_K_ADISTS, st);
-  adists_global_kernel<<<B, 256, 0, st>>>(q, B, ctot, coff, creal, wgt, gamma, tw, sw);
+  if (K > 0)
+    adists_global_group_kernel<<<B, 256, 0, st>>>(q, B, ctot, coff, creal, wgt, gamma, tw, sw, K);
+  else
+    adists_global_kernel<<<B, 256, 0, st>>>(q, B, ctot, coff, creal, wgt, gamma, tw, sw);
   return check_launch("adists_global");
 }
 
@@ -1681,6 +1766,363 @@ int nqa_adists_dists_forward(const float *x, const float *y, int B, int H, int W
     return NQA_E_ARG;
   }
   return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, map_out, stream, s1, s2);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// K renders against ONE reference, for R such groups (include/nqa.h, nqa_adists_forward_group).  Everything A-DISTS takes
+// from x alone -- the reference's pyramid, its entropy weights, gamma and the probability chain -- runs once per
+// reference; the window pass and the D sums run per pair r * K + k against it.
+// ---------------------------------------------------------------------------------
+static const long kAdistsGroupMaxPairs = 65535;  // pairs ride a grid's y / z dimension (adists_prep_kernel, finalize)
+
+struct GroupPlan {
+  // byte offsets into the workspace
+  size_t bufA, bufB, taps[5], img4, part, q, ent, hsum, wgt, maps[NQA_NUM_TAPS][4], acc_ref, acc_pair, chain_part, ones,
+      total;
+  StageDesc sd;  // statistics partials in finalize's layout, B := R * K (the group statistics kernels' blocks)
+  EntDesc ed;    // entropy partials of the R references
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS], c[NQA_NUM_TAPS];
+  int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];
+  bool windowed[NQA_NUM_TAPS];
+  int ent_ppb[NQA_NUM_TAPS];
+};
+
+static GroupPlan make_group_plan(int R, int K, int H, int W, int prec) {
+  GroupPlan p;
+  memset(&p, 0, sizeof(p));
+  const size_t esz = prec_elem_bytes(prec);
+  const int B = R * K, n = R + B;
+  tap_dims(H, W, p.h, p.w);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) p.c[k] = kChns[k];
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += align_up(bytes, 256);
+    return o;
+  };
+  const size_t act = (size_t)n * max_act_elems(H, W) * esz;
+  p.bufA = take(act);
+  p.bufB = take(act);
+  for (int k = 0; k < 5; ++k) p.taps[k] = take((size_t)n * p.h[k + 1] * p.w[k + 1] * p.c[k + 1] * esz);
+  p.img4 = take((size_t)R * H * W * 4 * 4);
+  // the statistics partials as nqa_dists_forward_group lays them out: the plane kernel on the images, the NHWC group
+  // kernel on the five taps
+  long doff = 0, eoff = 0;
+  int coff = 0;
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    const int hw = p.h[k] * p.w[k];
+    p.sd.part_off[k] = doff;
+    p.sd.nblk[k] = k == 0 ? cdiv(hw, stats_nchw_ppb(hw)) : cdiv(hw, group_stats_units_per_block(hw, p.c[k], prec, R));
+    p.sd.hw[k] = hw;
+    p.sd.c[k] = p.c[k];
+    p.sd.coff[k] = coff;
+    doff += (long)B * p.sd.nblk[k] * p.c[k] * 5;
+    const int cpad = k == 0 ? 4 : p.c[k];
+    p.ent_ppb[k] = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, R);
+    p.ed.part_off[k] = eoff;
+    p.ed.nblk[k] = cdiv(hw, p.ent_ppb[k]);
+    p.ed.c[k] = cpad;
+    p.ed.creal[k] = p.c[k];
+    p.ed.coff[k] = coff;
+    eoff += (long)R * p.ed.nblk[k] * cpad;
+    coff += p.c[k];
+  }
+  p.sd.nstage = NQA_NUM_TAPS;
+  p.sd.ctot = p.ed.ctot = coff;
+  p.part = take((size_t)doff * 8);
+  p.q = take((size_t)8 * B * coff * 4);
+  p.ent = take((size_t)eoff * 8);
+  p.hsum = take((size_t)R * coff * 4);
+  p.wgt = take((size_t)R * coff * 4);
+  map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k)
+    for (int j = 0; j < 4; ++j)  // gamma and ps_prod per reference, tw and sw per pair
+      p.maps[k][j] = take((size_t)(j == 0 || j == 3 ? R : B) * p.mh[k] * p.mw[k] * 4);
+  p.acc_ref = take((size_t)6 * R * sizeof(ChainAcc));
+  p.acc_pair = take((size_t)6 * B * sizeof(ChainAcc));
+  p.chain_part = take((size_t)(2 * R > B ? 2 * R : B) * kChainBlocks * sizeof(double));
+  p.ones = take((size_t)R * sizeof(float));
+  p.total = off;
+  return p;
+}
+
+// NQA_OK if the group forward takes these arguments, else NQA_E_ARG with the error set under the caller's name
+static int group_args_check(const char *who, int R, int K, int H, int W, int prec) {
+  if (R <= 0 || K <= 0 || H <= 0 || W <= 0) {
+    set_error("%s: non-positive size (R=%d K=%d H=%d W=%d)", who, R, K, H, W);
+    return NQA_E_ARG;
+  }
+  if ((long)R * K > kAdistsGroupMaxPairs) {
+    set_error("%s: R*K = %ld pairs, more than %ld in one call (slice over R)", who, (long)R * K, kAdistsGroupMaxPairs);
+    return NQA_E_ARG;
+  }
+  if (!prec_valid(prec)) {
+    set_error(is_mixed(prec) ? "%s: the mixed modes are DISTS modes (prec %d): A-DISTS needs float precision in every layer"
+                             : "%s: unknown prec %d", who, prec);
+    return NQA_E_ARG;
+  }
+  if ((long)H * W * 64 * (long)prec_elem_bytes(prec) >= (1L << 31)) {
+    set_error("%s: image too large for 32-bit in-image byte offsets", who);
+    return NQA_E_ARG;
+  }
+  return NQA_OK;
+}
+
+// The front of the group forward behind the statistics sums: adists_prep_kernel's scalars for the R * K pairs (from
+// finalize's layout, which the group statistics kernels fill; a wave per value, adists_prep_group_kernel), then the NHWC4 conversion, the six entropy passes, their fold and the
+// weights kernel on the R REFERENCES alone.  Reference r's inv_x / sum_x are those of pair r * K: the entropy kernel
+// indexes its two rows by image * stride, and the stride handed over is K rows.
+static int launch_front_group(const float *ref, void *const *taps, int R, int K, const GroupPlan &p, int prec,
+                              const double *part, float *q /* [8][R*K][ctot] */, float *img4, double *ent,
+                              float *hsum /* [R][ctot] */, float *wgt /* [R][ctot] */, hipStream_t st) {
+  const int ctot = p.sd.ctot, H = p.h[0], W = p.w[0], B = R * K;
+  int rc;
+  {
+    dim3 grid(cdiv(ctot, 4), B);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_prep_group_kernel<<<grid, 256, 0, st>>>(part, p.sd, q, B);
+    if ((rc = check_launch("adists_prep_group"))) return rc;
+  }
+  {
+    dim3 grid(cdiv(H * W, 256), R);
+    TimedLaunch t(NQA_K_ADISTS, st);
+    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(ref, img4, H * W);
+    if ((rc = check_launch("nchw3_to_nhwc4"))) return rc;
+  }
+  const size_t qst = (size_t)B * ctot;
+  const int stride = ctot * K;  // rows of q between two references' first pairs
+  if ((rc = launch_entropy<PrecF32>(img4, R, H * W, 4, p.ent_ppb[0], q + 0 * qst + p.sd.coff[0], q + 2 * qst + p.sd.coff[0],
+                                    stride, ent + p.ed.part_off[0], st)))
+    return rc;
+  for (int k = 1; k < NQA_NUM_TAPS; ++k) {
+    const int hw = p.h[k] * p.w[k];
+    const float *invx = q + 0 * qst + p.sd.coff[k], *sumx = q + 2 * qst + p.sd.coff[k];
+    double *ep = ent + p.ed.part_off[k];
+    switch (storage_prec(prec)) {  // (the references are the first R images of every tap)
+      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
+      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
+      default: rc = launch_entropy<PrecF16>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
+    }
+    if (rc) return rc;
+  }
+  {
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), R), 256, 0, st>>>(ent, p.ed, hsum);
+    adists_weights_kernel<<<R, 256, 0, st>>>(hsum, p.ed, wgt);
+    if ((rc = check_launch("adists_weights"))) return rc;
+  }
+  return NQA_OK;
+}
+
+// One stage of the group window pass: fx the R references' maps, fy the R * K renders', dispatched as adists_run
+// dispatches a pair stage.  nqa_adists_forward_group and nqa_adists_window_stage_group both launch through it.
+static int launch_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
+                                     const float *q, int ctot, int coff, const float *wgt, const Gauss &g, float *gamma,
+                                     float *tw, float *sw, hipStream_t st, int strip = 0) {
+  const int B = R * K;
+  if (H < kWin || W < kWin) return launch_global(q, B, ctot, coff, C, wgt, gamma, tw, sw, st, K);
+  if (C == 3)
+    return launch_window_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, ctot, coff,
+                                wgt, g, gamma, tw, sw, st, K);
+  switch (storage_prec(prec)) {
+    case NQA_PREC_F32: return launch_window_lanes<PrecF32>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
+    case NQA_PREC_BF16: return launch_window_lanes<PrecBF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
+    default: return launch_window_lanes<PrecF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
+  }
+}
+
+// The back part of the group forward.  m.gamma and m.ps hold R maps per stage, m.tw and m.sw R * K.  The probability
+// part (moments, fold, the two min / max passes, the global branch's sigmoid) is launch_chain's with B := R; the group
+// kernels then take the K renders' D sums against each reference's ps_prod, and adists_d_kernel runs over the pairs.
+static int launch_chain_group(const ChainMaps &m, int R, int K, ChainAcc *acc_ref /* [6][R] */,
+                              ChainAcc *acc_pair /* [6][R*K] */, double *cp /* [max(2 R, R K)][kChainBlocks] */,
+                              float *ones /* [R] */, float *d_out, hipStream_t st) {
+  const int B = R * K;
+  TimedLaunch t(NQA_K_ADISTS, st);
+  chain_init_kernel<<<cdiv(6 * R, 256), 256, 0, st>>>(acc_ref, 6 * R);
+  chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc_pair, 6 * B);
+  ones_kernel<<<cdiv(R, 256), 256, 0, st>>>(ones, R);
+  const float *prev = ones;
+  int hp = 1, wp = 1;
+  for (int k = 5; k >= 0; --k) {
+    const float *gamma = m.gamma[k], *tw = m.tw[k], *sw = m.sw[k];
+    float *psprod = m.ps[k];
+    ChainAcc *ar = acc_ref + (size_t)k * R, *ap = acc_pair + (size_t)k * B;
+    if (m.windowed[k]) {
+      const int n = m.mh[k] * m.mw[k];
+      dim3 grid(min(cdiv(n, 256), kChainBlocks), R);
+      chain_moments_kernel<<<grid, 256, 0, st>>>(gamma, n, cp);
+      chain_fold_kernel<<<R, 256, 0, st>>>(cp, grid.x, 2, 0, ar);
+      chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, ar);
+      chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, ar);
+      chain_final_group_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, ar, K, cp);
+      chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, ap);
+    } else {
+      chain_global_group_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, ap, B, K);
+    }
+    prev = psprod;
+    hp = m.mh[k];
+    wp = m.mw[k];
+  }
+  DDesc dd;
+  for (int k = 0; k < 6; ++k) dd.n[k] = m.mh[k] * m.mw[k];
+  adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc_pair, dd, B, d_out);
+  return check_launch("adists_chain_group");
+}
+
+struct ChainGroupPlan {
+  size_t acc_ref, acc_pair, part, ones, total;
+};
+static ChainGroupPlan chain_group_plan(int R, int K) {
+  const int B = R * K;
+  ChainGroupPlan c;
+  c.acc_ref = 0;
+  c.acc_pair = align_up((size_t)6 * R * sizeof(ChainAcc), 256);
+  c.part = c.acc_pair + align_up((size_t)6 * B * sizeof(ChainAcc), 256);
+  c.ones = c.part + align_up((size_t)(2 * R > B ? 2 * R : B) * kChainBlocks * sizeof(double), 256);
+  c.total = c.ones + align_up((size_t)R * sizeof(float), 256);
+  return c;
+}
+
+extern "C" {
+
+size_t nqa_adists_group_workspace_bytes(int R, int K, int H, int W, int prec) {
+  if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs || !prec_valid(prec)) return 0;
+  if ((long)H * W * 64 * (long)prec_elem_bytes(prec) >= (1L << 31)) return 0;
+  return make_group_plan(R, K, H, W, prec).total;
+}
+
+int nqa_adists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W, const void *packed,
+                             int prec, void *ws, size_t ws_bytes, float *d_out, float *s1, float *s2, void *stream) {
+  if (!ref || !renders || !packed || !ws || !d_out) {
+    set_error("adists_forward_group: null pointer");
+    return NQA_E_ARG;
+  }
+  if ((s1 == nullptr) != (s2 == nullptr)) {
+    set_error("adists_forward_group: s1 and s2 must both be given or both be null");
+    return NQA_E_ARG;
+  }
+  if (int rc = group_args_check("adists_forward_group", R, K, H, W, prec)) return rc;
+  const GroupPlan p = make_group_plan(R, K, H, W, prec);
+  if (ws_bytes < p.total) {
+    set_error("adists_forward_group: workspace %zu < %zu bytes", ws_bytes, p.total);
+    return NQA_E_WORKSPACE;
+  }
+  const Gauss *gp = checked_gauss("adists_forward_group");
+  if (!gp) return NQA_E_LAUNCH;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char *base = static_cast<char *>(ws);
+  const size_t esz = prec_elem_bytes(prec);
+  const int B = R * K, n = R + B, ctot = p.sd.ctot;
+  double *part = reinterpret_cast<double *>(base + p.part);
+  float *q = reinterpret_cast<float *>(base + p.q);
+  float *wgt = reinterpret_cast<float *>(base + p.wgt);
+  void *taps[5];
+  for (int k = 0; k < 5; ++k) taps[k] = base + p.taps[k];
+  int rc;
+
+  // ---- one pyramid of R + R * K images (the references first, render (r, k) at image R + r * K + k), all five taps
+  // kept; the group statistics kernels leave the pairs' sums in finalize's layout; the plain L2-pools follow ----
+  if ((rc = group_stats_nchw(ref, renders, R, K, 3, H * W, part + p.sd.part_off[0], st))) return rc;
+  rc = run_stages(ref, renders, R, base + p.bufA, base + p.bufB, n, H, W, packed, prec, taps,
+                  [&](int k, void *tap, int hk, int wk, int ck, void *) {
+                    const char *rn = static_cast<const char *>(tap) + (size_t)R * hk * wk * ck * esz;
+                    return group_stats_nhwc(tap, rn, R, K, hk * wk, ck, prec, part + p.sd.part_off[k + 1], st);
+                  },
+                  st);
+  if (rc) return rc;
+  // ---- DISTS' S1 / S2 of the pairs from the same sums ----
+  if (s1 && (rc = finalize(part, p.sd, B, s1, s2, st))) return rc;
+  // ---- per-pair scalars; NHWC4 images, entropies and channel weights of the references ----
+  if ((rc = launch_front_group(ref, taps, R, K, p, prec, part, q, reinterpret_cast<float *>(base + p.img4),
+                               reinterpret_cast<double *>(base + p.ent), reinterpret_cast<float *>(base + p.hsum), wgt, st)))
+    return rc;
+  // ---- heavy pass: tw / sw per pair, gamma per reference ----
+  ChainMaps cm;
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    float *gamma = reinterpret_cast<float *>(base + p.maps[k][0]);
+    float *tw = reinterpret_cast<float *>(base + p.maps[k][1]);
+    float *sw = reinterpret_cast<float *>(base + p.maps[k][2]);
+    cm.gamma[k] = gamma;
+    cm.tw[k] = tw;
+    cm.sw[k] = sw;
+    cm.ps[k] = reinterpret_cast<float *>(base + p.maps[k][3]);
+    cm.mh[k] = p.mh[k];
+    cm.mw[k] = p.mw[k];
+    cm.windowed[k] = p.windowed[k];
+    const void *fx = k == 0 ? static_cast<const void *>(ref) : taps[k - 1];
+    const void *fy = k == 0 ? static_cast<const void *>(renders)
+                            : static_cast<const char *>(taps[k - 1]) + (size_t)R * p.h[k] * p.w[k] * p.c[k] * esz;
+    if ((rc = launch_window_stage_group(fx, fy, R, K, p.h[k], p.w[k], p.c[k], prec, q, ctot, p.sd.coff[k], wgt, *gp, gamma,
+                                        tw, sw, st)))
+      return rc;
+  }
+  // ---- probability chain per reference, D per pair ----
+  return launch_chain_group(cm, R, K, reinterpret_cast<ChainAcc *>(base + p.acc_ref),
+                            reinterpret_cast<ChainAcc *>(base + p.acc_pair), reinterpret_cast<double *>(base + p.chain_part),
+                            reinterpret_cast<float *>(base + p.ones), d_out, st);
+}
+
+int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
+                                  const float *q, const float *wgt, int strip, float *gamma, float *tw, float *sw,
+                                  void *stream) {
+  if (!fx || !fy || !q || !wgt || !gamma || !tw || !sw) {
+    set_error("adists_window_stage_group: null pointer");
+    return NQA_E_ARG;
+  }
+  if (R <= 0 || K <= 0 || (long)R * K > kAdistsGroupMaxPairs) {
+    set_error("adists_window_stage_group: bad group (R=%d K=%d; at most %ld pairs)", R, K, kAdistsGroupMaxPairs);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_stage_check("adists_window_stage_group", R * K, H, W, C, prec, strip)) return rc;
+  const Gauss *gp = checked_gauss("adists_window_stage_group");
+  if (!gp) return NQA_E_LAUNCH;
+  return launch_window_stage_group(fx, fy, R, K, H, W, C, prec, q, C, 0, wgt, *gp, gamma, tw, sw,
+                                   static_cast<hipStream_t>(stream), strip);
+}
+
+size_t nqa_adists_chain_group_bytes(int R, int K, int H, int W) {
+  if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs) return 0;
+  return chain_group_plan(R, K).total;
+}
+
+int nqa_adists_chain_group(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K, int H,
+                           int W, void *ws, size_t ws_bytes, float *const *ps_prod, float *d, void *stream) {
+  if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
+    set_error("adists_chain_group: null pointer");
+    return NQA_E_ARG;
+  }
+  for (int k = 0; k < NQA_NUM_TAPS; ++k)
+    if (!gamma[k] || !tw[k] || !sw[k] || !ps_prod[k]) {
+      set_error("adists_chain_group: null pointer (stage %d)", k);
+      return NQA_E_ARG;
+    }
+  if (R <= 0 || K <= 0 || (long)R * K > kAdistsGroupMaxPairs) {
+    set_error("adists_chain_group: bad group (R=%d K=%d; at most %ld pairs)", R, K, kAdistsGroupMaxPairs);
+    return NQA_E_ARG;
+  }
+  if (int rc = chain_frame_check("adists_chain_group", R, H, W)) return rc;
+  const ChainGroupPlan c = chain_group_plan(R, K);
+  if (ws_bytes < c.total) {
+    set_error("adists_chain_group: workspace %zu < %zu bytes", ws_bytes, c.total);
+    return NQA_E_WORKSPACE;
+  }
+  ChainMaps cm;
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
+  tap_dims(H, W, h, w);
+  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    cm.gamma[k] = gamma[k];
+    cm.tw[k] = tw[k];
+    cm.sw[k] = sw[k];
+    cm.ps[k] = ps_prod[k];
+  }
+  char *base = static_cast<char *>(ws);
+  return launch_chain_group(cm, R, K, reinterpret_cast<ChainAcc *>(base + c.acc_ref),
+                            reinterpret_cast<ChainAcc *>(base + c.acc_pair), reinterpret_cast<double *>(base + c.part),
+                            reinterpret_cast<float *>(base + c.ones), d, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -584,6 +584,100 @@ def adists_dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor,
     return (d, s1, s2, m) if with_map else (d, s1, s2)
 
 
+def adists_forward_group(ref: torch.Tensor, renders: torch.Tensor, packed: torch.Tensor, prec,
+                         ws: Workspace | None = None, with_dists: bool = False):
+    """D (R*K,) float32 of K renders against ONE reference for R such groups: ref (R,3,H,W), renders (R,K,3,H,W), pair
+    r * K + k = (ref[r], renders[r, k]) with x = the reference.  Everything A-DISTS takes from x alone runs once per
+    reference (include/nqa.h, nqa_adists_forward_group).  with_dists=True returns (D, S1, S2), S1 / S2 (R*K,1475) the
+    DISTS similarities of the same pairs from the same sums.  Groups are independent: a batch of more than 65 535 pairs,
+    or one whose workspace would exceed NQA_MAX_WORKSPACE_GB, runs in equal slices over R."""
+    p = prec_id(prec)
+    dev = _need_cuda(ref, renders, packed)
+    r, k, h, w = _group_dims(ref, renders)
+    ref, renders = _f32c(ref), _f32c(renders)
+    mr = _max_pairs(lambda n: lib().nqa_adists_group_workspace_bytes(n, k, h, w, p), r)
+    mr = max(1, min(mr, 65535 // k))  # (pairs of one call: the library's limit)
+    if mr < r:
+        parts = [adists_forward_group(ref[i:i + mr], renders[i:i + mr], packed, prec, ws, with_dists)
+                 for i in range(0, r, mr)]
+        if with_dists:
+            return tuple(torch.cat([q[j] for q in parts]) for j in range(3))
+        return torch.cat(parts)
+    d = torch.empty((r * k,), dtype=torch.float32, device=dev)
+    s1 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev) if with_dists else None
+    s2 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev) if with_dists else None
+    nbytes = lib().nqa_adists_group_workspace_bytes(r, k, h, w, p)
+    buf = (ws or Workspace()).get(nbytes, dev)
+    _call(dev, lib().nqa_adists_forward_group, ptr(ref), ptr(renders), r, k, h, w, ptr(packed), p, ptr(buf), buf.numel(),
+          ptr(d), ptr(s1) if with_dists else None, ptr(s2) if with_dists else None, stream_ptr(dev))
+    return (d, s1, s2) if with_dists else d
+
+
+def adists_window_stage_group(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, prec,
+                              strip: int = 0):
+    """One stage of the group window pass as adists_forward_group launches it (include/nqa.h,
+    nqa_adists_window_stage_group): fx the R references' maps, fy the R*K renders' (pair r * K + k), q (8,R*K,C), wgt
+    (R,C); maps as adists_window_stage takes them.  Returns gamma (R, mh, mw) and tw, sw (R*K, mh, mw)."""
+    p, strip = prec_id(prec), int(strip)
+    dev = _need_cuda(fx, fy, q, wgt)
+    if p not in PREC_DTYPE:
+        raise ValueError(f"adists_window_stage_group: prec {p} is not one of the kernel-level modes")
+    if q.dim() != 3 or q.shape[0] != 8 or q.shape[2] not in CHNS or wgt.dim() != 2 or fx.dim() != 4 or fy.dim() != 4:
+        raise ValueError(f"adists_window_stage_group: expected q (8,R*K,C), wgt (R,C) and 4-d maps, got "
+                         f"{tuple(q.shape)} / {tuple(wgt.shape)} / {tuple(fx.shape)} / {tuple(fy.shape)}")
+    b, c, r = int(q.shape[1]), int(q.shape[2]), int(wgt.shape[0])
+    if r <= 0 or b % r:
+        raise ValueError(f"adists_window_stage_group: {b} pairs do not divide into {r} groups")
+    k = b // r
+    h, w = (int(fx.shape[2]), int(fx.shape[3])) if c == 3 else (int(fx.shape[1]), int(fx.shape[2]))
+    one = (3, h, w) if c == 3 else (h, w, c)
+    want = torch.float32 if c == 3 else PREC_DTYPE[p]
+    for name, t, sh, dt in (("fx", fx, (r,) + one, want), ("fy", fy, (b,) + one, want), ("q", q, (8, b, c), torch.float32),
+                            ("wgt", wgt, (r, c), torch.float32)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"adists_window_stage_group: {name} must be contiguous {dt} {sh}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    windowed = h >= WINDOW and w >= WINDOW
+    mh, mw = (h - WINDOW + 1, w - WINDOW + 1) if windowed else (1, 1)
+    if strip < 0 or (windowed and strip > mh):
+        raise ValueError(f"adists_window_stage_group: strip {strip} outside [0, {mh if windowed else 0}]")
+    gamma = torch.empty((r, mh, mw), dtype=torch.float32, device=dev)
+    tw = torch.empty((b, mh, mw), dtype=torch.float32, device=dev)
+    sw = torch.empty((b, mh, mw), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_adists_window_stage_group, ptr(fx), ptr(fy), r, k, h, w, c, p, ptr(q), ptr(wgt), strip,
+          ptr(gamma), ptr(tw), ptr(sw), stream_ptr(dev))
+    return gamma, tw, sw
+
+
+def adists_chain_group(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor], sw: Sequence[torch.Tensor], h: int,
+                       w: int, ws: Workspace | None = None):
+    """The back part of adists_forward_group as it launches it (include/nqa.h, nqa_adists_chain_group): gamma six
+    (R, mh, mw) maps, tw / sw six (R*K, mh, mw) maps for an h x w frame -> (ps_prod: six (R, mh, mw) maps, D (R*K,))."""
+    _chain_lists(gamma=gamma, tw=tw, sw=sw)
+    dev = _need_cuda(*gamma, *tw, *sw)
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or gamma[0].dim() != 3 or tw[0].dim() != 3 or gamma[0].shape[0] == 0 \
+            or tw[0].shape[0] % gamma[0].shape[0]:
+        raise ValueError(f"adists_chain_group: expected gamma (R, mh, mw) and tw (R*K, mh, mw), got "
+                         f"{tuple(gamma[0].shape)} / {tuple(tw[0].shape)}")
+    r, b = int(gamma[0].shape[0]), int(tw[0].shape[0])
+    dims, _ = adists_chain_dims(h, w)
+    for name, ts, n in (("gamma", gamma, r), ("tw", tw, b), ("sw", sw, b)):
+        for k, t in enumerate(ts):
+            sh = (n,) + dims[k]
+            if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"adists_chain_group: {name}[{k}] must be contiguous float32 {sh}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+    ps = [torch.empty((r,) + dm, dtype=torch.float32, device=dev) for dm in dims]
+    d = torch.empty((b,), dtype=torch.float32, device=dev)
+    nbytes = lib().nqa_adists_chain_group_bytes(r, b // r, h, w)
+    buf = (ws or Workspace()).get(nbytes, dev)
+    arr = lambda ts: (C.c_void_p * 6)(*[ptr(t) for t in ts])
+    _call(dev, lib().nqa_adists_chain_group, arr(gamma), arr(tw), arr(sw), r, b // r, h, w, ptr(buf), buf.numel(), arr(ps),
+          ptr(d), stream_ptr(dev))
+    return ps, d
+
+
 def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, p: int, strip: int):
     """Every check of adists_window_stage on its inputs; (B, H, W, C, output shape).  C is q's: 3 means float32 NCHW
     planes, anything else NHWC taps in prec's storage type."""

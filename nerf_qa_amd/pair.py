@@ -91,3 +91,20 @@ def score_pair(dists_model, adists_model, x, y, batch_average=False, as_loss=Fal
                 x, y, prec, lambda a, b, packed: ops.adists_dists_forward(a, b, packed, prec, ws))
             a_out = 1 - d.mean() if as_loss else 1 - d
     return dists_model._weighted(s1, s2, batch_average), a_out
+
+
+def score_group(dists_model, adists_model, ref, renders):
+    """(DISTS (R,K), A-DISTS (R,K)) of K renders against ONE reference for R such groups, from one pyramid of R + R*K
+    images: ref (R,3,H,W), renders (R,K,3,H,W), entry [r, k] the pair (ref[r], renders[r, k]) with x = the reference.
+    The contract of score_pair for batch_average=False, as_loss=False: the A-DISTS half is
+    adists_model.forward_group(ref, renders) bit for bit; the DISTS half is DISTS(precision=<pair precision>)
+    .forward_group, folded from the sums A-DISTS forms anyway, through the module's own alpha / beta weighting.  The pair
+    runs in A-DISTS' precision (pair_precision).  Raises as score_pair does."""
+    r, k, h, w = adists_model._group_checks(ref, renders, "score_group")
+    prec = pair_precision(dists_model, adists_model, h, w)
+    dev = ref.device
+    _check_same_weights(dists_model, adists_model, dev)
+    with torch.no_grad():
+        d, s1, s2 = ops.adists_forward_group(ref, renders, adists_model._packed_weights(dev, prec), prec, adists_model._ws,
+                                             with_dists=True)
+    return dists_model._weighted(s1, s2, False).reshape(r, k), (1 - d).reshape(r, k)

@@ -141,14 +141,24 @@ def score_video(ref: torch.Tensor, render: torch.Tensor, dists_model: Optional[t
 @torch.no_grad()
 def score_videos(ref: torch.Tensor, renders, dists_model: torch.nn.Module, batch_size: int = 8, group=None,
                  policy: Optional[str] = None, keep_aspect_ratio: bool = False, suffix: str = "",
-                 with_frame_bias: bool = True, return_frame_scores: bool = False) -> List[Dict[str, object]]:
+                 with_frame_bias: bool = True, return_frame_scores: bool = False, *,
+                 adists_model: Optional[torch.nn.Module] = None, shared_pyramid: bool = False) -> List[Dict[str, object]]:
     """DISTS of K rendered videos of ONE scene against its reference video (the rows of the reference's tables that share
     a reference_folder, test2_prep.py:89,201,304,404): `ref` as score_video takes it, `renders` a (K,N,...) tensor or a
     list of K tensors of ref's shape.  Returns a list of K column dicts, entry k what
     score_video(ref, renders[k], dists_model, ...) returns -- but every batch of reference frames goes through the VGG
     pyramid ONCE for the K renders (DISTS.forward_group) instead of once per render.  Frames are taken in batches of
     `batch_size` reference frames (each with its K renders); under a process group the frame ranges shard as in
-    score_video and ONE all-gather moves the (N, K) score table."""
+    score_video and ONE all-gather moves the (N, K) score table.
+
+    adists_model (keyword only): each of the K dicts also carries the A-DISTS columns and `frame_bias_adists`, named and
+    ordered as score_video(ref, renders[k], dists_model, adists_model, ...) returns them, from ADISTS.forward_group: the
+    reference frames' pyramid, entropy weights and texture-probability chain run once per batch for the K renders.
+    shared_pyramid=True (adists_model required): every batch is ONE pair.score_group call -- both metrics from one pyramid
+    of the batch's references and renders, in A-DISTS' precision (score_video's shared_pyramid, for groups) -- and one
+    all-gather moves the (N, 2K) table.  Without the two arguments the call is what it always was."""
+    if shared_pyramid and adists_model is None:
+        raise ValueError("score_videos(shared_pyramid=True) scores DISTS and A-DISTS from one pyramid: pass adists_model")
     rens = list(renders.unbind(0)) if torch.is_tensor(renders) else list(renders)
     if not rens:
         raise ValueError("score_videos: no renders")
@@ -157,26 +167,48 @@ def score_videos(ref: torch.Tensor, renders, dists_model: torch.nn.Module, batch
             raise ValueError(f"score_videos: render {k} differs from ref in shape: {tuple(getattr(t, 'shape', ()))} vs "
                              f"{tuple(ref.shape)}")
     n, kk = ref.shape[0], len(rens)
-    if getattr(dists_model, "precision", None) == "auto" and policy is None:  # one precision mode per video (score_video)
+    if not shared_pyramid and getattr(dists_model, "precision", None) == "auto" and policy is None:
+        # one precision mode per video (score_video); the shared pyramid runs in A-DISTS' precision, a function of the size
         sharding.agree_precision(dists_model, int(ref.shape[-2]), int(ref.shape[-1]), ref.device, group)
 
-    def batch(lo, hi):
-        a, bs = ref[lo:hi], [t[lo:hi] for t in rens]
-        if policy is not None:
-            a = prep.prepare_frames(a, policy, keep_aspect_ratio=keep_aspect_ratio)
-            bs = [prep.prepare_frames(b, policy, keep_aspect_ratio=keep_aspect_ratio) for b in bs]
-        return dists_model.forward_group(a, torch.stack(bs, dim=1), batch_average=False)
+    def run(call, columns):
+        def batch(lo, hi):
+            a, bs = ref[lo:hi], [t[lo:hi] for t in rens]
+            if policy is not None:
+                a = prep.prepare_frames(a, policy, keep_aspect_ratio=keep_aspect_ratio)
+                bs = [prep.prepare_frames(b, policy, keep_aspect_ratio=keep_aspect_ratio) for b in bs]
+            return call(a, torch.stack(bs, dim=1))
 
-    table = sharding.score_frames_sharded(batch, n, batch_size, ref.device, group, columns=kk).cpu().numpy().reshape(n, kk)
+        scores = sharding.score_frames_sharded(batch, n, batch_size, ref.device, group, columns=columns)
+        return scores.cpu().numpy().reshape(n, columns)
+
+    tables = {}
+    if shared_pyramid:
+        from .pair import score_group
+
+        def both(a, b):
+            ds, ad = score_group(dists_model, adists_model, a, b)
+            return torch.cat([ad.float(), ds.float()], dim=1)
+
+        table = run(both, 2 * kk)
+        tables["A-DISTS"], tables["DISTS"] = table[:, :kk], table[:, kk:]
+    else:
+        if adists_model is not None:
+            tables["A-DISTS"] = run(lambda a, b: adists_model.forward_group(a, b, as_loss=False), kk)
+        tables["DISTS"] = run(lambda a, b: dists_model.forward_group(a, b, batch_average=False), kk)
     outs = []
     for k in range(kk):
-        s = np.ascontiguousarray(table[:, k])
-        out: Dict[str, object] = dict(video_columns("DISTS", s, suffix))
+        frames = {name: np.ascontiguousarray(tables[name][:, k]) for name in ("A-DISTS", "DISTS") if name in tables}
+        out: Dict[str, object] = {}
+        for name, s in frames.items():  # (score_video's order: the A-DISTS columns first)
+            out.update(video_columns(name, s, suffix))
         if with_frame_bias:
             out["frame_count"] = -(-n // batch_size)  # len(DataLoader): batches, as the reference counts them
-            out["frame_bias_dists"] = to_str(frame_bias(s))
+            if "A-DISTS" in frames:
+                out["frame_bias_adists"] = to_str(frame_bias(frames["A-DISTS"]))
+            out["frame_bias_dists"] = to_str(frame_bias(frames["DISTS"]))
         if return_frame_scores:
-            out["_frame_scores"] = {"DISTS": s}
+            out["_frame_scores"] = frames
         outs.append(out)
     return outs
 
