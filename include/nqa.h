@@ -324,7 +324,7 @@ int nqa_adists_forward_group(const float *ref, const float *renders, int R, int 
                              float *d, float *s1, float *s2, void *stream);
 
 /* The window pass and the back part of nqa_adists_forward_group on their own, for tests and tools, through the launch
- * functions the group forward uses.
+ * functions the group forward uses (the pairwise forward's own, told the group size).
  *   nqa_adists_window_stage_group   nqa_adists_window_stage for R * K pairs: fx the R references' maps, fy the R * K
  *           renders' (pair r * K + k), q [8][R*K][C] per pair, wgt [R][C] per reference; gamma (R, H-20, W-20) per
  *           reference, tw / sw (R*K, H-20, W-20) per pair (the global branch: R and R * K values).  Dispatch, strip and
@@ -398,7 +398,7 @@ int nqa_adists_chain(const float *const *gamma, const float *const *tw, const fl
  * nqa_adists_forward runs for them, through the same launch functions, on the same grids, in the same order: the
  * statistics sums (the plane kernel on the images, the fused pool + statistics pass on taps 1..4 -- its pooled maps go to
  * the workspace and are discarded -- and the NHWC kernel on tap 5; the forward enqueues these between the layers of its
- * pyramid), then the preparation kernel, the images as NHWC4, the six entropy passes, their fold and the weights kernel
+ * pyramid), then the preparation kernel, the x images as NHWC4, the six entropy passes, their fold and the weights kernel
  * (ADISTS.py:127-135,150-161,166-167,176-180); the last five steps are one launch function shared with the forward.
  *   x, y    dev float32 NCHW (B,3,Hk[0],Wk[0]).
  *   taps    host array of five dev pointers, tap k = 1..5 at taps[k-1]: NHWC (2B,Hk[k],Wk[k],C_k), images x then y, in

@@ -47,6 +47,20 @@ __global__ __launch_bounds__(256) void nchw3_to_nhwc4_kernel(const float *__rest
 //   q[0]=inv_x  q[1]=inv_y   1/max(||f||_2, 1e-12)               (ADISTS.py:130,166-167)
 //   q[2]=sum_x               for the entropy normalisation       (:132)
 //   q[3..7]= mean_x mean_y var_x var_y cov of the RAW maps (population), for the global branch
+// s: the five sums of one (pair, channel) over hw pixels; o its place in a row of q, st the row length.
+__device__ inline void prep_store(const double (&s)[5], int hw, size_t o, size_t st, float *__restrict__ q) {
+  const double inv = 1.0 / (double)hw;
+  const double mx = s[0] * inv, my = s[1] * inv;
+  q[0 * st + o] = (float)(1.0 / fmax(sqrt(s[2]), 1e-12));
+  q[1 * st + o] = (float)(1.0 / fmax(sqrt(s[3]), 1e-12));
+  q[2 * st + o] = (float)s[0];
+  q[3 * st + o] = (float)mx;
+  q[4 * st + o] = (float)my;
+  q[5 * st + o] = (float)(s[2] * inv - mx * mx);
+  q[6 * st + o] = (float)(s[3] * inv - my * my);
+  q[7 * st + o] = (float)(s[4] * inv - mx * my);
+}
+
 __global__ __launch_bounds__(256) void adists_prep_kernel(const double *__restrict__ part, StageDesc d,
                                                           float *__restrict__ q /* [8][B][ctot] */, int B) {
   const int b = blockIdx.y;
@@ -60,17 +74,7 @@ __global__ __launch_bounds__(256) void adists_prep_kernel(const double *__restri
   for (int blk = 0; blk < d.nblk[k]; ++blk)
 #pragma unroll
     for (int j = 0; j < 5; ++j) s[j] += p[(size_t)blk * d.c[k] * 5 + j];
-  const double inv = 1.0 / (double)d.hw[k];
-  const double mx = s[0] * inv, my = s[1] * inv;
-  const size_t o = (size_t)b * d.ctot + gc, st = (size_t)B * d.ctot;
-  q[0 * st + o] = (float)(1.0 / fmax(sqrt(s[2]), 1e-12));
-  q[1 * st + o] = (float)(1.0 / fmax(sqrt(s[3]), 1e-12));
-  q[2 * st + o] = (float)s[0];
-  q[3 * st + o] = (float)mx;
-  q[4 * st + o] = (float)my;
-  q[5 * st + o] = (float)(s[2] * inv - mx * mx);
-  q[6 * st + o] = (float)(s[3] * inv - my * my);
-  q[7 * st + o] = (float)(s[4] * inv - mx * my);
+  prep_store(s, d.hw[k], (size_t)b * d.ctot + gc, (size_t)B * d.ctot, q);
 }
 
 // The same scalars for the group forward, one WAVE per (pair, channel): the group statistics kernels cut a tap into
@@ -94,17 +98,7 @@ __global__ __launch_bounds__(256) void adists_prep_group_kernel(const double *__
   for (int j = 0; j < 5; ++j)
     for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_down(s[j], off, 64);
   if (lane != 0) return;
-  const double inv = 1.0 / (double)d.hw[k];
-  const double mx = s[0] * inv, my = s[1] * inv;
-  const size_t o = (size_t)b * d.ctot + gc, st = (size_t)B * d.ctot;
-  q[0 * st + o] = (float)(1.0 / fmax(sqrt(s[2]), 1e-12));
-  q[1 * st + o] = (float)(1.0 / fmax(sqrt(s[3]), 1e-12));
-  q[2 * st + o] = (float)s[0];
-  q[3 * st + o] = (float)mx;
-  q[4 * st + o] = (float)my;
-  q[5 * st + o] = (float)(s[2] * inv - mx * mx);
-  q[6 * st + o] = (float)(s[3] * inv - my * my);
-  q[7 * st + o] = (float)(s[4] * inv - mx * my);
+  prep_store(s, d.hw[k], (size_t)b * d.ctot + gc, (size_t)B * d.ctot, q);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1033,11 +1027,19 @@ static Gauss make_gauss() {
   return g;
 }
 
+// Every host function below describes a call by three integers: X x-side images, B pairs, and K -- 0 for B independent
+// pairs (X = B, pair b reads x image b), > 0 for groups of K renders per reference (B = X * K, pair b reads x image
+// b / K).  What A-DISTS takes from x alone (entropy weights, gamma, the probability chain) is sized and launched by X,
+// what it takes from a pair (q, tw, sw, the D sums) by B.
+static const long kAdistsGroupMaxPairs = 65535;  // pairs ride a grid's y / z dimension (adists_prep_kernel, finalize)
+
 struct APlan {
-  // byte offsets into the workspace
-  size_t bufA, bufB, taps[5], img4x, img4y, part, q, ent, wgt, maps[NQA_NUM_TAPS][4], acc, chain_part, total;
-  StageDesc sd;
-  EntDesc ed;
+  // byte offsets into the workspace.  hsum, acc_pair and ones are areas of their own for groups; for pairs they alias
+  // q's row 2 (dead once the entropy passes have read sum_x), acc_x and bufB (the ping-pong buffers are free by then)
+  size_t bufA, bufB, taps[5], img4x, part, q, ent, hsum, wgt, maps[NQA_NUM_TAPS][4], acc_x, acc_pair, chain_part, ones,
+      total;
+  StageDesc sd;  // statistics partials of the B pairs in finalize's layout
+  EntDesc ed;    // entropy partials of the X x images
   int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS], c[NQA_NUM_TAPS];  // feature dims per tap (k=0 raw image)
   int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];                  // map dims (1x1 for the global branch)
   bool windowed[NQA_NUM_TAPS];
@@ -1065,17 +1067,20 @@ static void map_dims(const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], int m
 
 // The descriptors of the front part (statistics partials, entropy partials) for six taps of h[k] x w[k] x c[k]; doff and
 // eoff receive the doubles the two partial arrays hold.  make_plan and nqa_adists_front both size and launch by this.
-static void front_descs(int B, const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], const int c[NQA_NUM_TAPS], int prec,
-                        StageDesc &sd, EntDesc &ed, int ent_ppb[NQA_NUM_TAPS], long &doff, long &eoff) {
-  // statistics partials: stage 0 from the NCHW kernel, stages 1..5 from the NHWC kernel
+static void front_descs(int X, int B, int K, const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS],
+                        const int c[NQA_NUM_TAPS], int prec, StageDesc &sd, EntDesc &ed, int ent_ppb[NQA_NUM_TAPS],
+                        long &doff, long &eoff) {
+  // statistics partials of the B pairs: stage 0 from the plane kernel; stages 1..5 from the NHWC group kernel, or
+  // for pairs from the fused pool pass (taps 1..4, items = pooled pixels) and the NHWC kernel (tap 5)
   doff = 0;
   int coff = 0;
   for (int k = 0; k < 6; ++k) {
     const int hw = h[k] * w[k];
-    // taps 1..4 get their statistics inside the fused pool pass (items = pooled pixels)
     int nblk;
     if (k == 0)
       nblk = cdiv(hw, stats_nchw_ppb(hw));
+    else if (K > 0)
+      nblk = cdiv(hw, group_stats_units_per_block(hw, c[k], prec, X));
     else if (k <= 4)
       nblk = pool_stats_tiles((h[k] + 1) / 2, (w[k] + 1) / 2, c[k], prec, B, nullptr, nullptr);
     else
@@ -1090,53 +1095,63 @@ static void front_descs(int B, const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TA
   }
   sd.nstage = 6;
   sd.ctot = coff;
+  // entropy partials of the X x images
   eoff = 0;
   for (int k = 0; k < 6; ++k) {
     const int hw = h[k] * w[k];
     const int cpad = k == 0 ? 4 : c[k];
-    const int ppb = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, B);
+    const int ppb = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, X);
     ent_ppb[k] = ppb;
     ed.part_off[k] = eoff;
     ed.nblk[k] = cdiv(hw, ppb);
     ed.c[k] = cpad;
     ed.creal[k] = c[k];
     ed.coff[k] = sd.coff[k];
-    eoff += (long)B * ed.nblk[k] * cpad;
+    eoff += (long)X * ed.nblk[k] * cpad;
   }
   ed.ctot = coff;
 }
 
-static APlan make_plan(int B, int H, int W, int prec) {
+// The chain's cross-block partials: two moments per x image, then one D sum per pair, in the same area.
+static size_t chain_part_bytes(int X, int B) {
+  return (size_t)(2 * X > B ? 2 * X : B) * kChainBlocks * sizeof(double);
+}
+
+// One NHWC batch of n = X + B images (the x images first), all five taps kept.
+static APlan make_plan(int X, int B, int K, int H, int W, int prec) {
   APlan p;
   memset(&p, 0, sizeof(p));
   const size_t esz = prec_elem_bytes(prec);
+  const int n = X + B;
   tap_dims(H, W, p.h, p.w);
-  p.c[0] = 3;
-  for (int k = 1; k < 6; ++k) p.c[k] = kChns[k];
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) p.c[k] = kChns[k];
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
     off += align_up(bytes, 256);
     return o;
   };
-  const size_t act = (size_t)2 * B * max_act_elems(H, W) * esz;  // not H*W*64: tiny frames peak at a later stage
+  const size_t act = (size_t)n * max_act_elems(H, W) * esz;  // not H*W*64: tiny frames peak at a later stage
   p.bufA = take(act);
   p.bufB = take(act);
-  for (int k = 0; k < 5; ++k) p.taps[k] = take((size_t)2 * B * p.h[k + 1] * p.w[k + 1] * p.c[k + 1] * esz);
-  p.img4x = take((size_t)B * H * W * 4 * 4);
-  p.img4y = take((size_t)B * H * W * 4 * 4);
+  for (int k = 0; k < 5; ++k) p.taps[k] = take((size_t)n * p.h[k + 1] * p.w[k + 1] * p.c[k + 1] * esz);
+  p.img4x = take((size_t)X * H * W * 4 * 4);
   long doff, eoff;
-  front_descs(B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
+  front_descs(X, B, K, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
   const int coff = p.sd.ctot;
   p.part = take((size_t)doff * 8);
   p.q = take((size_t)8 * B * coff * 4);
   p.ent = take((size_t)eoff * 8);
-  p.wgt = take((size_t)B * coff * 4);
+  p.hsum = K > 0 ? take((size_t)X * coff * 4) : p.q + (size_t)2 * B * coff * 4;
+  p.wgt = take((size_t)X * coff * 4);
   map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
   for (int k = 0; k < 6; ++k)
-    for (int j = 0; j < 4; ++j) p.maps[k][j] = take((size_t)B * p.mh[k] * p.mw[k] * 4);
-  p.acc = take((size_t)6 * B * sizeof(ChainAcc));
-  p.chain_part = take((size_t)B * kChainBlocks * 2 * sizeof(double));
+    for (int j = 0; j < 4; ++j)  // gamma and ps_prod per x image, tw and sw per pair
+      p.maps[k][j] = take((size_t)(j == 0 || j == 3 ? X : B) * p.mh[k] * p.mw[k] * 4);
+  p.acc_x = take((size_t)6 * X * sizeof(ChainAcc));
+  p.acc_pair = K > 0 ? take((size_t)6 * B * sizeof(ChainAcc)) : p.acc_x;
+  p.chain_part = take(chain_part_bytes(X, B));
+  p.ones = K > 0 ? take((size_t)X * sizeof(float)) : p.bufB;
   p.total = off;
   return p;
 }
@@ -1264,6 +1279,25 @@ static const Gauss *checked_gauss(const char *who) {
   return &gauss;
 }
 
+// One stage of the heavy pass: the global branch for maps smaller than the window, the planar kernel for the image,
+// else the lanes pass in the taps' storage type.  fx holds the x-side maps, fy the B pairs' y maps.  The forward's
+// stage loop and the two single-stage entry points all dispatch here (`who` names the caller in a refusal).
+static int launch_window_stage(const char *who, const void *fx, const void *fy, int B, int K, int H, int W, int C,
+                               int prec, const float *q, int ctot, int coff, const float *wgt, float *gamma, float *tw,
+                               float *sw, hipStream_t st, int strip = 0) {
+  if (H < kWin || W < kWin) return launch_global(q, B, ctot, coff, C, wgt, gamma, tw, sw, st, K);
+  const Gauss *gp = checked_gauss(who);
+  if (!gp) return NQA_E_LAUNCH;
+  if (C == 3)
+    return launch_window_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, ctot, coff,
+                                wgt, *gp, gamma, tw, sw, st, K);
+  switch (storage_prec(prec)) {
+    case NQA_PREC_F32: return launch_window_lanes<PrecF32>(fx, fy, B, H, W, C, q, ctot, coff, wgt, *gp, gamma, tw, sw, st, strip, K);
+    case NQA_PREC_BF16: return launch_window_lanes<PrecBF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, *gp, gamma, tw, sw, st, strip, K);
+    default: return launch_window_lanes<PrecF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, *gp, gamma, tw, sw, st, strip, K);
+  }
+}
+
 }  // namespace nqa
 
 using namespace nqa;
@@ -1272,46 +1306,56 @@ extern "C" {
 
 size_t nqa_adists_workspace_bytes(int B, int H, int W, int prec) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return make_plan(B, H, W, prec).total;
+  return make_plan(B, B, 0, H, W, prec).total;
 }
 
 }  // extern "C"
 
 // The back part of the forward: the probability chain from the coarsest stage to the finest, the stages' D sums, D_b and,
-// with map_out, the as_map=True resampler.  adists_run and nqa_adists_chain both launch it through this function.
+// with map_out (pairs only), the as_map=True resampler.  The forwards and the two chain entry points all launch it
+// through this function.  The probability part (moments, fold, the two min / max passes, the global branch's sigmoid)
+// runs per x image; for groups chain_final_group_kernel / chain_global_group_kernel then take the K renders' D sums
+// against each reference's ps_prod.  The D fold and adists_d_kernel run over the pairs.
 struct ChainMaps {
-  const float *gamma[NQA_NUM_TAPS], *tw[NQA_NUM_TAPS], *sw[NQA_NUM_TAPS];  // (B, mh, mw) each
-  float *ps[NQA_NUM_TAPS];                                                 // ps_prod out, (B, mh, mw)
+  const float *gamma[NQA_NUM_TAPS], *tw[NQA_NUM_TAPS], *sw[NQA_NUM_TAPS];  // gamma (X, mh, mw); tw, sw (B, mh, mw)
+  float *ps[NQA_NUM_TAPS];                                                 // ps_prod out, (X, mh, mw)
   int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];
   bool windowed[NQA_NUM_TAPS];
 };
 
-static int launch_chain(const ChainMaps &m, int B, int H, int W, ChainAcc *acc /* [6][B] */,
-                        double *cp /* [B][kChainBlocks][2] */, float *ones /* [B] */, float *d_out, float *map_out,
+static int launch_chain(const ChainMaps &m, int X, int B, int K, int H, int W, ChainAcc *acc_x /* [6][X] */,
+                        ChainAcc *acc_pair /* [6][B]; acc_x itself for pairs */,
+                        double *cp /* chain_part_bytes(X, B) */, float *ones /* [X] */, float *d_out, float *map_out,
                         hipStream_t st) {
   int rc;
   {
     TimedLaunch t(NQA_K_ADISTS, st);
-    chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc, 6 * B);
+    chain_init_kernel<<<cdiv(6 * X, 256), 256, 0, st>>>(acc_x, 6 * X);
+    if (K > 0) chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc_pair, 6 * B);
     // initial ps_prod = ones (ADISTS.py:75): a 1x1 map of 1 upsamples to the same constant
-    ones_kernel<<<cdiv(B, 256), 256, 0, st>>>(ones, B);
+    ones_kernel<<<cdiv(X, 256), 256, 0, st>>>(ones, X);
     const float *prev = ones;
     int hp = 1, wp = 1;
     for (int k = 5; k >= 0; --k) {
       const float *gamma = m.gamma[k], *tw = m.tw[k], *sw = m.sw[k];
       float *psprod = m.ps[k];
-      ChainAcc *a = acc + (size_t)k * B;
+      ChainAcc *ax = acc_x + (size_t)k * X, *ap = acc_pair + (size_t)k * B;
       if (m.windowed[k]) {
         const int n = m.mh[k] * m.mw[k];
-        dim3 grid(min(cdiv(n, 256), kChainBlocks), B);
+        dim3 grid(min(cdiv(n, 256), kChainBlocks), X);
         chain_moments_kernel<<<grid, 256, 0, st>>>(gamma, n, cp);
-        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 2, 0, a);
-        chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, a);
-        chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, a);
-        chain_final_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, a, cp);
-        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, a);
+        chain_fold_kernel<<<X, 256, 0, st>>>(cp, grid.x, 2, 0, ax);
+        chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, ax);
+        chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, ax);
+        if (K > 0)
+          chain_final_group_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, ax, K, cp);
+        else
+          chain_final_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, ax, cp);
+        chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, ap);
+      } else if (K > 0) {
+        chain_global_group_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, ap, B, K);
       } else {
-        chain_global_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, a, B);
+        chain_global_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, ap, B);
       }
       prev = psprod;
       hp = m.mh[k];
@@ -1319,8 +1363,8 @@ static int launch_chain(const ChainMaps &m, int B, int H, int W, ChainAcc *acc /
     }
     DDesc dd;
     for (int k = 0; k < 6; ++k) dd.n[k] = m.mh[k] * m.mw[k];
-    adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc, dd, B, d_out);
-    if ((rc = check_launch("adists_chain"))) return rc;
+    adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc_pair, dd, B, d_out);
+    if ((rc = check_launch(K > 0 ? "adists_chain_group" : "adists_chain"))) return rc;
   }
   if (map_out) {
     MapDesc md;
@@ -1340,54 +1384,100 @@ static int launch_chain(const ChainMaps &m, int B, int H, int W, ChainAcc *acc /
 
 // The front part of the forward behind the statistics sums: from the fp64 partial sums `part` of the six taps (left by
 // stats_nchw, pool_stats and stats_nhwc) to the per-channel scalars q, the entropies of the x maps and the channel
-// weights.  adists_run and nqa_adists_front both launch it through this function.  h, w, c: the six taps' dims (k = 0 the
-// image); taps[k - 1]: tap k, 2B images (x then y).  On return q[2] holds hsum, the folded per-channel entropy.
-static int launch_front(const float *x, const float *y, void *const *taps, int B, const int h[NQA_NUM_TAPS],
+// weights.  The forwards and nqa_adists_front all launch it through this function.  h, w, c: the six taps' dims (k = 0
+// the image); taps[k - 1]: tap k, X + B images (the x images first).  The scalars are per pair -- for groups from
+// adists_prep_group_kernel, a wave per value --; the NHWC4 conversion, the six entropy passes, their fold and the
+// weights kernel run on the X x images alone.  x image i's inv_x / sum_x are those of its first pair: the entropy kernel
+// indexes its two rows by image * stride, and the stride handed over is max(K, 1) rows of q.  hsum [X][ctot] receives
+// the folded per-channel entropy; for pairs it is q's row 2, which is dead once the entropy kernels have run.
+static int launch_front(const float *x, void *const *taps, int X, int B, int K, const int h[NQA_NUM_TAPS],
                         const int w[NQA_NUM_TAPS], const int c[NQA_NUM_TAPS], int prec, const StageDesc &sd,
                         const EntDesc &ed, const int ent_ppb[NQA_NUM_TAPS], const double *part,
-                        float *q /* [8][B][ctot] */, float *img4x, float *img4y, double *ent, float *wgt, hipStream_t st) {
+                        float *q /* [8][B][ctot] */, float *img4x, double *ent, float *hsum, float *wgt /* [X][ctot] */,
+                        hipStream_t st) {
   const int ctot = sd.ctot, H = h[0], W = w[0];
   int rc;
   {
-    dim3 grid(cdiv(ctot, 256), B);
     TimedLaunch t(NQA_K_ADISTS, st);
-    adists_prep_kernel<<<grid, 256, 0, st>>>(part, sd, q, B);
-    if ((rc = check_launch("adists_prep"))) return rc;
+    if (K > 0)
+      adists_prep_group_kernel<<<dim3(cdiv(ctot, 4), B), 256, 0, st>>>(part, sd, q, B);
+    else
+      adists_prep_kernel<<<dim3(cdiv(ctot, 256), B), 256, 0, st>>>(part, sd, q, B);
+    if ((rc = check_launch(K > 0 ? "adists_prep_group" : "adists_prep"))) return rc;
   }
   {
-    dim3 grid(cdiv(H * W, 256), B);
+    dim3 grid(cdiv(H * W, 256), X);
     TimedLaunch t(NQA_K_ADISTS, st);
     nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(x, img4x, H * W);
-    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(y, img4y, H * W);
     if ((rc = check_launch("nchw3_to_nhwc4"))) return rc;
   }
   const size_t qst = (size_t)B * ctot;
+  const int stride = ctot * (K > 0 ? K : 1);  // floats of a q row between two x images' first pairs
   // stage 0's q/wgt rows are indexed with channel < 3; the NHWC4 kernels read index 3 too, which
   // is channel 0 of stage 1 in the concatenated vector -- harmless: its feature value is 0 (entropy
   // term 0) and the window kernel masks c >= creal.
-  if ((rc = launch_entropy<PrecF32>(img4x, B, H * W, 4, ent_ppb[0], q + 0 * qst + sd.coff[0], q + 2 * qst + sd.coff[0],
-                                    ctot, ent + ed.part_off[0], st)))
+  if ((rc = launch_entropy<PrecF32>(img4x, X, H * W, 4, ent_ppb[0], q + 0 * qst + sd.coff[0], q + 2 * qst + sd.coff[0],
+                                    stride, ent + ed.part_off[0], st)))
     return rc;
   for (int k = 1; k < 6; ++k) {
     const int hw = h[k] * w[k];
     const float *invx = q + 0 * qst + sd.coff[k], *sumx = q + 2 * qst + sd.coff[k];
     double *ep = ent + ed.part_off[k];
-    switch (storage_prec(prec)) {
-      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
-      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
-      default: rc = launch_entropy<PrecF16>(taps[k - 1], B, hw, c[k], ent_ppb[k], invx, sumx, ctot, ep, st); break;
+    switch (storage_prec(prec)) {  // (the x images are the first X of every tap)
+      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], X, hw, c[k], ent_ppb[k], invx, sumx, stride, ep, st); break;
+      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], X, hw, c[k], ent_ppb[k], invx, sumx, stride, ep, st); break;
+      default: rc = launch_entropy<PrecF16>(taps[k - 1], X, hw, c[k], ent_ppb[k], invx, sumx, stride, ep, st); break;
     }
     if (rc) return rc;
   }
   {
-    // hsum reuses the q[2] (sum_x) rows: they are dead once the entropy kernels have run
-    float *hsum = q + 2 * qst;
     TimedLaunch t(NQA_K_ADISTS, st);
-    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), B), 256, 0, st>>>(ent, ed, hsum);
-    adists_weights_kernel<<<B, 256, 0, st>>>(hsum, ed, wgt);
+    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), X), 256, 0, st>>>(ent, ed, hsum);
+    adists_weights_kernel<<<X, 256, 0, st>>>(hsum, ed, wgt);
     if ((rc = check_launch("adists_weights"))) return rc;
   }
   return NQA_OK;
+}
+
+// The forward behind the pyramid and its statistics sums, for both forms: per-pair scalars, the x images as NHWC4,
+// entropies and channel weights; the heavy pass (tw / sw per pair, gamma per x image); the probability chain per x
+// image, D per pair and, with map_out, the as_map=True resampler.  x: the X x images, y: the B y images; the
+// plan's five taps and `part` are complete on entry and nothing here writes them.
+static int adists_tail(const char *who, const float *x, const float *y, int X, int B, int K, const APlan &p, int prec,
+                       char *base, float *d_out, float *map_out, hipStream_t st) {
+  const size_t esz = prec_elem_bytes(prec);
+  const int ctot = p.sd.ctot, H = p.h[0], W = p.w[0];
+  float *q = reinterpret_cast<float *>(base + p.q);
+  float *wgt = reinterpret_cast<float *>(base + p.wgt);
+  void *taps[5];
+  for (int k = 0; k < 5; ++k) taps[k] = base + p.taps[k];
+  int rc;
+  if ((rc = launch_front(x, taps, X, B, K, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb,
+                         reinterpret_cast<const double *>(base + p.part), q, reinterpret_cast<float *>(base + p.img4x),
+                         reinterpret_cast<double *>(base + p.ent), reinterpret_cast<float *>(base + p.hsum), wgt, st)))
+    return rc;
+  ChainMaps cm;
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    float *gamma = reinterpret_cast<float *>(base + p.maps[k][0]);
+    float *tw = reinterpret_cast<float *>(base + p.maps[k][1]);
+    float *sw = reinterpret_cast<float *>(base + p.maps[k][2]);
+    cm.gamma[k] = gamma;
+    cm.tw[k] = tw;
+    cm.sw[k] = sw;
+    cm.ps[k] = reinterpret_cast<float *>(base + p.maps[k][3]);
+    cm.mh[k] = p.mh[k];
+    cm.mw[k] = p.mw[k];
+    cm.windowed[k] = p.windowed[k];
+    const void *fx = k == 0 ? static_cast<const void *>(x) : taps[k - 1];
+    const void *fy = k == 0 ? static_cast<const void *>(y)
+                            : static_cast<const char *>(taps[k - 1]) + (size_t)X * p.h[k] * p.w[k] * p.c[k] * esz;
+    if ((rc = launch_window_stage(who, fx, fy, B, K, p.h[k], p.w[k], p.c[k], prec, q, ctot, p.sd.coff[k], wgt, gamma, tw,
+                                  sw, st)))
+      return rc;
+  }
+  return launch_chain(cm, X, B, K, H, W, reinterpret_cast<ChainAcc *>(base + p.acc_x),
+                      reinterpret_cast<ChainAcc *>(base + p.acc_pair), reinterpret_cast<double *>(base + p.chain_part),
+                      reinterpret_cast<float *>(base + p.ones), d_out, map_out, st);
 }
 
 static int adists_run(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
@@ -1405,20 +1495,14 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
     set_error("adists_forward: image too large for 32-bit in-image byte offsets");
     return NQA_E_ARG;
   }
-  const APlan p = make_plan(B, H, W, prec);
+  const APlan p = make_plan(B, B, 0, H, W, prec);
   if (ws_bytes < p.total) {
     set_error("adists_forward: workspace %zu < %zu bytes", ws_bytes, p.total);
     return NQA_E_WORKSPACE;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   char *base = static_cast<char *>(ws);
-  const size_t esz = prec_elem_bytes(prec);
-  const int ctot = p.sd.ctot;
   double *part = reinterpret_cast<double *>(base + p.part);
-  float *q = reinterpret_cast<float *>(base + p.q);
-  double *ent = reinterpret_cast<double *>(base + p.ent);
-  float *wgt = reinterpret_cast<float *>(base + p.wgt);
-  ChainAcc *acc = reinterpret_cast<ChainAcc *>(base + p.acc);
   void *taps[5];
   for (int k = 0; k < 5; ++k) taps[k] = base + p.taps[k];
   int rc;
@@ -1439,61 +1523,25 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
   // ---- DISTS' S1 / S2 from the same sums (nqa_adists_dists_forward only).  `part` is complete here and nothing
   // below writes it: adists_prep_kernel reads it, hsum reuses rows of q, the chain's `ones` lives in bufB ----
   if (s1_out && (rc = finalize(part, p.sd, B, s1_out, s2_out, st))) return rc;
-  // ---- per-channel scalars, stage-0 images as NHWC4, entropies, channel weights ----
-  if ((rc = launch_front(x, y, taps, B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, part, q,
-                         reinterpret_cast<float *>(base + p.img4x), reinterpret_cast<float *>(base + p.img4y), ent, wgt, st)))
-    return rc;
-  // ---- heavy pass: gamma / TW / SW maps per stage ----
-  const Gauss *gp = checked_gauss("adists_forward");
-  if (!gp) return NQA_E_LAUNCH;
-  const Gauss &gauss = *gp;
-  for (int k = 0; k < 6; ++k) {
-    float *gamma = reinterpret_cast<float *>(base + p.maps[k][0]);
-    float *tw = reinterpret_cast<float *>(base + p.maps[k][1]);
-    float *sw = reinterpret_cast<float *>(base + p.maps[k][2]);
-    if (!p.windowed[k]) {
-      if ((rc = launch_global(q, B, ctot, p.sd.coff[k], p.c[k], wgt, gamma, tw, sw, st))) return rc;
-      continue;
-    }
-    if (k == 0) {
-      rc = launch_window_planar(x, y, B, H, W, q, ctot, 0, wgt, gauss, gamma, tw, sw, st);
-    } else {
-      const char *tx = static_cast<const char *>(taps[k - 1]);
-      const char *ty = tx + (size_t)B * p.h[k] * p.w[k] * p.c[k] * esz;
-      switch (storage_prec(prec)) {
-        case NQA_PREC_F32: rc = launch_window_lanes<PrecF32>(tx, ty, B, p.h[k], p.w[k], p.c[k], q, ctot, p.sd.coff[k], wgt, gauss, gamma, tw, sw, st); break;
-        case NQA_PREC_BF16: rc = launch_window_lanes<PrecBF16>(tx, ty, B, p.h[k], p.w[k], p.c[k], q, ctot, p.sd.coff[k], wgt, gauss, gamma, tw, sw, st); break;
-        default: rc = launch_window_lanes<PrecF16>(tx, ty, B, p.h[k], p.w[k], p.c[k], q, ctot, p.sd.coff[k], wgt, gauss, gamma, tw, sw, st); break;
-      }
-    }
-    if (rc) return rc;
-  }
-  // ---- probability chain, coarse to fine; D; the as_map=True resampler ----
-  ChainMaps cm;
-  for (int k = 0; k < 6; ++k) {
-    cm.gamma[k] = reinterpret_cast<const float *>(base + p.maps[k][0]);
-    cm.tw[k] = reinterpret_cast<const float *>(base + p.maps[k][1]);
-    cm.sw[k] = reinterpret_cast<const float *>(base + p.maps[k][2]);
-    cm.ps[k] = reinterpret_cast<float *>(base + p.maps[k][3]);
-    cm.mh[k] = p.mh[k];
-    cm.mw[k] = p.mw[k];
-    cm.windowed[k] = p.windowed[k];
-  }
-  // initial ps_prod = ones (ADISTS.py:75) lives in bufB: the ping-pong buffers are free now
-  return launch_chain(cm, B, H, W, acc, reinterpret_cast<double *>(base + p.chain_part),
-                      reinterpret_cast<float *>(base + p.bufB), d_out, map_out, st);
+  // ---- front, heavy pass, probability chain, D, the as_map=True resampler ----
+  return adists_tail("adists_forward", x, y, B, B, 0, p, prec, base, d_out, map_out, st);
 }
 
-// The back part on its own (include/nqa.h).  Workspace: ChainAcc[6][B], the chain's per-block partials, the B ones.
+// The back part on its own (include/nqa.h).  Workspace: ChainAcc[6][X], for groups ChainAcc[6][B], the chain's
+// per-block partials, the X ones.
 struct ChainPlan {
-  size_t acc, part, ones, total;
+  size_t acc_x, acc_pair, part, ones, total;
 };
-static ChainPlan chain_plan(int B) {
+static ChainPlan chain_plan(int X, int B, int K) {
   ChainPlan c;
-  c.acc = 0;
-  c.part = align_up((size_t)6 * B * sizeof(ChainAcc), 256);
-  c.ones = c.part + align_up((size_t)B * kChainBlocks * 2 * sizeof(double), 256);
-  c.total = c.ones + align_up((size_t)B * sizeof(float), 256);
+  c.acc_x = c.acc_pair = 0;
+  c.part = align_up((size_t)6 * X * sizeof(ChainAcc), 256);
+  if (K > 0) {
+    c.acc_pair = c.part;
+    c.part += align_up((size_t)6 * B * sizeof(ChainAcc), 256);
+  }
+  c.ones = c.part + align_up(chain_part_bytes(X, B), 256);
+  c.total = c.ones + align_up((size_t)X * sizeof(float), 256);
   return c;
 }
 static int chain_frame_check(const char *who, int B, int H, int W) {
@@ -1506,6 +1554,47 @@ static int chain_frame_check(const char *who, int B, int H, int W) {
     return NQA_E_ARG;
   }
   return NQA_OK;
+}
+// nqa_adists_chain (group false: X pairs, K ignored) and nqa_adists_chain_group (X references of K renders) behind
+// their argument lists: the refusals under the caller's name, then launch_chain on the caller's maps.
+static int chain_entry(const char *who, bool group, const float *const *gamma, const float *const *tw,
+                       const float *const *sw, int X, int K, int H, int W, void *ws, size_t ws_bytes,
+                       float *const *ps_prod, float *d, float *map, void *stream) {
+  if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
+    set_error("%s: null pointer", who);
+    return NQA_E_ARG;
+  }
+  for (int k = 0; k < NQA_NUM_TAPS; ++k)
+    if (!gamma[k] || !tw[k] || !sw[k] || !ps_prod[k]) {
+      set_error("%s: null pointer (stage %d)", who, k);
+      return NQA_E_ARG;
+    }
+  if (group && (X <= 0 || K <= 0 || (long)X * K > kAdistsGroupMaxPairs)) {
+    set_error("%s: bad group (R=%d K=%d; at most %ld pairs)", who, X, K, kAdistsGroupMaxPairs);
+    return NQA_E_ARG;
+  }
+  if (int rc = chain_frame_check(who, X, H, W)) return rc;
+  if (!group) K = 0;
+  const int B = group ? X * K : X;
+  const ChainPlan c = chain_plan(X, B, K);
+  if (ws_bytes < c.total) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, c.total);
+    return NQA_E_WORKSPACE;
+  }
+  ChainMaps cm;
+  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
+  tap_dims(H, W, h, w);
+  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
+  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
+    cm.gamma[k] = gamma[k];
+    cm.tw[k] = tw[k];
+    cm.sw[k] = sw[k];
+    cm.ps[k] = ps_prod[k];
+  }
+  char *base = static_cast<char *>(ws);
+  return launch_chain(cm, X, B, K, H, W, reinterpret_cast<ChainAcc *>(base + c.acc_x),
+                      reinterpret_cast<ChainAcc *>(base + c.acc_pair), reinterpret_cast<double *>(base + c.part),
+                      reinterpret_cast<float *>(base + c.ones), d, map, static_cast<hipStream_t>(stream));
 }
 
 extern "C" {
@@ -1527,49 +1616,22 @@ int nqa_adists_chain_dims(int H, int W, int *mh, int *mw) {
 
 size_t nqa_adists_chain_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return chain_plan(B).total;
+  return chain_plan(B, B, 0).total;
 }
 
 int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
                      void *ws, size_t ws_bytes, float *const *ps_prod, float *d, float *map, void *stream) {
-  if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
-    set_error("adists_chain: null pointer");
-    return NQA_E_ARG;
-  }
-  for (int k = 0; k < NQA_NUM_TAPS; ++k)
-    if (!gamma[k] || !tw[k] || !sw[k] || !ps_prod[k]) {
-      set_error("adists_chain: null pointer (stage %d)", k);
-      return NQA_E_ARG;
-    }
-  if (int rc = chain_frame_check("adists_chain", B, H, W)) return rc;
-  const ChainPlan c = chain_plan(B);
-  if (ws_bytes < c.total) {
-    set_error("adists_chain: workspace %zu < %zu bytes", ws_bytes, c.total);
-    return NQA_E_WORKSPACE;
-  }
-  ChainMaps cm;
-  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
-  tap_dims(H, W, h, w);
-  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
-  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
-    cm.gamma[k] = gamma[k];
-    cm.tw[k] = tw[k];
-    cm.sw[k] = sw[k];
-    cm.ps[k] = ps_prod[k];
-  }
-  char *base = static_cast<char *>(ws);
-  return launch_chain(cm, B, H, W, reinterpret_cast<ChainAcc *>(base + c.acc), reinterpret_cast<double *>(base + c.part),
-                      reinterpret_cast<float *>(base + c.ones), d, map, static_cast<hipStream_t>(stream));
+  return chain_entry("adists_chain", false, gamma, tw, sw, B, 0, H, W, ws, ws_bytes, ps_prod, d, map, stream);
 }
 
 }  // extern "C"
 
 // The front part on its own (include/nqa.h): the statistics launches that nqa_adists_forward interleaves with its
 // pyramid (stats_nchw, pool_stats per tap 1..4, stats_nhwc on tap 5: the same launch functions with the same arguments),
-// then launch_front.  The taps' sizes are the caller's.  Workspace: pool_stats' discarded pooled maps, the two NHWC4
-// images, the statistics partials, the entropy partials.
+// then launch_front.  The taps' sizes are the caller's.  Workspace: pool_stats' discarded pooled maps, the x images as
+// NHWC4, the statistics partials, the entropy partials.
 struct FrontPlan {
-  size_t pooled, img4x, img4y, part, ent, total;
+  size_t pooled, img4x, part, ent, total;
   StageDesc sd;
   EntDesc ed;
   int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS], c[NQA_NUM_TAPS], ent_ppb[NQA_NUM_TAPS];
@@ -1618,9 +1680,8 @@ static FrontPlan front_plan(int B, const int *Hk, const int *Wk, int prec) {
   }
   p.pooled = take(pooled);
   p.img4x = take((size_t)B * p.h[0] * p.w[0] * 4 * 4);
-  p.img4y = take((size_t)B * p.h[0] * p.w[0] * 4 * 4);
   long doff, eoff;
-  front_descs(B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
+  front_descs(B, B, 0, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, doff, eoff);
   p.part = take((size_t)doff * 8);
   p.ent = take((size_t)eoff * 8);
   p.total = off;
@@ -1680,9 +1741,9 @@ int nqa_adists_front(const float *x, const float *y, const void *const *taps, in
     if ((rc = pool_stats(tp[k - 1], B, p.h[k], p.w[k], p.c[k], prec, base + p.pooled, part + p.sd.part_off[k], st)))
       return rc;
   if ((rc = stats_nhwc(tp[4], B, p.h[5] * p.w[5], p.c[5], prec, part + p.sd.part_off[5], st))) return rc;
-  return launch_front(x, y, tp, B, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, part, q,
-                      reinterpret_cast<float *>(base + p.img4x), reinterpret_cast<float *>(base + p.img4y),
-                      reinterpret_cast<double *>(base + p.ent), wgt, st);
+  return launch_front(x, tp, B, B, 0, p.h, p.w, p.c, prec, p.sd, p.ed, p.ent_ppb, part, q,
+                      reinterpret_cast<float *>(base + p.img4x), reinterpret_cast<double *>(base + p.ent),
+                      q + (size_t)2 * B * p.sd.ctot, wgt, st);
 }
 
 }  // extern "C"
@@ -1730,18 +1791,8 @@ int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W,
     return NQA_E_ARG;
   }
   if (int rc = window_stage_check("adists_window_stage", B, H, W, C, prec, strip)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (H < kWin || W < kWin) return launch_global(q, B, C, 0, C, wgt, gamma, tw, sw, st);
-  const Gauss *gp = checked_gauss("adists_window_stage");
-  if (!gp) return NQA_E_LAUNCH;
-  if (C == 3)
-    return launch_window_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, C, 0, wgt,
-                                *gp, gamma, tw, sw, st);
-  switch (storage_prec(prec)) {
-    case NQA_PREC_F32: return launch_window_lanes<PrecF32>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
-    case NQA_PREC_BF16: return launch_window_lanes<PrecBF16>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
-    default: return launch_window_lanes<PrecF16>(fx, fy, B, H, W, C, q, C, 0, wgt, *gp, gamma, tw, sw, st, strip);
-  }
+  return launch_window_stage("adists_window_stage", fx, fy, B, 0, H, W, C, prec, q, C, 0, wgt, gamma, tw, sw,
+                             static_cast<hipStream_t>(stream), strip);
 }
 
 int nqa_adists_forward(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
@@ -1775,78 +1826,6 @@ int nqa_adists_dists_forward(const float *x, const float *y, int B, int H, int W
 // from x alone -- the reference's pyramid, its entropy weights, gamma and the probability chain -- runs once per
 // reference; the window pass and the D sums run per pair r * K + k against it.
 // ---------------------------------------------------------------------------------
-static const long kAdistsGroupMaxPairs = 65535;  // pairs ride a grid's y / z dimension (adists_prep_kernel, finalize)
-
-struct GroupPlan {
-  // byte offsets into the workspace
-  size_t bufA, bufB, taps[5], img4, part, q, ent, hsum, wgt, maps[NQA_NUM_TAPS][4], acc_ref, acc_pair, chain_part, ones,
-      total;
-  StageDesc sd;  // statistics partials in finalize's layout, B := R * K (the group statistics kernels' blocks)
-  EntDesc ed;    // entropy partials of the R references
-  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS], c[NQA_NUM_TAPS];
-  int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];
-  bool windowed[NQA_NUM_TAPS];
-  int ent_ppb[NQA_NUM_TAPS];
-};
-
-static GroupPlan make_group_plan(int R, int K, int H, int W, int prec) {
-  GroupPlan p;
-  memset(&p, 0, sizeof(p));
-  const size_t esz = prec_elem_bytes(prec);
-  const int B = R * K, n = R + B;
-  tap_dims(H, W, p.h, p.w);
-  for (int k = 0; k < NQA_NUM_TAPS; ++k) p.c[k] = kChns[k];
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += align_up(bytes, 256);
-    return o;
-  };
-  const size_t act = (size_t)n * max_act_elems(H, W) * esz;
-  p.bufA = take(act);
-  p.bufB = take(act);
-  for (int k = 0; k < 5; ++k) p.taps[k] = take((size_t)n * p.h[k + 1] * p.w[k + 1] * p.c[k + 1] * esz);
-  p.img4 = take((size_t)R * H * W * 4 * 4);
-  // the statistics partials as nqa_dists_forward_group lays them out: the plane kernel on the images, the NHWC group
-  // kernel on the five taps
-  long doff = 0, eoff = 0;
-  int coff = 0;
-  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
-    const int hw = p.h[k] * p.w[k];
-    p.sd.part_off[k] = doff;
-    p.sd.nblk[k] = k == 0 ? cdiv(hw, stats_nchw_ppb(hw)) : cdiv(hw, group_stats_units_per_block(hw, p.c[k], prec, R));
-    p.sd.hw[k] = hw;
-    p.sd.c[k] = p.c[k];
-    p.sd.coff[k] = coff;
-    doff += (long)B * p.sd.nblk[k] * p.c[k] * 5;
-    const int cpad = k == 0 ? 4 : p.c[k];
-    p.ent_ppb[k] = stats_units_per_block(hw, cpad, k == 0 ? NQA_PREC_F32 : prec, R);
-    p.ed.part_off[k] = eoff;
-    p.ed.nblk[k] = cdiv(hw, p.ent_ppb[k]);
-    p.ed.c[k] = cpad;
-    p.ed.creal[k] = p.c[k];
-    p.ed.coff[k] = coff;
-    eoff += (long)R * p.ed.nblk[k] * cpad;
-    coff += p.c[k];
-  }
-  p.sd.nstage = NQA_NUM_TAPS;
-  p.sd.ctot = p.ed.ctot = coff;
-  p.part = take((size_t)doff * 8);
-  p.q = take((size_t)8 * B * coff * 4);
-  p.ent = take((size_t)eoff * 8);
-  p.hsum = take((size_t)R * coff * 4);
-  p.wgt = take((size_t)R * coff * 4);
-  map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
-  for (int k = 0; k < NQA_NUM_TAPS; ++k)
-    for (int j = 0; j < 4; ++j)  // gamma and ps_prod per reference, tw and sw per pair
-      p.maps[k][j] = take((size_t)(j == 0 || j == 3 ? R : B) * p.mh[k] * p.mw[k] * 4);
-  p.acc_ref = take((size_t)6 * R * sizeof(ChainAcc));
-  p.acc_pair = take((size_t)6 * B * sizeof(ChainAcc));
-  p.chain_part = take((size_t)(2 * R > B ? 2 * R : B) * kChainBlocks * sizeof(double));
-  p.ones = take((size_t)R * sizeof(float));
-  p.total = off;
-  return p;
-}
 
 // NQA_OK if the group forward takes these arguments, else NQA_E_ARG with the error set under the caller's name
 static int group_args_check(const char *who, int R, int K, int H, int W, int prec) {
@@ -1870,128 +1849,12 @@ static int group_args_check(const char *who, int R, int K, int H, int W, int pre
   return NQA_OK;
 }
 
-// The front of the group forward behind the statistics sums: adists_prep_kernel's scalars for the R * K pairs (from
-// finalize's layout, which the group statistics kernels fill; a wave per value, adists_prep_group_kernel), then the NHWC4 conversion, the six entropy passes, their fold and the
-// weights kernel on the R REFERENCES alone.  Reference r's inv_x / sum_x are those of pair r * K: the entropy kernel
-// indexes its two rows by image * stride, and the stride handed over is K rows.
-static int launch_front_group(const float *ref, void *const *taps, int R, int K, const GroupPlan &p, int prec,
-                              const double *part, float *q /* [8][R*K][ctot] */, float *img4, double *ent,
-                              float *hsum /* [R][ctot] */, float *wgt /* [R][ctot] */, hipStream_t st) {
-  const int ctot = p.sd.ctot, H = p.h[0], W = p.w[0], B = R * K;
-  int rc;
-  {
-    dim3 grid(cdiv(ctot, 4), B);
-    TimedLaunch t(NQA_K_ADISTS, st);
-    adists_prep_group_kernel<<<grid, 256, 0, st>>>(part, p.sd, q, B);
-    if ((rc = check_launch("adists_prep_group"))) return rc;
-  }
-  {
-    dim3 grid(cdiv(H * W, 256), R);
-    TimedLaunch t(NQA_K_ADISTS, st);
-    nchw3_to_nhwc4_kernel<<<grid, 256, 0, st>>>(ref, img4, H * W);
-    if ((rc = check_launch("nchw3_to_nhwc4"))) return rc;
-  }
-  const size_t qst = (size_t)B * ctot;
-  const int stride = ctot * K;  // rows of q between two references' first pairs
-  if ((rc = launch_entropy<PrecF32>(img4, R, H * W, 4, p.ent_ppb[0], q + 0 * qst + p.sd.coff[0], q + 2 * qst + p.sd.coff[0],
-                                    stride, ent + p.ed.part_off[0], st)))
-    return rc;
-  for (int k = 1; k < NQA_NUM_TAPS; ++k) {
-    const int hw = p.h[k] * p.w[k];
-    const float *invx = q + 0 * qst + p.sd.coff[k], *sumx = q + 2 * qst + p.sd.coff[k];
-    double *ep = ent + p.ed.part_off[k];
-    switch (storage_prec(prec)) {  // (the references are the first R images of every tap)
-      case NQA_PREC_F32: rc = launch_entropy<PrecF32>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
-      case NQA_PREC_BF16: rc = launch_entropy<PrecBF16>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
-      default: rc = launch_entropy<PrecF16>(taps[k - 1], R, hw, p.c[k], p.ent_ppb[k], invx, sumx, stride, ep, st); break;
-    }
-    if (rc) return rc;
-  }
-  {
-    TimedLaunch t(NQA_K_ADISTS, st);
-    adists_entropy_fold_kernel<<<dim3(cdiv(ctot, 4), R), 256, 0, st>>>(ent, p.ed, hsum);
-    adists_weights_kernel<<<R, 256, 0, st>>>(hsum, p.ed, wgt);
-    if ((rc = check_launch("adists_weights"))) return rc;
-  }
-  return NQA_OK;
-}
-
-// One stage of the group window pass: fx the R references' maps, fy the R * K renders', dispatched as adists_run
-// dispatches a pair stage.  nqa_adists_forward_group and nqa_adists_window_stage_group both launch through it.
-static int launch_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
-                                     const float *q, int ctot, int coff, const float *wgt, const Gauss &g, float *gamma,
-                                     float *tw, float *sw, hipStream_t st, int strip = 0) {
-  const int B = R * K;
-  if (H < kWin || W < kWin) return launch_global(q, B, ctot, coff, C, wgt, gamma, tw, sw, st, K);
-  if (C == 3)
-    return launch_window_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, ctot, coff,
-                                wgt, g, gamma, tw, sw, st, K);
-  switch (storage_prec(prec)) {
-    case NQA_PREC_F32: return launch_window_lanes<PrecF32>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
-    case NQA_PREC_BF16: return launch_window_lanes<PrecBF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
-    default: return launch_window_lanes<PrecF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, g, gamma, tw, sw, st, strip, K);
-  }
-}
-
-// The back part of the group forward.  m.gamma and m.ps hold R maps per stage, m.tw and m.sw R * K.  The probability
-// part (moments, fold, the two min / max passes, the global branch's sigmoid) is launch_chain's with B := R; the group
-// kernels then take the K renders' D sums against each reference's ps_prod, and adists_d_kernel runs over the pairs.
-static int launch_chain_group(const ChainMaps &m, int R, int K, ChainAcc *acc_ref /* [6][R] */,
-                              ChainAcc *acc_pair /* [6][R*K] */, double *cp /* [max(2 R, R K)][kChainBlocks] */,
-                              float *ones /* [R] */, float *d_out, hipStream_t st) {
-  const int B = R * K;
-  TimedLaunch t(NQA_K_ADISTS, st);
-  chain_init_kernel<<<cdiv(6 * R, 256), 256, 0, st>>>(acc_ref, 6 * R);
-  chain_init_kernel<<<cdiv(6 * B, 256), 256, 0, st>>>(acc_pair, 6 * B);
-  ones_kernel<<<cdiv(R, 256), 256, 0, st>>>(ones, R);
-  const float *prev = ones;
-  int hp = 1, wp = 1;
-  for (int k = 5; k >= 0; --k) {
-    const float *gamma = m.gamma[k], *tw = m.tw[k], *sw = m.sw[k];
-    float *psprod = m.ps[k];
-    ChainAcc *ar = acc_ref + (size_t)k * R, *ap = acc_pair + (size_t)k * B;
-    if (m.windowed[k]) {
-      const int n = m.mh[k] * m.mw[k];
-      dim3 grid(min(cdiv(n, 256), kChainBlocks), R);
-      chain_moments_kernel<<<grid, 256, 0, st>>>(gamma, n, cp);
-      chain_fold_kernel<<<R, 256, 0, st>>>(cp, grid.x, 2, 0, ar);
-      chain_psminmax_kernel<<<grid, 256, 0, st>>>(gamma, n, ar);
-      chain_ppminmax_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, ar);
-      chain_final_group_kernel<<<grid, 256, 0, st>>>(gamma, m.mh[k], m.mw[k], prev, hp, wp, tw, sw, psprod, ar, K, cp);
-      chain_fold_kernel<<<B, 256, 0, st>>>(cp, grid.x, 1, 1, ap);
-    } else {
-      chain_global_group_kernel<<<cdiv(B, 256), 256, 0, st>>>(gamma, prev, hp * wp, tw, sw, psprod, ap, B, K);
-    }
-    prev = psprod;
-    hp = m.mh[k];
-    wp = m.mw[k];
-  }
-  DDesc dd;
-  for (int k = 0; k < 6; ++k) dd.n[k] = m.mh[k] * m.mw[k];
-  adists_d_kernel<<<cdiv(B, 256), 256, 0, st>>>(acc_pair, dd, B, d_out);
-  return check_launch("adists_chain_group");
-}
-
-struct ChainGroupPlan {
-  size_t acc_ref, acc_pair, part, ones, total;
-};
-static ChainGroupPlan chain_group_plan(int R, int K) {
-  const int B = R * K;
-  ChainGroupPlan c;
-  c.acc_ref = 0;
-  c.acc_pair = align_up((size_t)6 * R * sizeof(ChainAcc), 256);
-  c.part = c.acc_pair + align_up((size_t)6 * B * sizeof(ChainAcc), 256);
-  c.ones = c.part + align_up((size_t)(2 * R > B ? 2 * R : B) * kChainBlocks * sizeof(double), 256);
-  c.total = c.ones + align_up((size_t)R * sizeof(float), 256);
-  return c;
-}
-
 extern "C" {
 
 size_t nqa_adists_group_workspace_bytes(int R, int K, int H, int W, int prec) {
   if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs || !prec_valid(prec)) return 0;
   if ((long)H * W * 64 * (long)prec_elem_bytes(prec) >= (1L << 31)) return 0;
-  return make_group_plan(R, K, H, W, prec).total;
+  return make_plan(R, R * K, K, H, W, prec).total;
 }
 
 int nqa_adists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W, const void *packed,
@@ -2005,20 +1868,16 @@ int nqa_adists_forward_group(const float *ref, const float *renders, int R, int 
     return NQA_E_ARG;
   }
   if (int rc = group_args_check("adists_forward_group", R, K, H, W, prec)) return rc;
-  const GroupPlan p = make_group_plan(R, K, H, W, prec);
+  const int B = R * K, n = R + B;
+  const APlan p = make_plan(R, B, K, H, W, prec);
   if (ws_bytes < p.total) {
     set_error("adists_forward_group: workspace %zu < %zu bytes", ws_bytes, p.total);
     return NQA_E_WORKSPACE;
   }
-  const Gauss *gp = checked_gauss("adists_forward_group");
-  if (!gp) return NQA_E_LAUNCH;
   hipStream_t st = static_cast<hipStream_t>(stream);
   char *base = static_cast<char *>(ws);
   const size_t esz = prec_elem_bytes(prec);
-  const int B = R * K, n = R + B, ctot = p.sd.ctot;
   double *part = reinterpret_cast<double *>(base + p.part);
-  float *q = reinterpret_cast<float *>(base + p.q);
-  float *wgt = reinterpret_cast<float *>(base + p.wgt);
   void *taps[5];
   for (int k = 0; k < 5; ++k) taps[k] = base + p.taps[k];
   int rc;
@@ -2035,34 +1894,8 @@ int nqa_adists_forward_group(const float *ref, const float *renders, int R, int 
   if (rc) return rc;
   // ---- DISTS' S1 / S2 of the pairs from the same sums ----
   if (s1 && (rc = finalize(part, p.sd, B, s1, s2, st))) return rc;
-  // ---- per-pair scalars; NHWC4 images, entropies and channel weights of the references ----
-  if ((rc = launch_front_group(ref, taps, R, K, p, prec, part, q, reinterpret_cast<float *>(base + p.img4),
-                               reinterpret_cast<double *>(base + p.ent), reinterpret_cast<float *>(base + p.hsum), wgt, st)))
-    return rc;
-  // ---- heavy pass: tw / sw per pair, gamma per reference ----
-  ChainMaps cm;
-  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
-    float *gamma = reinterpret_cast<float *>(base + p.maps[k][0]);
-    float *tw = reinterpret_cast<float *>(base + p.maps[k][1]);
-    float *sw = reinterpret_cast<float *>(base + p.maps[k][2]);
-    cm.gamma[k] = gamma;
-    cm.tw[k] = tw;
-    cm.sw[k] = sw;
-    cm.ps[k] = reinterpret_cast<float *>(base + p.maps[k][3]);
-    cm.mh[k] = p.mh[k];
-    cm.mw[k] = p.mw[k];
-    cm.windowed[k] = p.windowed[k];
-    const void *fx = k == 0 ? static_cast<const void *>(ref) : taps[k - 1];
-    const void *fy = k == 0 ? static_cast<const void *>(renders)
-                            : static_cast<const char *>(taps[k - 1]) + (size_t)R * p.h[k] * p.w[k] * p.c[k] * esz;
-    if ((rc = launch_window_stage_group(fx, fy, R, K, p.h[k], p.w[k], p.c[k], prec, q, ctot, p.sd.coff[k], wgt, *gp, gamma,
-                                        tw, sw, st)))
-      return rc;
-  }
-  // ---- probability chain per reference, D per pair ----
-  return launch_chain_group(cm, R, K, reinterpret_cast<ChainAcc *>(base + p.acc_ref),
-                            reinterpret_cast<ChainAcc *>(base + p.acc_pair), reinterpret_cast<double *>(base + p.chain_part),
-                            reinterpret_cast<float *>(base + p.ones), d_out, st);
+  // ---- front on the references, heavy pass per pair, probability chain per reference, D per pair ----
+  return adists_tail("adists_forward_group", ref, renders, R, B, K, p, prec, base, d_out, nullptr, st);
 }
 
 int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
@@ -2077,52 +1910,18 @@ int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, 
     return NQA_E_ARG;
   }
   if (int rc = window_stage_check("adists_window_stage_group", R * K, H, W, C, prec, strip)) return rc;
-  const Gauss *gp = checked_gauss("adists_window_stage_group");
-  if (!gp) return NQA_E_LAUNCH;
-  return launch_window_stage_group(fx, fy, R, K, H, W, C, prec, q, C, 0, wgt, *gp, gamma, tw, sw,
-                                   static_cast<hipStream_t>(stream), strip);
+  return launch_window_stage("adists_window_stage_group", fx, fy, R * K, K, H, W, C, prec, q, C, 0, wgt, gamma, tw, sw,
+                             static_cast<hipStream_t>(stream), strip);
 }
 
 size_t nqa_adists_chain_group_bytes(int R, int K, int H, int W) {
   if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs) return 0;
-  return chain_group_plan(R, K).total;
+  return chain_plan(R, R * K, K).total;
 }
 
 int nqa_adists_chain_group(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K, int H,
                            int W, void *ws, size_t ws_bytes, float *const *ps_prod, float *d, void *stream) {
-  if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
-    set_error("adists_chain_group: null pointer");
-    return NQA_E_ARG;
-  }
-  for (int k = 0; k < NQA_NUM_TAPS; ++k)
-    if (!gamma[k] || !tw[k] || !sw[k] || !ps_prod[k]) {
-      set_error("adists_chain_group: null pointer (stage %d)", k);
-      return NQA_E_ARG;
-    }
-  if (R <= 0 || K <= 0 || (long)R * K > kAdistsGroupMaxPairs) {
-    set_error("adists_chain_group: bad group (R=%d K=%d; at most %ld pairs)", R, K, kAdistsGroupMaxPairs);
-    return NQA_E_ARG;
-  }
-  if (int rc = chain_frame_check("adists_chain_group", R, H, W)) return rc;
-  const ChainGroupPlan c = chain_group_plan(R, K);
-  if (ws_bytes < c.total) {
-    set_error("adists_chain_group: workspace %zu < %zu bytes", ws_bytes, c.total);
-    return NQA_E_WORKSPACE;
-  }
-  ChainMaps cm;
-  int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
-  tap_dims(H, W, h, w);
-  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
-  for (int k = 0; k < NQA_NUM_TAPS; ++k) {
-    cm.gamma[k] = gamma[k];
-    cm.tw[k] = tw[k];
-    cm.sw[k] = sw[k];
-    cm.ps[k] = ps_prod[k];
-  }
-  char *base = static_cast<char *>(ws);
-  return launch_chain_group(cm, R, K, reinterpret_cast<ChainAcc *>(base + c.acc_ref),
-                            reinterpret_cast<ChainAcc *>(base + c.acc_pair), reinterpret_cast<double *>(base + c.part),
-                            reinterpret_cast<float *>(base + c.ones), d, static_cast<hipStream_t>(stream));
+  return chain_entry("adists_chain_group", true, gamma, tw, sw, R, K, H, W, ws, ws_bytes, ps_prod, d, nullptr, stream);
 }
 
 }  // extern "C"

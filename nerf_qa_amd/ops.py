@@ -620,31 +620,12 @@ def adists_window_stage_group(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tenso
     (R,C); maps as adists_window_stage takes them.  Returns gamma (R, mh, mw) and tw, sw (R*K, mh, mw)."""
     p, strip = prec_id(prec), int(strip)
     dev = _need_cuda(fx, fy, q, wgt)
-    if p not in PREC_DTYPE:
-        raise ValueError(f"adists_window_stage_group: prec {p} is not one of the kernel-level modes")
-    if q.dim() != 3 or q.shape[0] != 8 or q.shape[2] not in CHNS or wgt.dim() != 2 or fx.dim() != 4 or fy.dim() != 4:
-        raise ValueError(f"adists_window_stage_group: expected q (8,R*K,C), wgt (R,C) and 4-d maps, got "
-                         f"{tuple(q.shape)} / {tuple(wgt.shape)} / {tuple(fx.shape)} / {tuple(fy.shape)}")
-    b, c, r = int(q.shape[1]), int(q.shape[2]), int(wgt.shape[0])
-    if r <= 0 or b % r:
-        raise ValueError(f"adists_window_stage_group: {b} pairs do not divide into {r} groups")
-    k = b // r
-    h, w = (int(fx.shape[2]), int(fx.shape[3])) if c == 3 else (int(fx.shape[1]), int(fx.shape[2]))
-    one = (3, h, w) if c == 3 else (h, w, c)
-    want = torch.float32 if c == 3 else PREC_DTYPE[p]
-    for name, t, sh, dt in (("fx", fx, (r,) + one, want), ("fy", fy, (b,) + one, want), ("q", q, (8, b, c), torch.float32),
-                            ("wgt", wgt, (r, c), torch.float32)):
-        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
-            raise ValueError(f"adists_window_stage_group: {name} must be contiguous {dt} {sh}, got {t.dtype} "
-                             f"{tuple(t.shape)}")
-    windowed = h >= WINDOW and w >= WINDOW
-    mh, mw = (h - WINDOW + 1, w - WINDOW + 1) if windowed else (1, 1)
-    if strip < 0 or (windowed and strip > mh):
-        raise ValueError(f"adists_window_stage_group: strip {strip} outside [0, {mh if windowed else 0}]")
-    gamma = torch.empty((r, mh, mw), dtype=torch.float32, device=dev)
-    tw = torch.empty((b, mh, mw), dtype=torch.float32, device=dev)
-    sw = torch.empty((b, mh, mw), dtype=torch.float32, device=dev)
-    _call(dev, lib().nqa_adists_window_stage_group, ptr(fx), ptr(fy), r, k, h, w, c, p, ptr(q), ptr(wgt), strip,
+    r = int(wgt.shape[0]) if wgt.dim() == 2 else 0
+    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip, "adists_window_stage_group", r)
+    gamma = torch.empty((r,) + shape[1:], dtype=torch.float32, device=dev)
+    tw = torch.empty(shape, dtype=torch.float32, device=dev)
+    sw = torch.empty(shape, dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_adists_window_stage_group, ptr(fx), ptr(fy), r, b // r, h, w, c, p, ptr(q), ptr(wgt), strip,
           ptr(gamma), ptr(tw), ptr(sw), stream_ptr(dev))
     return gamma, tw, sw
 
@@ -656,18 +637,8 @@ def adists_chain_group(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor]
     _chain_lists(gamma=gamma, tw=tw, sw=sw)
     dev = _need_cuda(*gamma, *tw, *sw)
     h, w = int(h), int(w)
-    if h <= 0 or w <= 0 or gamma[0].dim() != 3 or tw[0].dim() != 3 or gamma[0].shape[0] == 0 \
-            or tw[0].shape[0] % gamma[0].shape[0]:
-        raise ValueError(f"adists_chain_group: expected gamma (R, mh, mw) and tw (R*K, mh, mw), got "
-                         f"{tuple(gamma[0].shape)} / {tuple(tw[0].shape)}")
-    r, b = int(gamma[0].shape[0]), int(tw[0].shape[0])
-    dims, _ = adists_chain_dims(h, w)
-    for name, ts, n in (("gamma", gamma, r), ("tw", tw, b), ("sw", sw, b)):
-        for k, t in enumerate(ts):
-            sh = (n,) + dims[k]
-            if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"adists_chain_group: {name}[{k}] must be contiguous float32 {sh}, got {t.dtype} "
-                                 f"{tuple(t.shape)}")
+    r = int(gamma[0].shape[0]) if gamma[0].dim() == 3 else 0
+    b, dims = _chain_dims(gamma, tw, sw, h, w, "adists_chain_group", r)
     ps = [torch.empty((r,) + dm, dtype=torch.float32, device=dev) for dm in dims]
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     nbytes = lib().nqa_adists_chain_group_bytes(r, b // r, h, w)
@@ -678,32 +649,37 @@ def adists_chain_group(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor]
     return ps, d
 
 
-def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, p: int, strip: int):
-    """Every check of adists_window_stage on its inputs; (B, H, W, C, output shape).  C is q's: 3 means float32 NCHW
-    planes, anything else NHWC taps in prec's storage type."""
+def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, p: int, strip: int,
+                       who: str = "adists_window_stage", r: int | None = None):
+    """Every check of adists_window_stage (or, with the group count r, adists_window_stage_group) on its inputs;
+    (B, H, W, C, shape of a per-pair output map).  C is q's: 3 means float32 NCHW planes, anything else NHWC taps in
+    prec's storage type.  The x-side tensors (fx, wgt) have r rows, or B without r; the pair-side ones (fy, q) B."""
     if p not in PREC_DTYPE:
-        raise ValueError(f"adists_window_stage: prec {p} is not one of the kernel-level modes")
+        raise ValueError(f"{who}: prec {p} is not one of the kernel-level modes")
     if q.dim() != 3 or q.shape[0] != 8 or q.shape[2] not in CHNS:
-        raise ValueError(f"adists_window_stage: q must be (8, B, C) with C in {sorted(set(CHNS))}, got {tuple(q.shape)}")
+        raise ValueError(f"{who}: q must be (8, B, C) with C in {sorted(set(CHNS))}, got {tuple(q.shape)}")
     b, c = int(q.shape[1]), int(q.shape[2])
-    if fx.dim() != 4 or fx.shape != fy.shape or fx.numel() == 0:
-        raise ValueError(f"adists_window_stage: expected two non-empty 4-d taps of equal shape, got {tuple(fx.shape)} / "
+    nx = b if r is None else r
+    if nx <= 0 or b % nx:
+        raise ValueError(f"{who}: {b} pairs do not divide into {nx} groups")
+    if fx.dim() != 4 or fy.dim() != 4 or fx.shape[1:] != fy.shape[1:] or fx.numel() == 0:
+        raise ValueError(f"{who}: expected two non-empty 4-d taps of equal image shape, got {tuple(fx.shape)} / "
                          f"{tuple(fy.shape)}")
     if c == 3:
         h, w = int(fx.shape[2]), int(fx.shape[3])
-        shape, want = (b, 3, h, w), torch.float32
+        one, want = (3, h, w), torch.float32
     else:
         h, w = int(fx.shape[1]), int(fx.shape[2])
-        shape, want = (b, h, w, c), PREC_DTYPE[p]
-    for name, t, sh, dt in (("fx", fx, shape, want), ("fy", fy, shape, want), ("q", q, (8, b, c), torch.float32),
-                            ("wgt", wgt, (b, c), torch.float32)):
+        one, want = (h, w, c), PREC_DTYPE[p]
+    for name, t, sh, dt in (("fx", fx, (nx,) + one, want), ("fy", fy, (b,) + one, want),
+                            ("q", q, (8, b, c), torch.float32), ("wgt", wgt, (nx, c), torch.float32)):
         if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
-            raise ValueError(f"adists_window_stage: {name} must be contiguous {dt} {sh}, got {t.dtype} {tuple(t.shape)}"
+            raise ValueError(f"{who}: {name} must be contiguous {dt} {sh}, got {t.dtype} {tuple(t.shape)}"
                              f"{'' if t.is_contiguous() else ' (not contiguous)'}")
     windowed = h >= WINDOW and w >= WINDOW
     out = (b, h - WINDOW + 1, w - WINDOW + 1) if windowed else (b, 1, 1)
     if strip < 0 or (windowed and strip > out[1]):
-        raise ValueError(f"adists_window_stage: strip {strip} outside [0, {out[1] if windowed else 0}]")
+        raise ValueError(f"{who}: strip {strip} outside [0, {out[1] if windowed else 0}]")
     return b, h, w, c, out
 
 
@@ -757,20 +733,24 @@ def _chain_lists(**lists) -> None:
             raise ValueError(f"adists_chain: {name} must be a list of six tensors, one per stage")
 
 
-def _chain_dims(gamma, tw, sw, h: int, w: int):
-    """Every check of adists_chain on its inputs but their device; (B, [(mh, mw)] per stage)."""
+def _chain_dims(gamma, tw, sw, h: int, w: int, who: str = "adists_chain", r: int | None = None):
+    """Every check of adists_chain (or, with the group count r, adists_chain_group) on its inputs but their device;
+    (B, [(mh, mw)] per stage).  The x-side maps (gamma) have r rows, or B without r; the pair-side ones (tw, sw) B."""
     _chain_lists(gamma=gamma, tw=tw, sw=sw)
-    if gamma[0].dim() != 3 or gamma[0].shape[0] == 0:
-        raise ValueError(f"adists_chain: maps must be (B, mh, mw), got {tuple(gamma[0].shape)}")
+    if gamma[0].dim() != 3 or tw[0].dim() != 3 or gamma[0].shape[0] == 0:
+        raise ValueError(f"{who}: maps must be (B, mh, mw), got {tuple(gamma[0].shape)} / {tuple(tw[0].shape)}")
     if int(h) <= 0 or int(w) <= 0:
-        raise ValueError(f"adists_chain: bad frame size {h} x {w}")
-    b = int(gamma[0].shape[0])
+        raise ValueError(f"{who}: bad frame size {h} x {w}")
+    b = int(gamma[0].shape[0]) if r is None else int(tw[0].shape[0])
+    nx = b if r is None else r
+    if nx <= 0 or b % nx:
+        raise ValueError(f"{who}: {b} pairs do not divide into {nx} groups")
     dims, _ = adists_chain_dims(h, w)
-    for name, ts in (("gamma", gamma), ("tw", tw), ("sw", sw)):
+    for name, ts, n in (("gamma", gamma, nx), ("tw", tw, b), ("sw", sw, b)):
         for k, t in enumerate(ts):
-            sh = (b,) + dims[k]
+            sh = (n,) + dims[k]
             if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"adists_chain: {name}[{k}] must be contiguous float32 {sh}, got {t.dtype} "
+                raise ValueError(f"{who}: {name}[{k}] must be contiguous float32 {sh}, got {t.dtype} "
                                  f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
     return b, dims
 
