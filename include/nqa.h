@@ -584,6 +584,45 @@ int nqa_window_moments_forward(const float *x, const float *y, int P, int H, int
 int nqa_window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *g0, const float *g1,
                                 const float *g2, const float *g3, const float *g4, float *gx, float *gy, void *stream);
 
+/* ---- A-DISTS as a loss with the gradient on y alone (nerf_qa_amd/autograd.py, adists_backward_y;
+ * nqa_adists_backward.hip): ONE stage of the head's backward.  With x fixed, the texture probabilities and the channel
+ * weights are constants, and only the T / S terms (ADISTS.py:165-183) and F.normalize of y (:167) are differentiated.
+ *   x, y    dev float32 planar maps (B, C, H, W): the image pair (C = 3) or a tap pair converted to NCHW.
+ *   q, wgt  dev float32 [8][B][ctot] and [B][ctot] as nqa_adists_front leaves them; the stage's C channels start at
+ *           column coff (ctot = C, coff = 0 for a slice made for nqa_adists_window_stage).  Rows 0, 1: a_x, a_y =
+ *           1 / max(||.||_2, 1e-12) of the raw maps; rows 3..7 (global branch only): mean_x mean_y var_x var_y cov.
+ *   ps      dev float32 (B, mh, mw): ps_prod of the stage as nqa_adists_chain writes it, mh x mw = (H-20) x (W-20), or
+ *           1 x 1 for the global branch.
+ *   u       dev float32 (B): u_b = dL/dD_b (for 1 - mean(D): -upstream / B).
+ *   mask    != 0: gy is multiplied by the map's own ReLU mask (y > 0), so a dead channel gets exactly 0 (taps); 0: not
+ *           (the image).
+ *   gy      dev float32, dL/dy: planar (B, C, H, W), or with out_nhwc != 0 NHWC (B, H, W, C).
+ * Arithmetic, with N = mh * mw and eps = 1e-6.  Windowed stage (H, W >= 21): from the raw window means m_x, m_y, m_xx,
+ * m_yy, m_xy of nqa_window_moments_forward,
+ *     xm = a_x m_x, ym = a_y m_y, xv = a_x^2 m_xx - xm^2, yv = a_y^2 m_yy - ym^2, cov = a_x a_y m_xy - xm ym,
+ *     T = (2 xm ym + eps) / (xm^2 + ym^2 + eps), S = (2 cov + eps) / (xv + yv + eps),
+ *     A = u_b w_c (1 - p) / N, Bc = u_b w_c p / N,
+ *     dT/dym = (2 xm - 2 ym T) / (xm^2 + ym^2 + eps), dS/dcov = 2 / (xv + yv + eps), dS/dyv = -S / (xv + yv + eps),
+ *     G_ym = A dT/dym - Bc (xm dS/dcov + 2 ym dS/dyv), G_yy = Bc dS/dyv, G_xy = Bc dS/dcov,
+ *     g1 = a_y G_ym, g3 = a_y^2 G_yy, g4 = a_x a_y G_xy   (fp64 on the float moments, rounded to float once),
+ *     P = W^T g1 + 2 y W^T g3 + x W^T g4                    (nqa_window_moments_backward's gy with gx null),
+ *     gy = P - y a_y^2 <P, y>, or P alone where ||y|| < 1e-12 (torch's clamp in F.normalize), times the mask.
+ * <P, y> is the sum over the plane, accumulated in fp64 from per-block partials folded in a fixed order.  Global stage
+ * (H or W under 21): the same with plain means over H * W from q rows 3..7 (xv = a_x^2 var_x, ...), N = 1, one p per pair,
+ * P(r) = (g1 + 2 y(r) g3 + x(r) g4) / (H W).  One writer per element, no atomics: bitwise repeatable; no pair reads
+ * another pair's numbers; nothing is read back to the host.  Launches are counted as NQA_K_ADISTS.
+ * Workspace: nqa_adists_ts_backward_bytes(B, C, H, W) (0 for sizes that are refused): the five moment maps, P and the
+ * fp64 partials; 16-byte aligned.
+ * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, coff < 0 or coff + C > ctot, more
+ * than 65535 pairs, a misaligned workspace, or -- on a windowed stage with W % 4 == 0, where rows move as 16-byte
+ * accesses -- x, y, ps or gy not 16-byte aligned; NQA_E_SHAPE H > 2^20, more than 2^30 pixels per plane, more than 2^31
+ * blocks in a launch, or out_nhwc on a windowed stage with C % 32 != 0; NQA_E_WORKSPACE a short workspace (checked
+ * last). */
+size_t nqa_adists_ts_backward_bytes(int B, int C, int H, int W);
+int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
+                           int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *workspace,
+                           size_t workspace_bytes, float *gy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,9 @@ as_loss=True in the reference runs the pyramids WITH autograd (:139-141).  Here,
 on and x or y requires grad), the tapped maps come from autograd.PyramidTaps (HIP forward, HIP backward through the 13 conv
 layers in f32s, as for DISTS(require_grad=True)) and the head -- texture probabilities, entropy weights, windowed T / S -- is
 evaluated in torch operations on the GPU (ADISTS/head.py) so that autograd differentiates it; the value returned is still the
-fused kernel's.  Otherwise the value 1-mean(D) comes from the fused kernel alone (there is no graph to lose).  No script of
+fused kernel's.  With the gradient on y alone (x the fixed frame: the training-loss use) and loss_head="auto" the head's
+backward is HIP as well (autograd.AdistsLossY, csrc/nqa_adists_backward.hip): no torch head, no graph over maps, no host
+read.  Otherwise the value 1-mean(D) comes from the fused kernel alone (there is no graph to lose).  No script of
 the reference calls it with a gradient (prep.py:186, test2_prep.py:151 pass as_loss=False).  as_map=True returns the
 reference's [B,B,H,W] distortion map (:163,188-193) from one extra kernel.
 """
@@ -49,13 +51,27 @@ from ..vgg_weights import load_vgg16_convs
 # (profiles/r02_stress_final.txt), and tools/gpu_stress.py now re-checks that with both conv1_1 forms.
 DEFAULT_PRECISION = "auto"
 AUTO_EXACT_PIXELS = 128 * 128
-TWO_STREAM_MIN_PAIRS = 4          # batches of this many pairs or more ...
+# The head of the loss path (as_loss=True under autograd).  "auto": the one-sided HIP backward (autograd.AdistsLossY)
+# where only y requires grad -- a render optimised against a fixed frame x -- and the torch head (ADISTS/head.py)
+# wherever x requires grad; "torch": the torch head for every case.  NQA_ADISTS_LOSS_HEAD sets the default.
+DEFAULT_LOSS_HEAD = "auto"
+LOSS_HEADS = ("auto", "torch")
+
+
+def _check_loss_head(v):
+    if v not in LOSS_HEADS:
+        raise ValueError(f"loss_head must be one of {LOSS_HEADS}, got {v!r}")
+    return v
+
+
+TWO_STREAM_MIN_PAIRS = 4         # batches of this many pairs or more ...
 TWO_STREAM_MIN_PIXELS = 512 * 512  # ... of frames this large run as two half-batches on two HIP streams (_score)
 
 
 class ADISTS(torch.nn.Module):
-    def __init__(self, window_size=21, precision=None, vgg16_path=None):
+    def __init__(self, window_size=21, precision=None, vgg16_path=None, loss_head=None):
         super().__init__()
+        self.loss_head = _check_loss_head(loss_head or os.environ.get("NQA_ADISTS_LOSS_HEAD", DEFAULT_LOSS_HEAD))
         if window_size != 21:
             raise NotImplementedError("the HIP windowed-statistics kernel is built for the 21x21 window "
                                       "the reference always uses")
@@ -123,6 +139,7 @@ class ADISTS(torch.nn.Module):
         d = self.__dict__
         d.setdefault("precision", os.environ.get("NQA_ADISTS_PRECISION", DEFAULT_PRECISION))
         d.setdefault("vgg_source", "unpickled module (Conv2d weights of stage1..5)")
+        d.setdefault("loss_head", _check_loss_head(os.environ.get("NQA_ADISTS_LOSS_HEAD", DEFAULT_LOSS_HEAD)))
         d.pop("_packed_key", None)
         d["_packed"], d["_ws"], d["_side"] = {}, ops.Workspace(), {}
 
@@ -162,9 +179,15 @@ class ADISTS(torch.nn.Module):
         """1 - mean(D) WITH its gradient towards x and y (ADISTS.py:139-141, 195).  The tapped maps come from
         autograd.PyramidTaps (HIP forward; HIP backward through the conv stack in f32s), the head is head.adists_d in
         torch operations, which autograd differentiates.  The VALUE returned is the scoring path's own (the fused
-        kernel, same precision policy as as_loss=False), with the torch expression's gradient attached."""
+        kernel, same precision policy as as_loss=False), with the torch expression's gradient attached.
+
+        With the gradient on y alone (x the fixed ground-truth frame, prep.py:186) and loss_head "auto" there is no
+        torch head and no autograd graph over maps: autograd.AdistsLossY returns the same value and its backward is
+        autograd.adists_backward_y, HIP from end to end, without a device -> host read."""
         from .. import autograd
         from . import head
+        if self.loss_head != "torch" and y.requires_grad and not x.requires_grad:
+            return autograd.AdistsLossY.apply(x, y, self)
         tx = autograd.PyramidTaps.apply(x, self) if x.requires_grad else self._taps_nograd(x)
         ty = autograd.PyramidTaps.apply(y, self) if y.requires_grad else self._taps_nograd(y)
         d = head.adists_d([x.float()] + list(tx), [y.float()] + list(ty), self.window_size)

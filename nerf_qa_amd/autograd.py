@@ -15,6 +15,9 @@ path: only the images that need a gradient are walked back, the statistics' grad
 renormalisation are HIP (csrc/nqa_loss_backward.hip, the scaled kernels of csrc/nqa_backward.hip) with per-image exponents
 in device memory, and nothing is read back to the host.  pyramid_backward and _stats_grad are the first form: the
 reference the tests pin, A-DISTS' head, and the baseline of tools/gpu_loss_step_bench.py.
+
+A-DISTS as a loss with the gradient on y alone (x the fixed frame) has the same kind of path: AdistsLossY /
+adists_backward_y, the head's backward in csrc/nqa_adists_backward.hip on top of the scoring path's staged entry points.
 """
 from __future__ import annotations
 
@@ -260,6 +263,76 @@ def dists_backward(module, x, y, g1, g2, need=(True, True), host_scaled=False):
     if need[0] and need[1]:
         return gimg[:b] + gx0, gimg[b:] + gy0
     return (gimg + gx0, None) if need[0] else (None, gimg + gy0)
+
+
+def _adists_y_bytes(b, h, w):
+    """Device bytes adists_backward_y holds beside the pyramid for b pairs of h x w frames at its largest stage (relu1_2:
+    the two planar copies of the taps, the NHWC gradient and the stage's workspace)."""
+    return 3 * b * 64 * h * w * 4 + int(ops.lib().nqa_adists_ts_backward_bytes(b, 64, h, w))
+
+
+@torch.no_grad()
+def adists_backward_y(module, x, y, u):
+    """dL/dy (B,3,H,W) of a loss over A-DISTS' D_b with dL/dD = u (B,) on the device, for a FIXED x: the one-sided loss
+    path of ADISTS.forward (a render y optimised against a ground-truth frame x, the reference's own argument order,
+    prep.py:186).  HIP from end to end and without one device -> host read: x gives its taps (pyramid_taps) and, through
+    the scoring path's staged entry points, q, the channel weights and the probability chain ps_prod -- constants here;
+    y's pyramid is kept (pyramid_keep), every stage's T / S terms and y's normalisation are differentiated by
+    csrc/nqa_adists_backward.hip (ops.adists_ts_backward, ReLU masks folded in, gradients written as NHWC) and the five tap
+    gradients go down pyramid_backward_device.  Bitwise repeatable; a pair's gradient does not depend on the rest of
+    the batch.  Batches whose scratch would pass NQA_MAX_WORKSPACE_GB run in slices of pairs."""
+    x, y, u = x.float().contiguous(), y.float().contiguous(), ops._f32c(u)
+    b, _, h, w = x.shape
+    n = ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b)
+    if n < b:
+        return torch.cat([adists_backward_y(module, x[i:i + n], y[i:i + n], u[i:i + n]) for i in range(0, b, n)])
+    prec, dev, ws = "f32s", x.device, module._ws
+    tx = pyramid_taps(module, x)
+    acts, ty, pooled = pyramid_keep(module, y)
+    # ---- what the head takes from x alone, and the per-channel scalars of both: the forward's own kernels ----
+    q = torch.empty((8, b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
+    wgt = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
+    ops.adists_front_into(x, y, [torch.cat([a, c]) for a, c in zip(tx, ty)], prec, q, wgt, ws)
+    dims, _ = ops.adists_chain_dims(h, w)
+    maps = [torch.empty((4, b) + d, dtype=torch.float32, device=dev) for d in dims]  # gamma, tw, sw, ps_prod per stage
+    off = 0
+    for k, c in enumerate(ops.CHNS):
+        fx, fy = (x, y) if k == 0 else (tx[k - 1], ty[k - 1])
+        ops.adists_window_stage_into(fx, fy, q[:, :, off:off + c].contiguous(), wgt[:, off:off + c].contiguous(), prec, 0,
+                                     maps[k][0], maps[k][1], maps[k][2])
+        off += c
+    d = torch.empty((b,), dtype=torch.float32, device=dev)
+    ops.adists_chain_into([m[0] for m in maps], [m[1] for m in maps], [m[2] for m in maps], h, w, [m[3] for m in maps], d,
+                          None, ws)
+    # ---- the six stages' gradients towards y's maps ----
+    g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws)
+    off, g_taps = 3, []
+    for k in range(1, 6):
+        px, py = ops.nhwc_to_nchw_f32(tx[k - 1], prec), ops.nhwc_to_nchw_f32(ty[k - 1], prec)
+        g_taps.append(ops.adists_ts_backward(px, py, q, wgt, maps[k][3], u, mask=True, coff=off, nhwc=True, ws=ws))
+        off += ops.CHNS[k]
+    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + g0
+
+
+class AdistsLossY(torch.autograd.Function):
+    """(x fixed, y) -> 1 - mean(D) of A-DISTS, differentiable in y alone.  The value is the scoring path's own (the fused
+    kernel, ADISTS._score); x and y are all that is saved; the backward is adists_backward_y with u = -grad / B formed on
+    the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, module):
+        ctx.module = module
+        ctx.save_for_backward(x, y)
+        return 1 - module._score(x, y, module.precision_for(x.shape[-2], x.shape[-1])).mean()
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, y = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        b = x.shape[0]
+        u = (grad.detach().float().reshape(1) * (-1.0 / b)).expand(b).contiguous()
+        return None, adists_backward_y(ctx.module, x, y, u).to(y.dtype), None
 
 
 class PyramidTaps(torch.autograd.Function):

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
 SOURCES = ["nqa_api.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_group_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
-           "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_window_moments.hip"]
+           "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_window_moments.hip",
+           "nqa_adists_backward.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]  # the remarks are parsed below: no hand-scheduled kernel may spill
@@ -27,7 +28,9 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_igemm_mixed_kernel", "conv3x3_reg
               "absmax_partial_kernel", "exponent_finish_kernel", "relu_mask_split16_kernel", "l2pool_backward_kernel",
               "conv1_1_backward_kernel", "window_moments_fwd_kernel", "window_moments_bwd_kernel",
               "group_stats_nhwc_kernel", "group_stats_nchw_kernel",
-              "adists_window_lds_group_kernel", "adists_window_planar_group_kernel")
+              "adists_window_lds_group_kernel", "adists_window_planar_group_kernel",
+              "adists_ts_coef_kernel", "adists_ts_dot_kernel", "adists_ts_fold_kernel", "adists_ts_apply_kernel",
+              "adists_ts_apply_nhwc_kernel", "adists_ts_global_kernel")
 
 
 def parse_resource_remarks(text: str) -> dict:

@@ -1396,4 +1396,57 @@ int nqa_window_moments_backward(const float *x, const float *y, int P, int H, in
   return window_moments_backward(x, y, P, H, W, g, gx, gy, static_cast<hipStream_t>(stream));
 }
 
+// ---- one stage of the A-DISTS head's backward towards y (nqa_adists_backward.hip) ------------------------------------
+// The refusals that depend on sizes alone; quiet for the _bytes query.
+static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, int coff, int out_nhwc) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ctot <= 0 || coff < 0 || (long)coff + C > ctot || B > 65535) {
+    if (who)
+      set_error("%s: bad argument (B %d, C %d, H %d, W %d, ctot %d, coff %d: non-positive size, channels outside q, or "
+                "more than 65535 pairs)", who, B, C, H, W, ctot, coff);
+    return NQA_E_ARG;
+  }
+  if (H > (1 << 20) || (long)H * W > (1L << 30)) {
+    if (who) set_error("%s: %d x %d: H > 2^20 or more than 2^30 pixels per plane", who, H, W);
+    return NQA_E_SHAPE;
+  }
+  if (!adists_ts_backward_fits(B, C, H, W)) {
+    if (who) set_error("%s: %d planes of %d x %d need more than 2^31 blocks in one launch (slice the batch)", who, B * C, H, W);
+    return NQA_E_SHAPE;
+  }
+  if (out_nhwc && H >= 21 && W >= 21 && C % 32) {
+    if (who) set_error("%s: an NHWC gradient of a windowed stage needs C %% 32 == 0, got C %d", who, C);
+    return NQA_E_SHAPE;
+  }
+  return 0;
+}
+
+size_t nqa_adists_ts_backward_bytes(int B, int C, int H, int W) {
+  if (ts_bad_sizes(nullptr, B, C, H, W, C, 0, 0)) return 0;
+  return adists_ts_backward_bytes(B, C, H, W);
+}
+
+int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
+                           int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *workspace,
+                           size_t workspace_bytes, float *gy, void *stream) {
+  if (!x || !y || !q || !wgt || !ps || !u || !workspace || !gy) {
+    set_error("adists_ts_backward: bad argument (null pointer)");
+    return NQA_E_ARG;
+  }
+  if (int rc = ts_bad_sizes("adists_ts_backward", B, C, H, W, ctot, coff, out_nhwc)) return rc;
+  // the windowed stage runs the planar window-moments kernels and inherits their rule; the workspace holds doubles
+  const bool rows16 = W % 4 == 0 && H >= 21 && W >= 21;
+  if (((uintptr_t)workspace & 15) ||
+      (rows16 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ps | (uintptr_t)gy) & 15))) {
+    set_error("adists_ts_backward: the workspace, and with W %d a multiple of 4 the maps, must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  const size_t need = adists_ts_backward_bytes(B, C, H, W);
+  if (workspace_bytes < need) {
+    set_error("adists_ts_backward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return adists_ts_backward(x, y, B, C, H, W, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0, workspace, gy,
+                            static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -311,6 +311,14 @@ int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp
 int window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st);
 int window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
                             float *gy, hipStream_t st);
+// ---- one stage of the A-DISTS head's backward towards y (nqa_adists_backward.hip) ----
+// planar float maps (B, C, H, W); q [8][B][ctot] and wgt [B][ctot] with the stage's channels at coff; ps (B, mh, mw);
+// u (B) = dL/dD; gy planar, or NHWC (B, H, W, C) with out_nhwc (C % 32 == 0 on a windowed stage)
+bool adists_ts_backward_fits(int B, int C, int H, int W);
+size_t adists_ts_backward_bytes(int B, int C, int H, int W);
+int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
+                       int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *ws, float *gy,
+                       hipStream_t st);
 int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off,
                           int relu, void *out, hipStream_t st);
 int l2pool_to_split16(const void *in_f16, int n, int H, int W, int C, void *out_split16, hipStream_t st);

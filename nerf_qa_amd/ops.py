@@ -1138,3 +1138,39 @@ def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequ
           *[None if g is None else ptr(g) for g in g5], None if gx is None else ptr(gx), None if gy is None else ptr(gy),
           stream_ptr(dev))
     return gx, gy
+
+
+# ---- one stage of the A-DISTS head's backward towards y (include/nqa.h, nqa_adists_backward.hip) ------------------
+def adists_ts_backward(x: torch.Tensor, y: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, ps: torch.Tensor,
+                       u: torch.Tensor, mask: bool, coff: int = 0, nhwc: bool = False, ws: Workspace | None = None,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """dL/dy of one A-DISTS stage with x fixed (include/nqa.h, nqa_adists_ts_backward): x, y float32 planar maps
+    (B,C,H,W); q (8,B,ctot) and wgt (B,ctot) as adists_front leaves them, the stage's channels at columns coff .. coff+C;
+    ps (B,mh,mw) the stage's ps_prod of adists_chain; u (B,) = dL/dD.  mask: times the ReLU mask (y > 0).  Returns the
+    gradient planar (B,C,H,W), or NHWC (B,H,W,C) with nhwc=True (what pyramid_backward_device takes)."""
+    dev = _need_cuda(x, y, q, wgt, ps, u)
+    for t in (x, y):
+        if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError(f"adists_ts_backward: expected non-empty contiguous float32 NCHW maps, got {t.dtype} {tuple(t.shape)}")
+    if y.shape != x.shape:
+        raise ValueError(f"adists_ts_backward: x {tuple(x.shape)} and y {tuple(y.shape)} differ")
+    b, c, h, w = (int(v) for v in x.shape)
+    coff = int(coff)
+    if q.dim() != 3 or q.shape[0] != 8 or q.shape[1] != b or coff < 0 or coff + c > q.shape[2]:
+        raise ValueError(f"adists_ts_backward: q must be (8, {b}, ctot) with columns {coff} .. {coff + c} inside, got {tuple(q.shape)}")
+    ctot = int(q.shape[2])
+    windowed = h >= WINDOW and w >= WINDOW
+    mshape = (b, h - WINDOW + 1, w - WINDOW + 1) if windowed else (b, 1, 1)
+    for name, t, sh in (("q", q, (8, b, ctot)), ("wgt", wgt, (b, ctot)), ("ps", ps, mshape), ("u", u, (b,))):
+        if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"adists_ts_backward: {name} must be contiguous float32 {sh}, got {t.dtype} {tuple(t.shape)}")
+    shape = (b, h, w, c) if nhwc else (b, c, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"adists_ts_backward: out must be contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    nbytes = lib().nqa_adists_ts_backward_bytes(b, c, h, w)
+    buf = (ws or Workspace()).get(max(nbytes, 16), dev)
+    _call(dev, lib().nqa_adists_ts_backward, ptr(x), ptr(y), b, c, h, w, ptr(q), ptr(wgt), ctot, coff, ptr(ps), ptr(u),
+          int(bool(mask)), int(bool(nhwc)), ptr(buf), buf.numel(), ptr(out), stream_ptr(dev))
+    return out

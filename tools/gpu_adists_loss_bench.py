@@ -10,10 +10,16 @@ The same split for the head alone on fixed taps (no pyramid, no conv backward), 
 largest windowed stage (relu1_2) with their fraction of the HBM stream figure of profiles/r04_stream_bw.txt and of the
 non-packed fp32 vector rate (210 multiply-adds per value pair forward: 5 moments x 42 taps).
 
+The loss step with the gradient on y only has a third row:
+
+  hip       ADISTS(loss_head="auto"): autograd.AdistsLossY, the one-sided backward of csrc/nqa_adists_backward.hip -- no
+            torch head, no autograd graph over maps.  (slices and default force loss_head="torch", the head they measure.)
+
 Times from device events after warm-up: median [min, max] of REPS windows of ITERS steps.
 
-Usage: python tools/gpu_adists_loss_bench.py [OUT]  -- prints the report, and also writes it to OUT when given
-(profiles/adists_loss_step_bench.txt is one such report)."""
+Usage: python tools/gpu_adists_loss_bench.py [OUT] [--loss-y-only]  -- prints the report, and also writes it to OUT when
+given (profiles/adists_loss_step_bench.txt holds such reports).  --loss-y-only: only the loss step with the gradient
+on y, default against hip (a minute instead of the whole report; also what a baseline tree is measured with)."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import functools
 import re
@@ -25,8 +31,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from nerf_qa_amd import build, ops, synth  # noqa: E402
+from nerf_qa_amd import autograd, build, ops, synth  # noqa: E402
 from nerf_qa_amd.ADISTS import ADISTS, head  # noqa: E402
+
+HIP_HEAD = hasattr(autograd, "AdistsLossY")  # (False on a tree from before the one-sided backward: the baseline's rows only)
 
 WARMUP, ITERS, REPS = 2, 10, 5
 SHAPES = ((256, 256, 8), (1080, 1920, 1))
@@ -71,6 +79,8 @@ def stream_gbs():
 
 
 def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    quick = "--loss-y-only" in sys.argv[1:]
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -109,10 +119,14 @@ def main():
 
         say(f"\n{h}x{w} B={b}")
         res = {}
-        for what, fn in (("loss step", step), ("head alone", head_step)):
-            for both in (False, True):
-                for impl, f in (("slices", slices), ("default", plain)):
+        for what, fn in (("loss step", step),) if quick else (("loss step", step), ("head alone", head_step)):
+            for both in (False,) if quick else (False, True):
+                impls = (("default", plain),) if quick else (("slices", slices), ("default", plain))
+                if what == "loss step" and not both and HIP_HEAD:
+                    impls += (("hip", plain),)  # the one-sided HIP backward (autograd.AdistsLossY): no torch head at all
+                for impl, f in impls:
                     head.adists_d = f  # (ADISTS._loss_with_grad and head_step look it up at call time)
+                    model.loss_head = "auto" if impl == "hip" else "torch"  # slices / default: the torch head, as before
                     try:
                         torch.cuda.empty_cache()
                         torch.cuda.reset_peak_memory_stats(dev)
@@ -123,6 +137,15 @@ def main():
                     m, lo, hi = res[what, both, impl]
                     say(f"  {name:42s} {m:9.3f} ms  [{lo:.3f}, {hi:.3f}]   peak memory "
                         f"{torch.cuda.max_memory_allocated(dev) / 2 ** 30:6.2f} GiB")
+        if ("loss step", False, "hip") in res:
+            d, p = res["loss step", False, "default"], res["loss step", False, "hip"]
+            say(f"  loss step, grad on y only: default / hip = {d[0] / p[0]:.2f} (worst case, slowest hip window against "
+                f"fastest default window: {d[1] / p[2]:.2f}; min-to-max spread of the repeats: default "
+                f"{(d[2] - d[1]) / d[0] * 100:.1f} %, hip {(p[2] - p[1]) / p[0] * 100:.1f} %)")
+        if quick:
+            del x0, y0, tx, ty
+            torch.cuda.empty_cache()
+            continue
         for what in ("loss step", "head alone"):
             for both in (False, True):
                 s, d = res[what, both, "slices"], res[what, both, "default"]
@@ -152,8 +175,8 @@ def main():
                 f"= {fma / m * 1e3 / FMA_PER_S * 100:5.1f} % of the vector rate")
         del x0, y0, tx, ty, fx, fy, gs
         torch.cuda.empty_cache()
-    if len(sys.argv) > 1:
-        out = sys.argv[1]
+    if args:
+        out = args[0]
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
