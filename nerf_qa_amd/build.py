@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
-SOURCES = ["nqa_api.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_group_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
+SOURCES = ["nqa_api.hip", "nqa_weights.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_group_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
            "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_window_moments.hip",
            "nqa_adists_backward.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,6 @@
-// extern "C" surface of libnqa_hip.so (include/nqa.h): error plumbing, timing ring,
-// weight packing, and the drivers that chain the kernels into forward_once /
-// DISTS.forward (nerf_qa/DISTS_pytorch/DISTS_pt.py:91-148).
+// extern "C" surface of libnqa_hip.so (include/nqa.h): error plumbing, launch preparation, timing ring,
+// and the drivers that chain the kernels into forward_once / DISTS.forward
+// (nerf_qa/DISTS_pytorch/DISTS_pt.py:91-148).  The weight packers are in nqa_weights.hip.
 #include <math.h>
 #include <stdarg.h>
 #include <string.h>
@@ -35,6 +35,40 @@ int check_launch(const char *what) {
 Tuning &tuning() {
   static thread_local Tuning t;
   return t;
+}
+
+// ---- launch preparation (nqa_common.h) ----------------------------------------------------
+int current_device() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? dev : 0;
+}
+
+int num_cus(const char *who) {
+  static std::atomic<int> cus[64];  // (concurrent first calls both query and store the same value)
+  const int dev = current_device() & 63;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+      if (who) set_error("%s: cannot query the device", who);
+      return 0;
+    }
+    n = prop.multiProcessorCount;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+int raise_lds_limit(const void *kernel, std::atomic<bool> *done_dev, int bytes, const char *who) {
+  std::atomic<bool> &done = done_dev[current_device() & 63];
+  if (!done) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+      set_error("%s: cannot raise the dynamic LDS limit to %d bytes", who, bytes);
+      return NQA_E_LAUNCH;
+    }
+    done = true;
+  }
+  return NQA_OK;
 }
 
 // ---- timing ring ------------------------------------------------------------------
@@ -77,103 +111,6 @@ TimedLaunch::TimedLaunch(int kc, hipStream_t s) : kclass(kc), stream(s), slot(-1
 }
 TimedLaunch::~TimedLaunch() {
   if (slot >= 0) (void)hipEventRecord(g_ev1[slot], stream);
-}
-
-// ---- packed weight blob -------------------------------------------------------------
-// bytes per weight in the blob of `prec`: NQA_PREC_F32M holds f16 (hi, lo) pairs for layers 1..6 and f32s rows
-// (also hi + lo halves) for layers 7..12
-static size_t blob_weight_bytes(int prec) { return is_mixed(prec) ? 4 : prec_elem_bytes(prec); }
-static size_t layer_bytes(int layer, int prec) {
-  const ConvSpec &c = kConvs[layer];
-  if (layer == 0) return align_up(27 * 64 * 4 + 64 * 4, 256) + 6144;
-  // weights, then float bias[cout] followed by ONE float: 1 / (the layer's power-of-two weight scale)
-  return align_up((size_t)c.cin * c.cout * 9 * blob_weight_bytes(prec), 256) + align_up((size_t)c.cout * 4 + 4, 256);
-}
-size_t layer_offset(int layer, int prec) {
-  size_t o = kZeroPage;
-  for (int l = 0; l < layer; ++l) o += layer_bytes(l, prec);
-  return o;
-}
-size_t layer0_mfma_offset(int prec) { return layer_offset(0, prec) + align_up(27 * 64 * 4 + 64 * 4, 256); }
-// Register-resident weight fragments of layers 1..4 (conv1_2, conv2_1: Cin 64; conv2_2, conv3_1: Cin 128), 16-bit
-// modes only: the whole layer as 16x16x32 MFMA A fragments [cout/32][2 tiles of 16][Cin/32*9 k-steps][64 lanes][8 halfs],
-// k-step = chunk * 9 + tap (chunk = 32 input channels), lane = (row l15, k-group c4): element j is
-// w[cout = 32*g + 16*i + l15][cin = 32*chunk + 8*c4 + j][tap].  conv3x3_regw_kernel loads its 2 x 18 fragments
-// (144 VGPRs) once per persistent block.  Appended behind the ordinary layers.
-// (NQA_PREC_F32M: the same fragments for 16 channels per group, once as the f16 `hi` and once as the `lo` part of the
-// scaled weights: [cout/16][part][k-steps][64 lanes][8 halfs])
-// (NQA_PREC_F32S: conv1_2 and conv2_1 in the two-term form, for conv1_regw_split_kernel and conv3x3_regw_split_kernel)
-size_t regw_bytes(int layer, int prec) {
-  if (prec == NQA_PREC_F32S) return layer <= 2 ? (size_t)kConvs[layer].cout * 64 * 9 * 2 * 2 : 0;  // conv1_2, conv2_1
-  return (size_t)kConvs[layer].cout * kConvs[layer].cin * 9 * 2 * (is_mixed(prec) ? 2 : 1);
-}
-static const int kRegwFirst = 1, kRegwLast = 4;  // conv1_2, conv2_1 (Cin 64); conv2_2, conv3_1 (Cin 128)
-// conv1_1 as 16x16x32 MFMA A fragments for conv1_regw_kernel: [4 tiles of 16 channels][2 MFMAs][64 lanes][8 halfs];
-// MFMA m contracts kernel rows 2m and 2m+1: k = 16*(ky - 2m) + 4*kx + c (kx, c padded to 4; zero for ky = 3)
-static constexpr size_t kW1M16Bytes = 4 * 2 * 64 * 16;
-size_t regw_offset(int layer, int prec) {
-  size_t o = layer_offset(NQA_NUM_CONVS, prec);
-  for (int l = kRegwFirst; l < layer; ++l) o += regw_bytes(l, prec);
-  return o;
-}
-size_t layer0_m16_offset(int prec) { return regw_offset(kRegwLast + 1, prec); }
-size_t layer_bias_offset(int layer, int prec) {
-  const ConvSpec &c = kConvs[layer];
-  if (layer == 0) return layer_offset(0, prec) + 27 * 64 * 4;
-  return layer_offset(layer, prec) + align_up((size_t)c.cin * c.cout * 9 * blob_weight_bytes(prec), 256);
-}
-
-static uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);                    // round to nearest even
-}
-static uint16_t f32_to_f16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u;
-  u &= 0x7FFFFFFFu;
-  if (u >= 0x7F800000u) return (uint16_t)(sign | (u > 0x7F800000u ? 0x7E00u : 0x7C00u));
-  if (u >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // rounds to >= 65520 -> inf
-  if (u < 0x33000001u) return (uint16_t)sign;               // < 2^-25 (or == 2^-25 tie -> 0)
-  const int e = (int)(u >> 23) - 127;
-  uint32_t m = (u & 0x7FFFFFu) | 0x800000u;
-  int shift;
-  uint32_t base;
-  if (e < -14) {  // subnormal half
-    shift = 13 + (-14 - e);
-    base = 0;
-  } else {
-    shift = 13;
-    base = (uint32_t)(e + 15) << 10;
-    m &= 0x7FFFFFu;
-  }
-  uint32_t r = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (r & 1u))) ++r;
-  return (uint16_t)(sign | (base + r));
-}
-static float f16_to_f32(uint16_t hv) {
-  const int e = (hv >> 10) & 31, m = hv & 1023;
-  float v;
-  if (e == 0) v = ldexpf((float)m, -24);
-  else if (e == 31) v = m ? NAN : INFINITY;
-  else v = ldexpf((float)(m | 1024), e - 25);
-  return (hv & 0x8000) ? -v : v;
-}
-
-// power of two that puts a layer's largest |w| in [512, 1024): the f16 `lo` part of a scaled weight is then a normal
-// half (see the f32s packing below); the conv epilogues multiply by the exact inverse
-static int weight_scale_exp(const float *w, size_t count) {
-  float wmax = 0.f;
-  for (size_t i = 0; i < count; ++i) wmax = fmaxf(wmax, fabsf(w[i]));
-  int k = 0;
-  if (wmax > 0.f && isfinite(wmax)) {
-    k = (int)floor(log2(1024.0 / (double)wmax));
-    k = k < -8 ? -8 : (k > 24 ? 24 : k);
-  }
-  return k;
 }
 
 // ---- drivers ----------------------------------------------------------------------------
@@ -325,204 +262,6 @@ int nqa_timing_collect(int launches[NQA_K_COUNT], double ms[NQA_K_COUNT]) {
     ms[g_cls[s]] += (double)t;
   }
   g_used = 0;
-  return NQA_OK;
-}
-
-size_t nqa_packed_weights_bytes(int prec) {
-  if (!prec_valid_pyramid(prec)) return 0;
-  size_t n = layer_offset(NQA_NUM_CONVS, prec);
-  if (is_mixed(prec) || prec_elem_bytes(prec) == 2 || prec == NQA_PREC_F32S)
-    n = layer0_m16_offset(prec) + kW1M16Bytes * (is_mixed(prec) || prec == NQA_PREC_F32S ? 2 : 1);
-  return n;
-}
-
-int nqa_pack_vgg_weights(const float *const w_host[NQA_NUM_CONVS], const float *const b_host[NQA_NUM_CONVS], int prec,
-                         void *packed_host) {
-  if (!w_host || !b_host || !packed_host) {
-    set_error("pack_vgg_weights: null pointer");
-    return NQA_E_ARG;
-  }
-  if (!prec_valid_pyramid(prec)) {
-    set_error("pack_vgg_weights: unknown prec %d", prec);
-    return NQA_E_ARG;
-  }
-  char *blob = static_cast<char *>(packed_host);
-  memset(blob, 0, nqa_packed_weights_bytes(prec));
-  {  // layer 0: w0[k][co], k = (ky*3+kx)*3 + c, from OIHW
-    float *w0 = reinterpret_cast<float *>(blob + layer_offset(0, prec));
-    for (int co = 0; co < 64; ++co)
-      for (int c = 0; c < 3; ++c)
-        for (int t = 0; t < 9; ++t) w0[(t * 3 + c) * 64 + co] = w_host[0][(co * 3 + c) * 9 + t];
-    memcpy(blob + layer_bias_offset(0, prec), b_host[0], 64 * 4);
-    if (!is_mixed(prec) && prec_elem_bytes(prec) == 2) {  // MFMA A fragments for the fused stage-1 kernel
-      uint16_t *wm = reinterpret_cast<uint16_t *>(blob + layer0_mfma_offset(prec));
-      for (int ky = 0; ky < 3; ++ky)
-        for (int co = 0; co < 64; ++co)
-          for (int hh = 0; hh < 2; ++hh)
-            for (int j = 0; j < 8; ++j) {
-              const int kx = 2 * hh + j / 4, c = j % 4;
-              const float v = (kx < 3 && c < 3) ? w_host[0][(co * 3 + c) * 9 + ky * 3 + kx] : 0.f;
-              wm[((ky * 64 + co) * 2 + hh) * 8 + j] = prec == NQA_PREC_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
-            }
-    }
-  }
-  for (int l = 1; l < NQA_NUM_CONVS; ++l) {
-    const ConvSpec &cs = kConvs[l];
-    // the kernel precision that reads this layer: NQA_PREC_F32M = f16 kernels (two-term weights) for layers 1..6,
-    // f32s kernels for the rest
-    const int lprec = stage_prec(prec, cs.stage), nterm = layer_terms(prec, l);
-    const int cpc = prec_elem_bytes(lprec) == 4 ? 4 : 8, kc = 4 * cpc;
-    const int bn = 64, ncc = cs.cin / kc;
-    char *dst = blob + layer_offset(l, prec);
-    {  // 1 / weight scale behind the bias (1 in every mode but f32s)
-      float one = 1.f;
-      memcpy(blob + layer_bias_offset(l, prec) + (size_t)cs.cout * 4, &one, 4);
-    }
-    if (nterm == 2) {
-      // f16 (hi, lo) pairs of the weights times a power of two (as for f32s below: lo must be a NORMAL half), in
-      // the stage order of conv3x3_igemm_kernel<..., NTERM = 2>: per 64-channel sub-slab and 32-channel chunk,
-      // [ky][part: hi, lo][kx][64 rows][4 chunks of 8 halfs]; chunk swizzle as in the one-term 16-bit blob
-      const int k = weight_scale_exp(w_host[l], (size_t)cs.cout * cs.cin * 9);
-      const float wscale = ldexpf(1.f, k), winv = ldexpf(1.f, -k);
-      memcpy(blob + layer_bias_offset(l, prec) + (size_t)cs.cout * 4, &winv, 4);
-      for (int ct = 0; ct < cs.cout / bn; ++ct)
-        for (int cc = 0; cc < ncc; ++cc)
-          for (int ky = 0; ky < 3; ++ky)
-            for (int part = 0; part < 2; ++part)
-              for (int kx = 0; kx < 3; ++kx)
-                for (int n = 0; n < bn; ++n)
-                  for (int pos = 0; pos < 4; ++pos) {
-                    const int c = pos ^ (l >= 2 ? ((n >> 2) & 1) * 2 : (n >> 2) & 3);
-                    uint16_t *row = reinterpret_cast<uint16_t *>(dst) +
-                                    ((((((((size_t)ct * ncc + cc) * 3 + ky) * 2 + part) * 3 + kx) * bn + n) * 4 + pos) * 8);
-                    for (int j = 0; j < 8; ++j) {
-                      const int cin = cc * 32 + c * 8 + j, cout = ct * bn + n;
-                      const float v = w_host[l][((size_t)cout * cs.cin + cin) * 9 + ky * 3 + kx] * wscale;
-                      const uint16_t hi = f32_to_f16(v);
-                      row[j] = part == 0 ? hi : f32_to_f16(v - f16_to_f32(hi));
-                    }
-                  }
-      memcpy(blob + layer_bias_offset(l, prec), b_host[l], (size_t)cs.cout * 4);
-      continue;
-    }
-    if (lprec == NQA_PREC_F32S) {
-      // rows of 16 input channels as [hi 0-7 | hi 8-15 | lo 0-7 | lo 8-15] halves, lo = f16(w*s - hi).
-      // s is a power of two per layer that puts the layer's largest |w| in [512, 1024): a VGG weight is
-      // ~1e-2, whose residual after the f16 `hi` (~5e-6) is a SUBNORMAL half with an absolute quantum of 6e-8
-      // -- 25 times coarser than float32 relative to the weight, which left 2e-6 of noise on every
-      // pre-activation and flipped nearly-dead channels of A-DISTS (oracle/knife_edge_study.py).  Scaled,
-      // hi and lo are both normal halves (22-23 significant bits together); the scale is exact and the
-      // conv epilogue multiplies the accumulator by 1/s (also exact) before the bias.
-      float wmax = 0.f;
-      for (size_t i = 0; i < (size_t)cs.cout * cs.cin * 9; ++i) wmax = fmaxf(wmax, fabsf(w_host[l][i]));
-      int k = 0;
-      if (wmax > 0.f && isfinite(wmax)) {
-        k = (int)floor(log2(1024.0 / (double)wmax));
-        k = k < -8 ? -8 : (k > 24 ? 24 : k);
-      }
-      const float wscale = ldexpf(1.f, k), winv = ldexpf(1.f, -k);
-      memcpy(blob + layer_bias_offset(l, prec) + (size_t)cs.cout * 4, &winv, 4);
-      for (int ct = 0; ct < cs.cout / bn; ++ct)
-        for (int cc = 0; cc < ncc; ++cc)
-          for (int t = 0; t < 9; ++t)
-            for (int n = 0; n < bn; ++n)
-              for (int pos = 0; pos < 4; ++pos) {
-                const int c = pos ^ ((n >> 2) & 3);
-                uint16_t *row = reinterpret_cast<uint16_t *>(dst) + (((((size_t)ct * ncc + cc) * 9 + t) * bn + n) * 4 + pos) * 8;
-                for (int j = 0; j < 8; ++j) {
-                  const int cin = cc * 16 + (c & 1) * 8 + j, cout = ct * bn + n;
-                  const float v = w_host[l][((size_t)cout * cs.cin + cin) * 9 + t] * wscale;
-                  const uint16_t hi = f32_to_f16(v);
-                  row[j] = c < 2 ? hi : f32_to_f16(v - f16_to_f32(hi));
-                }
-              }
-      memcpy(blob + layer_bias_offset(l, prec), b_host[l], (size_t)cs.cout * 4);
-      continue;
-    }
-    for (int ct = 0; ct < cs.cout / bn; ++ct)
-      for (int cc = 0; cc < ncc; ++cc)
-        for (int t = 0; t < 9; ++t)
-          for (int n = 0; n < bn; ++n)
-            for (int pos = 0; pos < 4; ++pos) {
-              // chunk swizzle of the MFMA shape that reads the layer: 16x16x32 for the 16-bit igemm
-              // layers (2..13), 32x32x16 for conv1_2 (shared with the fused stage-1 kernel) and f32
-              const int c = pos ^ ((cpc == 8 && l >= 2) ? ((n >> 2) & 1) * 2 : (n >> 2) & 3);
-              const size_t e0 = (((((size_t)ct * ncc + cc) * 9 + t) * bn + n) * 4 + pos) * cpc;
-              for (int j = 0; j < cpc; ++j) {
-                const int cin = cc * kc + c * cpc + j, cout = ct * bn + n;
-                const float v = w_host[l][((size_t)cout * cs.cin + cin) * 9 + t];
-                if (lprec == NQA_PREC_F32)
-                  reinterpret_cast<float *>(dst)[e0 + j] = v;
-                else
-                  reinterpret_cast<uint16_t *>(dst)[e0 + j] = lprec == NQA_PREC_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
-              }
-            }
-    memcpy(blob + layer_bias_offset(l, prec), b_host[l], (size_t)cs.cout * 4);
-  }
-  if (is_mixed(prec) || prec == NQA_PREC_F32S) {
-    // conv1_1 for conv1_regw_kernel<.., NTERM = 2> (and, in f32s, conv1_regw_split_kernel): [4 tiles of 16 channels][2
-    // MFMAs][part: hi, lo][64 lanes][8 halfs] of
-    // the weights times a power of two; 1 / that scale in the first float of the 32x32-fragment area
-    const int k1 = weight_scale_exp(w_host[0], 64 * 27);
-    const float s1 = ldexpf(1.f, k1), inv1 = ldexpf(1.f, -k1);
-    memcpy(blob + layer0_mfma_offset(prec), &inv1, 4);
-    uint16_t *w1 = reinterpret_cast<uint16_t *>(blob + layer0_m16_offset(prec));
-    for (int i = 0; i < 4; ++i)
-      for (int m = 0; m < 2; ++m)
-        for (int part = 0; part < 2; ++part)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int k = 8 * (lane >> 4) + j, ky = 2 * m + (k >> 4), kx = (k >> 2) & 3, c = k & 3;
-              const int cout = 16 * i + (lane & 15);
-              const float v = (ky < 3 && kx < 3 && c < 3) ? w_host[0][(cout * 3 + c) * 9 + ky * 3 + kx] * s1 : 0.f;
-              const uint16_t hi = f32_to_f16(v);
-              w1[((((size_t)i * 2 + m) * 2 + part) * 64 + lane) * 8 + j] = part == 0 ? hi : f32_to_f16(v - f16_to_f32(hi));
-            }
-    // two-term register fragments of layers 1..4 (conv3x3_regw_kernel<.., NTERM = 2> and regw128; f32s: conv1_2 only)
-    for (int l = kRegwFirst; l <= (prec == NQA_PREC_F32S ? kRegwFirst + 1 : kRegwLast); ++l) {
-      const ConvSpec &cs = kConvs[l];
-      const int nks = cs.cin / 32 * 9;
-      const float wscale = ldexpf(1.f, weight_scale_exp(w_host[l], (size_t)cs.cout * cs.cin * 9));  // (as the layer's rows)
-      uint16_t *dst = reinterpret_cast<uint16_t *>(blob + regw_offset(l, prec));
-      for (int g = 0; g < cs.cout / 16; ++g)
-        for (int part = 0; part < 2; ++part)
-          for (int ks = 0; ks < nks; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int j = 0; j < 8; ++j) {
-                const int cout = 16 * g + (lane & 15), cin = 32 * (ks / 9) + 8 * (lane >> 4) + j, t = ks % 9;
-                const float v = w_host[l][((size_t)cout * cs.cin + cin) * 9 + t] * wscale;
-                const uint16_t hi = f32_to_f16(v);
-                dst[((((size_t)g * 2 + part) * nks + ks) * 64 + lane) * 8 + j] = part == 0 ? hi : f32_to_f16(v - f16_to_f32(hi));
-              }
-    }
-  }
-  if (!is_mixed(prec) && prec_elem_bytes(prec) == 2) {
-    for (int l = kRegwFirst; l <= kRegwLast; ++l) {
-      const ConvSpec &cs = kConvs[l];
-      const int nks = cs.cin / 32 * 9;  // k-steps: chunk * 9 + tap
-      uint16_t *dst = reinterpret_cast<uint16_t *>(blob + regw_offset(l, prec));
-      for (int g = 0; g < cs.cout / 32; ++g)
-        for (int i = 0; i < 2; ++i)
-          for (int ks = 0; ks < nks; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int j = 0; j < 8; ++j) {
-                const int cout = 32 * g + 16 * i + (lane & 15), cin = 32 * (ks / 9) + 8 * (lane >> 4) + j, t = ks % 9;
-                const float v = w_host[l][((size_t)cout * cs.cin + cin) * 9 + t];
-                dst[((((size_t)g * 2 + i) * nks + ks) * 64 + lane) * 8 + j] =
-                    prec == NQA_PREC_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
-              }
-    }
-    uint16_t *w1 = reinterpret_cast<uint16_t *>(blob + layer0_m16_offset(prec));
-    for (int i = 0; i < 4; ++i)
-      for (int m = 0; m < 2; ++m)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int k = 8 * (lane >> 4) + j, ky = 2 * m + (k >> 4), kx = (k >> 2) & 3, c = k & 3;
-            const int cout = 16 * i + (lane & 15);
-            const float v = (ky < 3 && kx < 3 && c < 3) ? w_host[0][(cout * 3 + c) * 9 + ky * 3 + kx] : 0.f;
-            w1[(((size_t)i * 2 + m) * 64 + lane) * 8 + j] = prec == NQA_PREC_BF16 ? f32_to_bf16(v) : f32_to_f16(v);
-          }
-  }
   return NQA_OK;
 }
 
@@ -1171,41 +910,6 @@ int nqa_dists_score(const float *s1, const float *s2, const float *alpha, const 
 
 
 // ---- backward pass (DISTS require_grad=True; nqa_backward.hip) -----------------------------------------------------
-static size_t conv_split_bias_off(int cout, int cin) { return align_up((size_t)cout * cin * 9 * 4, 256); }
-
-size_t nqa_packed_conv_split_bytes(int cout, int cin) {
-  if (cout <= 0 || cin <= 0 || cout % 64 || cin % 16) return 0;
-  return conv_split_bias_off(cout, cin) + align_up((size_t)cout * 4 + 4, 256);
-}
-
-int nqa_pack_conv_split(const float *w_oihw, int cout, int cin, void *packed_host) {
-  if (!w_oihw || !packed_host || cout <= 0 || cin <= 0 || cout % 64 || cin % 16) {
-    set_error("pack_conv_split: bad argument (cout %d must be a multiple of 64, cin %d of 16)", cout, cin);
-    return NQA_E_ARG;
-  }
-  char *blob = static_cast<char *>(packed_host);
-  memset(blob, 0, nqa_packed_conv_split_bytes(cout, cin));  // (bias = 0)
-  const int k = weight_scale_exp(w_oihw, (size_t)cout * cin * 9);
-  const float wscale = ldexpf(1.f, k), winv = ldexpf(1.f, -k);
-  memcpy(blob + conv_split_bias_off(cout, cin) + (size_t)cout * 4, &winv, 4);
-  const int bn = 64, ncc = cin / 16;  // the f32s row layout of nqa_pack_vgg_weights
-  for (int ct = 0; ct < cout / bn; ++ct)
-    for (int cc = 0; cc < ncc; ++cc)
-      for (int t = 0; t < 9; ++t)
-        for (int n = 0; n < bn; ++n)
-          for (int pos = 0; pos < 4; ++pos) {
-            const int c = pos ^ ((n >> 2) & 3);
-            uint16_t *row = reinterpret_cast<uint16_t *>(blob) + (((((size_t)ct * ncc + cc) * 9 + t) * bn + n) * 4 + pos) * 8;
-            for (int j = 0; j < 8; ++j) {
-              const int ci = cc * 16 + (c & 1) * 8 + j, co = ct * bn + n;
-              const float v = w_oihw[((size_t)co * cin + ci) * 9 + t] * wscale;
-              const uint16_t hi = f32_to_f16(v);
-              row[j] = c < 2 ? hi : f32_to_f16(v - f16_to_f32(hi));
-            }
-          }
-  return NQA_OK;
-}
-
 int nqa_conv3x3_split(const void *in_split16, int n, int H, int W, int cin, int cout, const void *packed_conv, int relu,
                       float *out_nhwc, void *stream) {
   if (!in_split16 || !packed_conv || !out_nhwc) {

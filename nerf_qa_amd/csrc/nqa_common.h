@@ -181,24 +181,47 @@ static inline int layer_terms(int prec, int layer) {
 static const int kChns[NQA_NUM_TAPS] = {3, 64, 128, 256, 512, 512};
 static const int kChnOff[NQA_NUM_TAPS] = {0, 3, 67, 195, 451, 963};
 
-// Packed-blob layout (bytes).  [0,256): zero page (source of out-of-image halo pixels).
-// Layer 0: float w[27][64] (k = (ky*3+kx)*3+c) then float bias[64].  Layers 1..12: tiles
-// [cout/64][cin/KC][9 taps][64 rows] of 64 bytes (chunk c of row n stored at position
-// c ^ ((n>>2)&3), or c ^ 2*((n>>2)&1) for the 16-bit layers 2..12 read by the 16x16x32 MFMA), then
-// float bias[cout].  The 64-channel granularity lets any block tile
-// that is a multiple of 64 channels stream whole sub-slabs.
+// ---- Packed weight blob -------------------------------------------------------------------------------------------------
+// What nqa_pack_vgg_weights writes for mode `prec` and every kernel reads (nqa_weights.hip: one walk over the sections
+// below per mode fills a table, the accessors here read it).  Sections in blob order; sections 1..4 and each part of 4
+// start on a multiple of 256 bytes, the fragment sections 5..6 follow one another without padding.
+//   "16-bit modes" = bf16, f16 (elements in the mode's format); "two-term modes" = f32s and the mixed modes f32m, f32m2,
+//   f32m4, f16w.  (hi, lo) of a weight w: hi = f16(w * s), lo = f16(w * s - hi), s the power of two that puts the
+//   layer's largest |w| in [512, 1024) (so that lo is a normal half; 2^-8 <= s <= 2^24, s = 1 for an all-zero layer).
+//
+// 1. Zero page, 256 bytes: the source of out-of-image halo pixels.
+// 2. Layer 0 (conv1_1) for the float kernels: float w[27][64], k = (ky*3+kx)*3 + c, then float bias[64].
+// 3. conv1_1 as 32x32x16 MFMA A fragments, 6144 bytes: [ky][cout][h][8 elements], element j of half h is the weight of
+//    (kx = 2h + j/4, c = j%4), i.e. k = ky*16 + kx*4 + c, zero for kx = 3 or c = 3.  16-bit modes only (conv1_fused_kernel,
+//    conv1_tile_kernel).  f32: zeros.  Two-term modes: the first float is 1/s of section 6, the rest zeros.
+// 4. Layers 1..12, each: its rows, then float bias[cout] followed by ONE float 1/s (1 where the rows are unscaled).
+//    Rows are tiles [cout/64][cin/KC] of [9 taps][64 rows][4 positions of 16 bytes]; chunk c of row n lies at position
+//    c ^ ((n>>2)&3), or c ^ 2*((n>>2)&1) in the 16-bit and two-term-row layers 2..12 (read by the 16x16x32 MFMA).  The
+//    64-channel granularity lets any block tile that is a multiple of 64 channels stream whole sub-slabs.  By the kernel
+//    precision that reads the layer (stage_prec, layer_terms):
+//      f32            KC = 16; chunk c = 4 floats, input channels 4c.. of the tile
+//      bf16, f16      KC = 32; chunk c = 8 elements, channels 8c..
+//      f32s           KC = 16; chunk c = 8 halfs, channels 8(c&1)..: hi for c < 2, lo for c >= 2 (4 bytes per weight)
+//      two-term rows  (a mixed mode's layers up to its boundary) KC = 32; the tile is [ky][hi, lo][kx][64 rows][4
+//                     positions] (18 slabs); chunk c = 8 halfs, channels 8c.. (4 bytes per weight)
+// 5. Layers 1..4 (conv1_2, conv2_1: Cin 64; conv2_2, conv3_1: Cin 128) whole as 16x16x32 MFMA A fragments for the
+//    register-weights kernels: [cout/16 tiles][terms][Cin/32 * 9 k-steps][64 lanes][8 halfs], k-step = chunk * 9 + tap,
+//    element j of lane (row l15 = lane & 15, k-group c4 = lane >> 4) = w[16*tile + l15][32*chunk + 8*c4 + j][tap].
+//    16-bit modes: one term (a kernel's 32-channel group = two consecutive tiles).  Two-term modes: the tile's hi, then
+//    its lo, with the s of the layer's rows; f32s carries layers 1..2 only.  f32: none.
+// 6. conv1_1 as 16x16x32 A fragments: [4 tiles of 16 channels][2 MFMAs][terms][64 lanes][8 halfs]; MFMA m contracts
+//    kernel rows 2m and 2m+1: k = 8*c4 + j = 16*(ky - 2m) + 4*kx + c (kx, c padded to 4; zero for ky = 3).  Terms and
+//    modes as in 5 (8192 bytes per term); the two-term s is conv1_1's own, its 1/s heads section 3.
 static constexpr size_t kZeroPage = 256;
-size_t layer_offset(int layer, int prec);
-size_t layer_bias_offset(int layer, int prec);
-// conv1_1 again as 16-bit MFMA A fragments [ky][cout][h][8], k = ky*16 + kx*4 + c (zero for
-// kx = 3 or c = 3), 6144 bytes, for the fused stage-1 kernel (zeros in the f32 blob)
-size_t layer0_mfma_offset(int prec);
-// 16x16x32 MFMA A fragments of a 64-input-channel layer (1 or 2), 16-bit modes: see nqa_api.hip
-size_t regw_offset(int layer, int prec);
-size_t layer0_m16_offset(int prec);  // conv1_1 as 16x16x32 A fragments (16-bit modes)
-
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+size_t layer_offset(int layer, int prec);       // sections 2 / 4: the layer's weights (layer 0..12)
+size_t layer_bias_offset(int layer, int prec);  // its bias (layers 1..12: and 1/s)
+size_t layer0_mfma_offset(int prec);            // section 3
+size_t regw_offset(int layer, int prec);        // section 5, layer 1..4
+size_t layer0_m16_offset(int prec);             // section 6
+// a layer packed alone by nqa_pack_conv_split: f32s rows, then (at this offset) a zero bias[cout] and 1/s
+size_t conv_split_bias_off(int cout, int cin);
 
 // Where each stage's partial sums live and how to fold them (finalize_kernel).
 struct StageDesc {
@@ -246,7 +269,7 @@ __device__ inline PlaneMoments plane_moments(const double *__restrict__ part, co
 
 size_t max_act_elems(int H, int W);  // largest activation map of the pyramid, elements per image (nqa_api.hip)
 
-// ---- launch preparation (nqa_conv.hip) ---------------------------------------------------
+// ---- launch preparation (nqa_api.hip) ----------------------------------------------------
 int current_device();  // a failing hipGetDevice reads as device 0
 // compute units of the current device, cached per device (a process may drive several); 0 if the device cannot be
 // queried, with "<who>: cannot query the device" as the error when `who` is given

@@ -2292,40 +2292,6 @@ extern "C" int nqa_debug_stamps(unsigned long long *out8, int reset) {
 }
 #endif
 
-// ---- launch preparation (nqa_common.h) ----
-int current_device() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? dev : 0;
-}
-
-int num_cus(const char *who) {
-  static std::atomic<int> cus[64];  // (concurrent first calls both query and store the same value)
-  const int dev = current_device() & 63;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      if (who) set_error("%s: cannot query the device", who);
-      return 0;
-    }
-    n = prop.multiProcessorCount;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-int raise_lds_limit(const void *kernel, std::atomic<bool> *done_dev, int bytes, const char *who) {
-  std::atomic<bool> &done = done_dev[current_device() & 63];
-  if (!done) {
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-      set_error("%s: cannot raise the dynamic LDS limit to %d bytes", who, bytes);
-      return NQA_E_LAUNCH;
-    }
-    done = true;
-  }
-  return NQA_OK;
-}
-
 template <typename P>
 static int launch_conv1_1(const float *x, int n, int H, int W, const char *packed, void *out, hipStream_t st,
                           int blob_prec = P::ID) {

@@ -82,7 +82,7 @@ __device__ __forceinline__ void unit_run(int total_units, int &u_lo, int &u_hi) 
 }
 
 // ---- weights ---------------------------------------------------------------------------------------------------------
-// The blob's register-weights format (nqa_api.hip): per 16-channel tile and k-step one 16x16x32 MFMA A fragment, 16 bytes
+// The blob's register-weights format (nqa_common.h): per 16-channel tile and k-step one 16x16x32 MFMA A fragment, 16 bytes
 // per lane.  Channel group g of a layer = two fragment sets i of NKS k-steps: two 16-channel tiles (one-term weights), or
 // the f16 (hi, lo) parts of ONE tile's weights (two-term).  One fragment, straight into registers; the kernels keep the
 // loops over (i, ks) -- a helper that filled their wf[2][NKS] changed most of them.

@@ -42,7 +42,7 @@ MIN_SUBNORMAL_HALF, MIN_NORMAL_HALF = 2.0 ** -24, 2.0 ** -14
 
 # ---- (a) operands ---------------------------------------------------------------------------------------------------------
 def weight_scale_exp(w: np.ndarray) -> int:
-    """nqa_api.hip weight_scale_exp: the power of two that puts the largest |w| in [512, 1024)."""
+    """nqa_weights.hip weight_scale_exp: the power of two that puts the largest |w| in [512, 1024)."""
     wmax = float(np.abs(w).max())
     if not (wmax > 0.0 and math.isfinite(wmax)):
         return 0

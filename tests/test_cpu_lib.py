@@ -1,5 +1,5 @@
 """CPU-side checks: the C-ABI library loads, exports every declared symbol, validates
-arguments, and its host-side weight packer lays tiles out as the kernels expect."""
+arguments, and its host-side weight packer (csrc/nqa_weights.hip) lays tiles out as the kernels expect."""
 import ctypes as C
 import os
 import re

@@ -4,8 +4,8 @@
     python tools/kernel_isa_diff.py BASE_TREE [--files a.hip b.hip ...]
 
 Both trees' sources (default: every file of build.SOURCES) are compiled with build.FLAGS + build.FILE_FLAGS, device
-pass only, to assembly (at most 16 compilers at a time; no GPU is used).  Kernels are matched by mangled name across
-all files, local label numbers are normalised, comment-only lines dropped, and each kernel is put into one class:
+pass only, to assembly (at most 16 compilers at a time; no GPU is used; a source that one tree lacks gives that tree no
+kernels).  Kernels are matched by mangled name across all files, local label numbers are normalised, comment-only lines dropped, and each kernel is put into one class:
 
     identical          same instruction text and same .amdhsa_ descriptor
     commuted           every differing line has the same opcode and destination and the same sources in another order
@@ -108,6 +108,8 @@ def unified(base, new, name: str) -> str:
 
 def compile_one(build, tree: str, src: str, outdir: str):
     """Device pass of tree/nerf_qa_amd/csrc/src to assembly -> (src, parse_kernels of it)."""
+    if not os.path.exists(os.path.join(tree, "nerf_qa_amd", "csrc", src)):
+        return src, {}  # a source only the other tree has: its kernels, if any, show as "head only" / "base only"
     os.makedirs(outdir, exist_ok=True)
     out = os.path.join(outdir, src.replace(".hip", ".s"))
     cmd = [build.HIPCC, *build.FLAGS, *build.FILE_FLAGS.get(src, []), "--cuda-device-only", "-S",
