@@ -564,6 +564,34 @@ int nqa_l2pool_backward_scaled(const float *tap_nhwc, const float *g_pooled_nhwc
 int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16, const float *w_oihw_dev, const int *k,
                                 const int *k_total, int n, int H, int W, float *g_image_nchw, void *stream);
 
+/* ---- DISTS as a loss against a PREPARED TARGET (nerf_qa_amd/autograd.py, DistsTargetSimilarities): the statistics of
+ * one tap pair split where the forward ends.  nqa_dists_stats_nhwc_backward is "sums, coefficients, gradient"; here the
+ * forward runs the sums, keeps their per-block fp64 partials and forms S1 / S2 from them, and the backward starts from
+ * the kept partials -- the same sums kernel on the same grid, so they are bit for bit what the backward would have formed.
+ *
+ *   nqa_dists_stats_target               tx, ty as above.  Writes the partials ([B][nblk][C][5] doubles: sum x, sum y,
+ *       sum x^2, sum y^2, sum xy per block of pixels; nqa_dists_stats_target_bytes of them, 8-byte aligned) and
+ *       S1 = (2 mx my + c) / (mx^2 + my^2 + c), S2 = (2 cov + c) / (vx + vy + c), c = 1e-6 (DISTS_pt.py:131-139),
+ *       evaluated in fp64 and rounded to float once, pair b's C values at s1 / s2 + b * s_stride (s_stride >= C).  One
+ *       writer per output, no atomics.  Two launches (sums, fold).
+ *   nqa_dists_stats_nhwc_backward_from   nqa_dists_stats_nhwc_backward without its sums pass: `partials` as
+ *       nqa_dists_stats_target left them for the same maps and shape (read only), `coef` the [B][C][6] fp64 coefficient
+ *       records (nqa_dists_stats_nhwc_backward_from_bytes, 8-byte aligned, scratch).  gx, gy, g_s1, g_s2, g_stride as
+ *       there, and the result equals that call's bit for bit.  Two launches (coefficients, gradient).
+ * The argument rules of nqa_dists_stats_nhwc_backward: C a power of two in 16..1024 and H * W <= 2^30 (else NQA_E_SHAPE),
+ * maps 16-byte aligned, no null pointer (gx or gy may be, not both), B in 1..65535, H, W > 0, stride >= C (else
+ * NQA_E_ARG); a short partials or coefficient buffer is NQA_E_WORKSPACE.  All refused on the host before any launch; the
+ * _bytes functions return 0 for a shape the kernels do not take.  Every launch is counted as NQA_K_STATS.  For C a
+ * multiple of 32 (every tap) the two sizes add up to nqa_dists_stats_nhwc_backward_bytes. */
+size_t nqa_dists_stats_target_bytes(int B, int H, int W, int C);
+int nqa_dists_stats_target(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C, void *partials,
+                           size_t partials_bytes, float *s1, float *s2, long s_stride, void *stream);
+size_t nqa_dists_stats_nhwc_backward_from_bytes(int B, int C);
+int nqa_dists_stats_nhwc_backward_from(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C,
+                                       const void *partials, size_t partials_bytes, const float *g_s1, const float *g_s2,
+                                       long g_stride, void *coef, size_t coef_bytes, float *gx_nhwc, float *gy_nhwc,
+                                       void *stream);
+
 /* ---- windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments;
  * nqa_window_moments.hip).  x, y: dev float NCHW maps taken as P = B * C independent planes of H x W; the window is the
  * normalised 21-tap Gaussian of sigma 7 as an outer product, valid correlation: h = H - 20, w = W - 20.

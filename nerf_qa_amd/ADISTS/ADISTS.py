@@ -222,6 +222,30 @@ class ADISTS(torch.nn.Module):
             return 1 - d.mean()
         return 1 - d
 
+    def prepare_target(self, x):
+        """The fixed side of a loss, prepared once: x (B,3,H,W) on the GPU, the image that drives the texture
+        probabilities and the channel weights (forward's x) -> a target (nerf_qa_amd/target.py) holding x as float32 and
+        its five float taps, detached, to be passed to forward_target at every step.  It supports .shape, .nbytes,
+        len(), target[i:j] (views) and target.select(indices); it belongs to this module and to its VGG weights as they
+        are now, and does not pickle.  ValueError for frames that require grad, NqaError for tensors off the GPU."""
+        from .. import target
+        return target.prepare(self, x, "ADISTS")
+
+    def forward_target(self, target, y, as_loss=True):
+        """forward(x, y, as_loss) for x = a prepared target: 1 - mean(D), or 1 - D (B,) with as_loss=False (as_map is not
+        offered).  Where y requires grad (grad mode on) a step is ONE kept pyramid of y, the head and its HIP backward
+        (autograd.AdistsTargetLoss): nothing of x's pyramid runs and nothing is read back to the host; y.grad is that
+        of forward(x, y) with loss_head="auto" bit for bit.  Always in f32s, the precision of every gradient path (the
+        value is the staged head's, not the fused kernel's).  The target is used whole: NqaError if its batch does not
+        fit NQA_MAX_WORKSPACE_GB (pass target[i:j] slices), and for tensors off the GPU; ValueError for a target of
+        another module, one prepared before the VGG weights changed, and a shape that does not fit."""
+        from .. import autograd, target as tgt
+        tgt.check(self, target, y, "ADISTS")
+        if torch.is_grad_enabled() and y.requires_grad:
+            return autograd.AdistsTargetLoss.apply(y, target, self, bool(as_loss))
+        d, _ = autograd.adists_target_d(self, target, y, keep=False)
+        return 1 - d.mean() if as_loss else 1 - d
+
     def _group_checks(self, ref, renders, who="forward_group"):
         """The argument checks of forward_group (pair.score_group shares them); returns (R, K, H, W)."""
         from .._lib import NqaError

@@ -590,6 +590,31 @@ class DISTS(torch.nn.Module):
         s1, s2 = self._similarities(x, y, require_grad)
         return self._weighted(s1, s2, batch_average)
 
+    def prepare_target(self, x):
+        """The fixed side of a loss, prepared once: x (B,3,H,W) on the GPU -> a target (nerf_qa_amd/target.py) holding x
+        as float32 and its five float taps, detached, to be passed to forward_target at every step.  It supports
+        .shape, .nbytes, len(), target[i:j] (views) and target.select(indices) (a gathered copy); it belongs to this
+        module and to its VGG weights as they are now, and does not pickle.  ValueError for frames that require grad
+        (the target takes no gradient), NqaError for tensors off the GPU."""
+        from .. import target
+        return target.prepare(self, x, "DISTS")
+
+    def forward_target(self, target, y, require_grad=False, batch_average=False):
+        """forward(x, y, require_grad, batch_average) for x = a prepared target: the same shapes and return.  With
+        require_grad=True and a y that requires grad (grad mode on) a step is ONE kept pyramid of y plus the backward
+        chain (autograd.DistsTargetSimilarities) -- nothing of x runs, nothing is computed twice, nothing is read back
+        to the host -- and y.grad is forward's own bit for bit.  Otherwise y gives its taps and nothing is kept.  Always
+        in f32s, the precision of every gradient path.  alpha / beta get their gradients as in forward.  ValueError for
+        a target of another module, one prepared before the VGG weights changed, and a shape that does not fit;
+        NqaError for tensors off the GPU."""
+        from .. import autograd, target as tgt
+        tgt.check(self, target, y, "DISTS")
+        if require_grad and torch.is_grad_enabled() and y.requires_grad:
+            s1, s2 = autograd.DistsTargetSimilarities.apply(y, target, self)
+        else:
+            s1, s2 = autograd.dists_target_similarities(self, target, y)
+        return self._weighted(s1, s2, batch_average)
+
     def _group_similarities(self, ref, renders):
         """(S1, S2), each (R*K, 1475), of renders (R,K,3,H,W) against ref (R,3,H,W) from one shared pyramid per group."""
         r, k = int(ref.shape[0]), int(renders.shape[1])

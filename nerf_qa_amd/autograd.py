@@ -18,6 +18,11 @@ reference the tests pin, A-DISTS' head, and the baseline of tools/gpu_loss_step_
 
 A-DISTS as a loss with the gradient on y alone (x the fixed frame) has the same kind of path: AdistsLossY /
 adists_backward_y, the head's backward in csrc/nqa_adists_backward.hip on top of the scoring path's staged entry points.
+
+Against a PREPARED TARGET (nerf_qa_amd/target.py: the fixed frame's taps computed once for the whole optimisation) both
+losses run one kept pyramid of y per step and nothing of x: DistsTargetSimilarities keeps the statistics' fp64 partials
+from its forward and starts the backward from them, AdistsTargetLoss runs adists_backward_y's two halves in its forward
+and its backward.
 """
 from __future__ import annotations
 
@@ -185,17 +190,29 @@ def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False):
     return ops.conv1_1_backward_scaled(g, acts[0], w0, k, K)  # d(ReLU) of relu1_1 and 2^-K inside
 
 
-def _image_stats_grad(x, y, g1, g2, need):
-    """The statistics' gradient of tap 0, the raw NCHW images, through the NCHW kernels of forward_from_feats: the image
-    goes in as map 0 of six, the other five are single zero pixels with zero upstream gradients."""
+def _image_stats(x, y):
+    """The statistics of tap 0, the raw NCHW images, through the NCHW kernels of forward_from_feats: the image goes in as
+    map 0 of six, the other five are single zero pixels.  (fx, fy, S1, S2 (B, 8): columns 0..2 are the image's, scratch:
+    the forward's fp64 sums, which _image_stats_grad_from starts from)."""
     b, dev = x.shape[0], x.device
     dummy = [torch.zeros((b, 1, 1, 1), dtype=torch.float32, device=dev)] * 5
-    pad = torch.zeros((b, 5), dtype=torch.float32, device=dev)
     fx, fy = [x] + dummy, [y] + dummy
-    _, _, scratch = ops.dists_stats_nchw(fx, fy, keep_scratch=True)
+    s1, s2, scratch = ops.dists_stats_nchw(fx, fy, keep_scratch=True)
+    return fx, fy, s1, s2, scratch
+
+
+def _image_stats_grad_from(fx, fy, scratch, g1, g2, need):
+    """The gradient of _image_stats towards the images, from its kept sums: zero upstream gradients for the dummy maps."""
+    pad = torch.zeros((g1.shape[0], 5), dtype=torch.float32, device=g1.device)
     gx, gy = ops.dists_stats_nchw_backward(fx, fy, scratch, torch.cat([g1[:, :3], pad], 1), torch.cat([g2[:, :3], pad], 1),
                                            [need[0]] + [False] * 5, [need[1]] + [False] * 5)
     return gx[0], gy[0]
+
+
+def _image_stats_grad(x, y, g1, g2, need):
+    """The statistics' gradient of tap 0, the raw NCHW images: _image_stats, then its backward."""
+    fx, fy, _, _, scratch = _image_stats(x, y)
+    return _image_stats_grad_from(fx, fy, scratch, g1, g2, need)
 
 
 @torch.no_grad()
@@ -286,9 +303,23 @@ def adists_backward_y(module, x, y, u):
     n = ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b)
     if n < b:
         return torch.cat([adists_backward_y(module, x[i:i + n], y[i:i + n], u[i:i + n]) for i in range(0, b, n)])
-    prec, dev, ws = "f32s", x.device, module._ws
     tx = pyramid_taps(module, x)
-    acts, ty, pooled = pyramid_keep(module, y)
+    _, state = adists_y_forward(module, x, tx, y)  # (D comes out on the way and is not needed here)
+    return adists_y_backward(module, x, tx, y, state, u)
+
+
+@torch.no_grad()
+def adists_y_forward(module, x, tx, y, keep=True):
+    """The first half of adists_backward_y, up to D: x, y float32 contiguous (B,3,H,W), tx the five float NHWC taps of x
+    (pyramid_taps).  Returns (D (B,), state) with state = (q, wgt, maps, acts, ty, pooled), what adists_y_backward
+    needs; keep=False runs y through pyramid_taps instead of pyramid_keep (acts and pooled are then None: a value
+    without a gradient to follow)."""
+    b, _, h, w = x.shape
+    prec, dev, ws = "f32s", x.device, module._ws
+    if keep:
+        acts, ty, pooled = pyramid_keep(module, y)
+    else:
+        acts, ty, pooled = None, pyramid_taps(module, y), None
     # ---- what the head takes from x alone, and the per-channel scalars of both: the forward's own kernels ----
     q = torch.empty((8, b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
     wgt = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
@@ -304,7 +335,15 @@ def adists_backward_y(module, x, y, u):
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     ops.adists_chain_into([m[0] for m in maps], [m[1] for m in maps], [m[2] for m in maps], h, w, [m[3] for m in maps], d,
                           None, ws)
-    # ---- the six stages' gradients towards y's maps ----
+    return d, (q, wgt, maps, acts, ty, pooled)
+
+
+@torch.no_grad()
+def adists_y_backward(module, x, tx, y, state, u):
+    """The second half of adists_backward_y: dL/dy for dL/dD = u (B,) from what adists_y_forward(keep=True) returned:
+    the six stages' gradients towards y's maps, then the chain."""
+    q, wgt, maps, acts, ty, pooled = state
+    prec, ws = "f32s", module._ws
     g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws)
     off, g_taps = 3, []
     for k in range(1, 6):
@@ -333,6 +372,44 @@ class AdistsLossY(torch.autograd.Function):
         b = x.shape[0]
         u = (grad.detach().float().reshape(1) * (-1.0 / b)).expand(b).contiguous()
         return None, adists_backward_y(ctx.module, x, y, u).to(y.dtype), None
+
+
+def adists_target_d(module, target, y, keep):
+    """(D, state) of adists_y_forward for a prepared target (nerf_qa_amd/target.py) as the x side.  A target is used
+    WHOLE: there is no slicing by NQA_MAX_WORKSPACE_GB here, and a batch whose scratch (_adists_y_bytes) would pass that
+    budget is refused with NqaError -- prepare or slice the target in smaller batches."""
+    b, _, h, w = target.shape
+    if ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b) < b:
+        from ._lib import NqaError
+        raise NqaError(f"forward_target: {b} pairs of {h} x {w} need {_adists_y_bytes(b, h, w)} bytes of scratch beside the "
+                       "pyramid, more than NQA_MAX_WORKSPACE_GB allows: pass the target in slices (target[i:j])")
+    return adists_y_forward(module, target.x, list(target.taps), y.detach().float().contiguous(), keep=keep)
+
+
+class AdistsTargetLoss(torch.autograd.Function):
+    """(prepared target, y) -> 1 - mean(D) of A-DISTS (as_loss) or 1 - D (B,), differentiable in y: AdistsLossY for a
+    target whose taps are already there.  The forward is adists_y_forward -- ONE kept pyramid of y, the front, the six
+    window stages and the chain, in f32s -- and keeps its state; the backward is adists_y_backward on it, with u = dL/dD
+    formed on the device.  No pyramid of x, no second pass over y, no device -> host read."""
+
+    @staticmethod
+    def forward(ctx, y, target, module, as_loss):
+        d, state = adists_target_d(module, target, y, keep=True)
+        ctx.module, ctx.target, ctx.state, ctx.as_loss = module, target, state, as_loss
+        ctx.save_for_backward(y)
+        return 1 - d.mean() if as_loss else 1 - d
+
+    @staticmethod
+    def backward(ctx, grad):
+        (y,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        b = y.shape[0]
+        g = grad.detach().float()
+        u = (g.reshape(1) * (-1.0 / b)).expand(b).contiguous() if ctx.as_loss else (-g).contiguous()
+        t = ctx.target
+        gy = adists_y_backward(ctx.module, t.x, list(t.taps), y.detach().float().contiguous(), ctx.state, u)
+        return gy.to(y.dtype), None, None, None
 
 
 class PyramidTaps(torch.autograd.Function):
@@ -376,6 +453,79 @@ class DistsSimilarities(torch.autograd.Function):
         x, y = ctx.saved_tensors
         gx, gy = dists_backward(ctx.module, x, y, g1.contiguous(), g2.contiguous(), need=ctx.needs_input_grad[:2])
         return gx, gy, None
+
+
+@torch.no_grad()
+def dists_target_stats(target, y, ty):
+    """(S1, S2, kept) of a prepared target against y (float32 contiguous) with taps ty: per tap 1..5 the sums kernel and
+    the fold (ops.dists_stats_target), tap 0 through _image_stats.  kept = (the five taps' per-block fp64 partials, tap
+    0's maps and sums): where the backward starts."""
+    b, dev = y.shape[0], y.device
+    s1 = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
+    s2 = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
+    off, parts = 3, []
+    for fx, fy in zip(target.taps, ty):
+        parts.append(ops.dists_stats_target(fx, fy, s1, s2, off))
+        off += fx.shape[-1]
+    fx0, fy0, a1, a2, scratch = _image_stats(target.x, y)
+    s1[:, :3] = a1[:, :3]
+    s2[:, :3] = a2[:, :3]
+    return s1, s2, (parts, fx0, fy0, scratch)
+
+
+def dists_target_similarities(module, target, y):
+    """(S1, S2) of a prepared target against y with no gradient to form: y's taps by pyramid_taps, the statistics of
+    DistsTargetSimilarities, nothing kept."""
+    y = y.detach().float().contiguous()
+    s1, s2, _ = dists_target_stats(target, y, pyramid_taps(module, y))
+    return s1, s2
+
+
+@torch.no_grad()
+def dists_target_forward(module, target, y):
+    """(S1, S2, state) of a prepared target against y (float32 contiguous) WITH what a gradient needs: ONE kept pyramid
+    of y (pyramid_keep) and the statistics, whose fp64 partials are kept.  state = (acts, ty, pooled, kept)."""
+    acts, ty, pooled = pyramid_keep(module, y)
+    s1, s2, kept = dists_target_stats(target, y, ty)
+    return s1, s2, (acts, ty, pooled, kept)
+
+
+@torch.no_grad()
+def dists_target_backward(module, target, state, g1, g2):
+    """dL/dy given dL/dS1, dL/dS2 (each (B, 1475)) from dists_target_forward's state: per tap the coefficient and
+    gradient launches of the loss path started from the kept partials (no second sums pass, no pyramid), tap 0 from its
+    kept sums, then pyramid_backward_device.  The same kernels on the same operands as dists_backward(need=(False,
+    True)): that path's gradient bit for bit."""
+    acts, ty, pooled, (parts, fx0, fy0, scratch) = state
+    g1, g2 = ops._f32c(g1), ops._f32c(g2)
+    off, g_taps = 3, []
+    for fx, fy, part in zip(target.taps, ty, parts):
+        g_taps.append(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
+        off += fx.shape[-1]
+    _, gy0 = _image_stats_grad_from(fx0, fy0, scratch, g1, g2, (False, True))
+    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + gy0
+
+
+class DistsTargetSimilarities(torch.autograd.Function):
+    """(prepared target, y) -> (S1, S2), each (B, 1475), differentiable in y: DistsSimilarities for a target whose taps
+    are already there (nerf_qa_amd/target.py).  forward = dists_target_forward, whose state the Function keeps; backward
+    = dists_target_backward.  Nothing of x runs, nothing is computed twice, and there is no device -> host read in
+    either direction."""
+
+    @staticmethod
+    def forward(ctx, y, target, module):
+        yf = y.detach().float().contiguous()
+        s1, s2, state = dists_target_forward(module, target, yf)
+        ctx.module, ctx.target, ctx.state, ctx.dtype = module, target, state, y.dtype
+        ctx.save_for_backward(yf)
+        return s1, s2
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        ctx.saved_tensors  # (y itself is in the state; this is autograd's check that it was not changed in place since)
+        return dists_target_backward(ctx.module, ctx.target, ctx.state, g1, g2).to(ctx.dtype), None, None
 
 
 class FeatsSimilarities(torch.autograd.Function):

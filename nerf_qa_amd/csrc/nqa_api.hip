@@ -992,6 +992,78 @@ int nqa_dists_stats_nhwc_backward(const float *tx_nhwc, const float *ty_nhwc, in
                              gy_nhwc, static_cast<hipStream_t>(stream));
 }
 
+// ---- the same statistics for a loss against a prepared target: the forward keeps the sums, the backward starts there ----
+// What the two entry points below check alike; 0 or the error code, with the message set under `who`.
+static int loss_target_bad(const char *who, bool null_ptr, int B, int H, int W, int C, long stride, uintptr_t maps) {
+  if (null_ptr || B <= 0 || B > 65535 || H <= 0 || W <= 0 || stride < C) {
+    set_error("%s: bad argument (null pointer, B %d outside 1..65535, %d x %d, or stride %ld < C %d)", who, B, H, W, stride,
+              C);
+    return NQA_E_ARG;
+  }
+  if (loss_bad_c(C)) {
+    set_error("%s: C %d must be a power of two in 16..1024", who, C);
+    return NQA_E_SHAPE;
+  }
+  if ((long)H * W > (1L << 30)) {
+    set_error("%s: %ld > 2^30 pixels per image", who, (long)H * W);
+    return NQA_E_SHAPE;
+  }
+  if (maps & 15) {
+    set_error("%s: the maps must be 16-byte aligned, the fp64 buffers 8-byte", who);
+    return NQA_E_ARG;
+  }
+  return NQA_OK;
+}
+
+size_t nqa_dists_stats_target_bytes(int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0 || loss_bad_c(C) || (long)H * W > (1L << 30)) return 0;
+  return loss_stats_partials_doubles(B, H * W, C) * sizeof(double);
+}
+
+int nqa_dists_stats_target(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C, void *partials,
+                           size_t partials_bytes, float *s1, float *s2, long s_stride, void *stream) {
+  const char *who = "dists_stats_target";
+  if (int rc = loss_target_bad(who, !tx_nhwc || !ty_nhwc || !partials || !s1 || !s2, B, H, W, C, s_stride,
+                               (uintptr_t)tx_nhwc | (uintptr_t)ty_nhwc | ((uintptr_t)partials & 7)))
+    return rc;
+  const size_t need = nqa_dists_stats_target_bytes(B, H, W, C);
+  if (partials_bytes < need) {
+    set_error("%s: partials %zu < %zu bytes", who, partials_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return loss_stats_target(tx_nhwc, ty_nhwc, B, H * W, C, static_cast<double *>(partials), s1, s2, s_stride,
+                           static_cast<hipStream_t>(stream));
+}
+
+size_t nqa_dists_stats_nhwc_backward_from_bytes(int B, int C) {
+  if (B <= 0 || loss_bad_c(C)) return 0;
+  return align_up(loss_stats_coef_doubles(B, C) * sizeof(double), 256);
+}
+
+int nqa_dists_stats_nhwc_backward_from(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C,
+                                       const void *partials, size_t partials_bytes, const float *g_s1, const float *g_s2,
+                                       long g_stride, void *coef, size_t coef_bytes, float *gx_nhwc, float *gy_nhwc,
+                                       void *stream) {
+  const char *who = "dists_stats_nhwc_backward_from";
+  if (int rc = loss_target_bad(who, !tx_nhwc || !ty_nhwc || !partials || !g_s1 || !g_s2 || !coef || (!gx_nhwc && !gy_nhwc), B,
+                               H, W, C, g_stride,
+                               (uintptr_t)tx_nhwc | (uintptr_t)ty_nhwc | (uintptr_t)gx_nhwc | (uintptr_t)gy_nhwc |
+                                   (((uintptr_t)partials | (uintptr_t)coef) & 7)))
+    return rc;
+  const size_t need_part = nqa_dists_stats_target_bytes(B, H, W, C);
+  if (partials_bytes < need_part) {
+    set_error("%s: partials %zu < %zu bytes", who, partials_bytes, need_part);
+    return NQA_E_WORKSPACE;
+  }
+  const size_t need = nqa_dists_stats_nhwc_backward_from_bytes(B, C);
+  if (coef_bytes < need) {
+    set_error("%s: coefficient buffer %zu < %zu bytes", who, coef_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return loss_stats_backward_from(tx_nhwc, ty_nhwc, B, H * W, C, static_cast<const double *>(partials), g_s1, g_s2, g_stride,
+                                  static_cast<double *>(coef), gx_nhwc, gy_nhwc, static_cast<hipStream_t>(stream));
+}
+
 size_t nqa_grad_exponent_bytes(int n, long per_image) {
   if (n <= 0 || per_image <= 0 || per_image % 4) return 0;
   return align_up((size_t)n * grad_exponent_nblk(per_image) * sizeof(unsigned), 256);

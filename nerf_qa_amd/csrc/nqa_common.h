@@ -327,6 +327,14 @@ int conv1_1_backward_scaled(const float *g, const void *act0_split16, const floa
 size_t loss_stats_backward_doubles(int B, int HW, int C);
 int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,
                         long g_stride, double *ws, float *gx, float *gy, hipStream_t st);
+// its two halves for a loss against a prepared target: the forward leaves the sums' partials ([B][nblk][C][5] doubles)
+// and S1 / S2 (pair b's C values at s + b * s_stride); the backward starts from them (coef: [B][C][6] doubles)
+size_t loss_stats_partials_doubles(int B, int HW, int C);
+size_t loss_stats_coef_doubles(int B, int C);
+int loss_stats_target(const float *tx, const float *ty, int B, int HW, int C, double *part, float *s1, float *s2,
+                      long s_stride, hipStream_t st);
+int loss_stats_backward_from(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
+                             const float *g_s2, long g_stride, double *coef, float *gx, float *gy, hipStream_t st);
 int grad_exponent_nblk(long per_image);
 int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
 // ---- windowed moments of the A-DISTS head and their backward (nqa_window_moments.hip) ----

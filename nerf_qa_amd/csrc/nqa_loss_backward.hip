@@ -2,6 +2,8 @@
 // for gfx950: what the loss path of nerf_qa_amd/autograd.py needs beyond the chain kernels of nqa_backward.hip.
 //
 //   loss_stats_sums_kernel   the five fp64 sums behind DISTS_pt.py:131-139 of a pair of float NHWC taps, per block
+//   loss_stats_fold_kernel   one wave per (pair, channel): folds them into S1 and S2 themselves (fp64, rounded to float once):
+//                            the forward of a loss against a prepared target, whose partials the backward then starts from
 //   loss_stats_coef_kernel   one wave per (pair, channel): folds them (plane_moments, the forward's own fold) into the
 //                            six fp64 numbers {mx, my, a, b, ox, oy} of nqa_stats_backward.hip
 //   loss_stats_grad_kernel   gx = (x > 0) * (ox + a (x - mx) + b (y - my)), gy likewise with x and y swapped: the affine
@@ -74,6 +76,22 @@ __global__ __launch_bounds__(256) void loss_stats_sums_kernel(const float *__res
 #pragma unroll
       for (int q = 0; q < 5; ++q) o[e * 5 + q] = s[q][e];
   }
+}
+
+// grid (cdiv(C, 4), B), 256 threads = 4 waves = 4 channels, laid out as loss_stats_coef_kernel.  s1 / s2 point at the tap's
+// first column of pair 0; pair b's row starts s_stride floats further.  One writer per output, no atomics.
+__global__ __launch_bounds__(256) void loss_stats_fold_kernel(const double *__restrict__ part, StageDesc d,
+                                                              float *__restrict__ s1, float *__restrict__ s2, long s_stride) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= d.ctot) return;
+  const PlaneMoments m = plane_moments(part, d, b, c, lane);
+  if (lane) return;
+  const double mx = m.mx, my = m.my, vx = m.vx, vy = m.vy, cov = m.cov;
+  const double c1 = 1e-6, c2 = 1e-6;
+  s1[(size_t)b * s_stride + c] = (float)((2.0 * mx * my + c1) / (mx * mx + my * my + c1));
+  s2[(size_t)b * s_stride + c] = (float)((2.0 * cov + c2) / (vx + vy + c2));
 }
 
 // grid (cdiv(C, 4), B), 256 threads = 4 waves = 4 channels.  g_s1 / g_s2 point at the tap's first column of pair 0;
@@ -196,36 +214,64 @@ static int loss_sums_ppb(int HW, int C) {
   return cdiv(cdiv(HW, loss_sums_nblk(HW, C)), PL) * PL;
 }
 
-size_t loss_stats_backward_doubles(int B, int HW, int C) {
+// The partials of one tap pair: [B][nblk][C][5] doubles.  The coefficient records behind them: [B][C][NQA_COEF].
+size_t loss_stats_partials_doubles(int B, int HW, int C) {
   const int nblk = cdiv(HW, loss_sums_ppb(HW, C));
-  return (size_t)B * nblk * C * 5 + (size_t)B * C * NQA_COEF;
+  return (size_t)B * nblk * C * 5;
+}
+size_t loss_stats_coef_doubles(int B, int C) { return (size_t)B * C * NQA_COEF; }
+size_t loss_stats_backward_doubles(int B, int HW, int C) {
+  return loss_stats_partials_doubles(B, HW, C) + loss_stats_coef_doubles(B, C);
 }
 
-int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,
-                        long g_stride, double *ws, float *gx, float *gy, hipStream_t st) {
-  const int ppb = loss_sums_ppb(HW, C), nblk = cdiv(HW, ppb);
-  double *part = ws, *coef = ws + (size_t)B * nblk * C * 5;
+static StageDesc loss_stage_desc(int HW, int C) {
   StageDesc d = {};
-  d.nblk[0] = nblk;
+  d.nblk[0] = cdiv(HW, loss_sums_ppb(HW, C));
   d.hw[0] = HW;
   d.c[0] = C;
   d.nstage = 1;
   d.ctot = C;
+  return d;
+}
+
+static int loss_stats_sums(const float *tx, const float *ty, int B, int HW, int C, double *part, hipStream_t st) {
+  const int ppb = loss_sums_ppb(HW, C), nblk = cdiv(HW, ppb);
+  TimedLaunch t(NQA_K_STATS, st);
+  loss_stats_sums_kernel<<<dim3(nblk, B), 256, 0, st>>>(tx, ty, HW, C, ppb, part);
+  return check_launch("loss_stats_sums");
+}
+
+// sums, then S1 / S2 from them; `part` stays as the backward's starting point
+int loss_stats_target(const float *tx, const float *ty, int B, int HW, int C, double *part, float *s1, float *s2,
+                      long s_stride, hipStream_t st) {
+  int rc;
+  if ((rc = loss_stats_sums(tx, ty, B, HW, C, part, st))) return rc;
+  TimedLaunch t(NQA_K_STATS, st);
+  loss_stats_fold_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, loss_stage_desc(HW, C), s1, s2, s_stride);
+  return check_launch("loss_stats_fold");
+}
+
+// the coefficients from partials that are already there, then the gradient
+int loss_stats_backward_from(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
+                             const float *g_s2, long g_stride, double *coef, float *gx, float *gy, hipStream_t st) {
   int rc;
   {
     TimedLaunch t(NQA_K_STATS, st);
-    loss_stats_sums_kernel<<<dim3(nblk, B), 256, 0, st>>>(tx, ty, HW, C, ppb, part);
-    if ((rc = check_launch("loss_stats_sums"))) return rc;
-  }
-  {
-    TimedLaunch t(NQA_K_STATS, st);
-    loss_stats_coef_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, d, g_s1, g_s2, g_stride, coef);
+    loss_stats_coef_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, loss_stage_desc(HW, C), g_s1, g_s2, g_stride, coef);
     if ((rc = check_launch("loss_stats_coef"))) return rc;
   }
   const int PL = 256 / (C / 4), gppb = PL * 8;
   TimedLaunch t(NQA_K_STATS, st);
   loss_stats_grad_kernel<<<dim3(cdiv(HW, gppb), B), 256, 0, st>>>(tx, ty, HW, C, gppb, coef, gx, gy);
   return check_launch("loss_stats_grad");
+}
+
+int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,
+                        long g_stride, double *ws, float *gx, float *gy, hipStream_t st) {
+  double *part = ws, *coef = ws + loss_stats_partials_doubles(B, HW, C);
+  int rc;
+  if ((rc = loss_stats_sums(tx, ty, B, HW, C, part, st))) return rc;
+  return loss_stats_backward_from(tx, ty, B, HW, C, part, g_s1, g_s2, g_stride, coef, gx, gy, st);
 }
 
 int grad_exponent_nblk(long per_image) {

@@ -1023,6 +1023,56 @@ def dists_stats_nhwc_backward(tx: torch.Tensor, ty: torch.Tensor, g_s1: torch.Te
     return gx, gy
 
 
+def _tap_pair(who: str, tx: torch.Tensor, ty: torch.Tensor, s_a: torch.Tensor, s_b: torch.Tensor, col: int):
+    """The checks dists_stats_target and dists_stats_nhwc_backward_from share: a pair of contiguous float NHWC taps and two
+    contiguous float (B, ctot) rows of per-channel values that hold the tap's C columns from `col`."""
+    dev = _need_cuda(tx, ty, s_a, s_b)
+    assert tx.dtype == ty.dtype == torch.float32 and tx.is_contiguous() and ty.is_contiguous() and tx.shape == ty.shape
+    assert s_a.dtype == s_b.dtype == torch.float32 and s_a.is_contiguous() and s_b.is_contiguous()
+    b, c = tx.shape[0], tx.shape[3]
+    if s_a.shape != s_b.shape or s_a.dim() != 2 or s_a.shape[0] != b or col < 0 or col + c > s_a.shape[1]:
+        raise ValueError(f"{who}: expected rows of shape ({b}, >= {col + c}), got {tuple(s_a.shape)} / {tuple(s_b.shape)}")
+    return dev
+
+
+def dists_stats_target(tx: torch.Tensor, ty: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, col: int) -> torch.Tensor:
+    """S1 / S2 of one pair of float NHWC taps (B,H,W,C) into columns col .. col + C of s1, s2 (float (B, ctot)); returns the
+    sums' per-block fp64 partials (a uint8 tensor), which dists_stats_nhwc_backward_from starts from."""
+    dev = _tap_pair("dists_stats_target", tx, ty, s1, s2, col)
+    b, h, w, c = tx.shape
+    nbytes = lib().nqa_dists_stats_target_bytes(b, h, w, c)
+    if not nbytes:
+        raise _lib.NqaError(f"dists_stats_target: unsupported tap shape {tuple(tx.shape)}")
+    part = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_dists_stats_target, ptr(tx), ptr(ty), b, h, w, c, ptr(part), part.numel(), ptr(s1) + 4 * col,
+          ptr(s2) + 4 * col, s1.shape[1], stream_ptr(dev))
+    return part
+
+
+def dists_stats_nhwc_backward_from(tx: torch.Tensor, ty: torch.Tensor, part: torch.Tensor, g_s1: torch.Tensor,
+                                   g_s2: torch.Tensor, col: int, need_x: bool = True, need_y: bool = True,
+                                   out_x: torch.Tensor | None = None, out_y: torch.Tensor | None = None):
+    """dists_stats_nhwc_backward without its sums pass: `part` is what dists_stats_target returned for the same taps.  The
+    result is that call's bit for bit."""
+    dev = _tap_pair("dists_stats_nhwc_backward_from", tx, ty, g_s1, g_s2, col)
+    assert part.dtype == torch.uint8 and part.is_contiguous() and part.device == dev
+    b, h, w, c = tx.shape
+    gx = (torch.empty_like(tx) if out_x is None else out_x) if need_x else None
+    gy = (torch.empty_like(ty) if out_y is None else out_y) if need_y else None
+    for g in (gx, gy):
+        assert g is None or (g.shape == tx.shape and g.dtype == torch.float32 and g.is_contiguous())
+    if gx is None and gy is None:
+        return None, None
+    nbytes = lib().nqa_dists_stats_nhwc_backward_from_bytes(b, c)
+    if not nbytes:
+        raise _lib.NqaError(f"dists_stats_nhwc_backward_from: unsupported tap shape {tuple(tx.shape)}")
+    coef = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_dists_stats_nhwc_backward_from, ptr(tx), ptr(ty), b, h, w, c, ptr(part), part.numel(),
+          ptr(g_s1) + 4 * col, ptr(g_s2) + 4 * col, g_s1.shape[1], ptr(coef), coef.numel(),
+          None if gx is None else ptr(gx), None if gy is None else ptr(gy), stream_ptr(dev))
+    return gx, gy
+
+
 def grad_exponent(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
     """k[i] (int32, on the device) = the exponent with max|g[i]| * 2^k[i] in [128, 256), 0 where that maximum is 0 or
     not finite; k_total[i] += k[i].  g: float, image i = g[i].  Nothing comes back to the host."""

@@ -17,9 +17,12 @@ The loss step with the gradient on y only has a third row:
 
 Times from device events after warm-up: median [min, max] of REPS windows of ITERS steps.
 
-Usage: python tools/gpu_adists_loss_bench.py [OUT] [--loss-y-only]  -- prints the report, and also writes it to OUT when
-given (profiles/adists_loss_step_bench.txt holds such reports).  --loss-y-only: only the loss step with the gradient
-on y, default against hip (a minute instead of the whole report; also what a baseline tree is measured with)."""
+Usage: python tools/gpu_adists_loss_bench.py [OUT] [--loss-y-only | --target]  -- prints the report, and also writes it
+to OUT when given (profiles/adists_loss_step_bench.txt holds such reports).  --loss-y-only: only the loss step with the
+gradient on y, default against hip (a minute instead of the whole report; also what a baseline tree is measured with).
+--target: only the hip loss step with the gradient on y against the step on a prepared target (ADISTS.prepare_target
+once, then forward_target(target, y) per step: one kept pyramid of y, nothing of x's), same pairs, one process, with the
+time of prepare_target itself; that report is APPENDED to OUT."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import functools
 import re
@@ -78,9 +81,48 @@ def stream_gbs():
     return best
 
 
+def target_report(model, dev, say):
+    """The one-sided hip step (x fixed, gradient on y) against the step on a prepared target, same pairs, one process."""
+    model.loss_head = "auto"
+    for h, w, b in SHAPES:
+        xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
+        x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
+        target = model.prepare_target(x0)
+
+        def step():
+            y = y0.detach().requires_grad_()
+            model(x0, y).backward()
+            return y.grad
+
+        def target_step():
+            y = y0.detach().requires_grad_()
+            model.forward_target(target, y).backward()
+            return y.grad
+
+        say(f"\n{h}x{w} B={b}")
+        res = {}
+        for name, fn in (("loss step, grad on y only, hip", step), ("target step, grad on y only", target_step),
+                         ("prepare_target(x)", lambda: model.prepare_target(x0))):
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats(dev)
+            res[name] = timed(fn)
+            m, lo, hi = res[name]
+            say(f"  {name:42s} {m:9.3f} ms  [{lo:.3f}, {hi:.3f}]   peak memory "
+                f"{torch.cuda.max_memory_allocated(dev) / 2 ** 30:6.2f} GiB")
+        o, t = res["loss step, grad on y only, hip"], res["target step, grad on y only"]
+        gain, spread = o[0] - t[0], (o[2] - o[1]) + (t[2] - t[1])
+        say(f"  target / one-sided: {t[0] / o[0]:.3f} (saves {gain:.3f} ms a step; the two runs' min-to-max spreads add up to "
+            f"{spread:.3f} ms: {'a gain beyond spread' if gain > spread else 'NO gain beyond spread'}); the target holds "
+            f"{target.nbytes / 2 ** 20:.1f} MiB")
+        say(f"  y.grad bit-identical: {bool(torch.equal(step().view(torch.int32), target_step().view(torch.int32)))}")
+        del x0, y0, target
+        torch.cuda.empty_cache()
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     quick = "--loss-y-only" in sys.argv[1:]
+    with_target = "--target" in sys.argv[1:]
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -99,7 +141,12 @@ def main():
 
     plain = head.adists_d
     slices = functools.partial(plain, window_impl="slices")
-    for h, w, b in SHAPES:
+    if with_target:
+        lines[1] = ("# --target: ADISTS(x, y) (as_loss=True, loss_head auto) with x fixed against forward_target on a prepared "
+                    f"target, stand-in weights; device events, median [min, max] of {REPS} windows of {ITERS} steps after "
+                    f"{WARMUP} warm-up steps")
+        target_report(model, dev, say)
+    for h, w, b in () if with_target else SHAPES:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
         tx = [x0] + model._taps_nograd(x0)
@@ -178,8 +225,8 @@ def main():
     if args:
         out = args[0]
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        with open(out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        with open(out, "a" if with_target else "w") as f:
+            f.write(("\n" if with_target else "") + "\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

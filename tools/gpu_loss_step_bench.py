@@ -10,8 +10,13 @@ Step times from device events after warm-up: median [min, max] of REPS windows o
 fused f32s forward in all three.  Also printed: the forward alone, the host's wall time to ENQUEUE a step (equal to the
 step time when the host waits for the device inside it, a fraction of it when it does not), and the peak device memory.
 
-Usage: python tools/gpu_loss_step_bench.py [OUT]  -- prints the report, and also writes it to OUT when given
-(profiles/loss_step_bench.txt is one such report)."""
+With --target the report is another one: the existing one-sided step with x FIXED and the gradient on y (the training use:
+a render y against a ground-truth frame x) against the step on a prepared target (DISTS.prepare_target once, then
+forward_target(target, y, require_grad=True, batch_average=True) per step: one kept pyramid of y, nothing of x), on the same
+pairs in the same process, with the time of prepare_target itself.
+
+Usage: python tools/gpu_loss_step_bench.py [OUT] [--target]  -- prints the report, and also writes it to OUT when given
+(profiles/loss_step_bench.txt holds such reports; a --target report is APPENDED to OUT)."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import subprocess
 import sys
@@ -76,7 +81,46 @@ def commit():
         return "unknown"
 
 
+def target_report(model, dev, say):
+    """The one-sided step (x fixed, gradient on y) against the step on a prepared target, same pairs, one process."""
+    for h, w, b in SHAPES:
+        xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
+        x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
+        target = model.prepare_target(x0)
+
+        def step():
+            y = y0.detach().requires_grad_()
+            model(x0, y, require_grad=True, batch_average=True).backward()
+            return y.grad
+
+        def target_step():
+            y = y0.detach().requires_grad_()
+            model.forward_target(target, y, require_grad=True, batch_average=True).backward()
+            return y.grad
+
+        say(f"\n{h}x{w} B={b}")
+        res = {}
+        for name, fn in (("one-sided step, grad on y only", step), ("target step,    grad on y only", target_step),
+                         ("prepare_target(x)", lambda: model.prepare_target(x0))):
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats(dev)
+            res[name] = timed(fn)
+            m, lo, hi, wall = res[name]
+            say(f"  {name:30s} {m:9.3f} ms  [{lo:.3f}, {hi:.3f}]   enqueue {wall:8.3f} ms   peak memory "
+                f"{torch.cuda.max_memory_allocated(dev) / 2 ** 30:6.2f} GiB")
+        o, t = res["one-sided step, grad on y only"], res["target step,    grad on y only"]
+        gain, spread = o[0] - t[0], (o[2] - o[1]) + (t[2] - t[1])
+        say(f"  target / one-sided: {t[0] / o[0]:.3f} (saves {gain:.3f} ms a step; the two runs' min-to-max spreads add up to "
+            f"{spread:.3f} ms: {'a gain beyond spread' if gain > spread else 'NO gain beyond spread'}); the target holds "
+            f"{target.nbytes / 2 ** 20:.1f} MiB")
+        say(f"  y.grad bit-identical: {bool(torch.equal(step().view(torch.int32), target_step().view(torch.int32)))}")
+        del x0, y0, target
+        torch.cuda.empty_cache()
+
+
 def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    with_target = "--target" in sys.argv[1:]
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -91,7 +135,11 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    for h, w, b in SHAPES:
+    if with_target:
+        lines[1] = ("# --target: DISTS(x, y, require_grad=True, batch_average=True) with x fixed against forward_target on a "
+                    "prepared target, precision f32s, stand-in weights;")
+        target_report(model, dev, say)
+    for h, w, b in () if with_target else SHAPES:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
 
@@ -129,11 +177,11 @@ def main():
         say(f"  max |g_loss_path - g_first_form| / max |g_first_form| on x: {((ga - gb).abs().max() / ga.abs().max()).item():.2e}")
         del x0, y0
         torch.cuda.empty_cache()
-    if len(sys.argv) > 1:
-        out = sys.argv[1]
+    if args:
+        out = args[0]
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        with open(out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        with open(out, "a" if with_target else "w") as f:
+            f.write(("\n" if with_target else "") + "\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
