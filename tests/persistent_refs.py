@@ -5,7 +5,7 @@ everything here.
 
 (a) A schedule model: the host grid rules (launch_regw, launch_regw128 with its `grid -= 8` trimming, launch_regw_split
     with its streams, launch_conv1_regw / launch_conv1_regw_split, launch_conv_pool) and the kernels' own tile split
-    (TileRun and unit_run of csrc/nqa_regw.h; conv3x3_regw_split_kernel's streams), restated in integer arithmetic.  It only
+    (TileRun and unit_run of csrc/nqa_regw.h; conv3x3_regw_split_kernel's streams; launch_conv1_pool), restated in integer arithmetic.  It only
     chooses batch sizes, proves that a case reaches its regime and names the block and step behind a failing pixel.  It
     is never a reference for values.
 (b) Exact-integer operands as in tests/test_gpu_conv_igemm_addr.py: activations in {0, 1, 2}, weights in {-1, 0, 1}, a
@@ -13,7 +13,10 @@ everything here.
     weights alike, so a kernel's output must be BIT-EQUAL to relu(conv2d) taken in float64 and rounded once.
 (c) A sparse weight set for conv2_2 (at most 31 weights of +-1 per output channel, bias in {-1, 0, 1}): the tap is an
     integer in [0, 63], so its squares, the L2-pool's window sums and every float32 moment the fused kernel keeps per
-    lane are exact integers too."""
+    lane are exact integers too.
+(d) The same for the fused stage 1 (csrc/nqa_conv1_pool.hip): raw pixels float32(mean_c + std_c v) that normalise to the
+    integers v in {-1, 0, 1, 2} exactly in half, sparse integer conv1_1 and conv1_2 with relu1_2 in [0, 63], and the
+    model of launch_conv1_pool (s1_runs .. s1_owners)."""
 import functools
 
 import numpy as np
@@ -28,6 +31,15 @@ IGEMM_INT_LAYERS = (7, 8)     # conv4_1, conv4_2: the same construction, for tes
 SPARSE_LAYER = 3
 SPARSE_TERMS = 31
 PART_BLOCKS = 256             # NQA_FUSED_PART_BLOCKS: the fused kernel's grid never exceeds its partial rows
+PART_BLOCKS_S1 = 512          # NQA_FUSED_PART_BLOCKS_S1: the fused stage 1 leaves two partial rows per block
+# the fused stage 1's frames: H % 4 = 2 and W % 32 = 2 (the last unit's second half-strip wholly outside, two live columns
+# in its first); H odd, six live columns; full units (the kernel's other instance); H % 4 = 0 under a ragged W (only where
+# a strip's last tap row is live does the carried row above have to be zeroed at the next strip's top)
+S1_SHAPES = ((150, 130), (37, 70), (64, 96), (36, 70))
+S1_MEAN = (np.float32(0.485), np.float32(0.456), np.float32(0.406))   # kMean, kStd of csrc/nqa_regw.h: float32 literals
+S1_STD = (np.float32(0.229), np.float32(0.224), np.float32(0.225))
+S1_LEVELS = (-1, 0, 1, 2)     # the normalised pixel values of the integer frames
+S1_TERMS = (6, 12)            # nonzero weights per output channel of the sparse conv1_1, conv1_2
 
 # tile height, slots of the LDS-DMA ring, grid rule -- by the name of the launcher's kernel
 KERNELS = {
@@ -151,12 +163,9 @@ def reload_case(cus: int, nct: int = 2):
     raise AssertionError(f"no small conv3_1 map makes a block reload its weights on {cus} CUs with {nct} channel tiles")
 
 
-def pool_runs(b_pairs: int, h: int, w: int, cus: int, nct: int):
-    """launch_conv_pool and conv3x3_regw128_pool_kernel: per block (u_lo, u_hi, warm-up step) of its contiguous run of
-    units in [pair][channel tile][strip][row] order, and (strips, rows)."""
-    strips, rows = cdiv(w, 16), cdiv(h, 4)
-    units = b_pairs * nct * strips * rows
-    nblk = min(units, cus, PART_BLOCKS)
+def unit_runs(units: int, nblk: int, rows: int):
+    """unit_run of csrc/nqa_regw.h for a grid of nblk blocks: per block (u_lo, u_hi, warm-up step) of its contiguous run
+    of units; a run that starts inside a strip of `rows` units begins with one warm-up unit (the tile above it)."""
     qq, rr = nblk >> 3, nblk & 7
     runs = []
     for blk in range(nblk):
@@ -164,16 +173,33 @@ def pool_runs(b_pairs: int, h: int, w: int, cus: int, nct: int):
         run = blk if nblk < 8 else (xcd * (qq + 1) if xcd < rr else rr * (qq + 1) + (xcd - rr) * qq) + local
         u_lo, u_hi = units * run // nblk, units * (run + 1) // nblk
         runs.append((u_lo, u_hi, u_lo < u_hi and u_lo % rows != 0))
-    return runs, strips, rows
+    return runs
+
+
+def runs_regime(runs, per_pair: int) -> dict:
+    """What pool_in_regime and s1_in_regime ask of a list of runs; per_pair = units of one image pair.  `own`: the most
+    units a run holds, `most` / `least`: steps (with the warm-up), `inside`: the most units of ONE pair any run holds (what a lane's moments are summed over between two flushes)."""
+    def inside(lo, hi):
+        return max((min(hi, (p + 1) * per_pair) - max(lo, p * per_pair) for p in range(lo // per_pair, (hi - 1) // per_pair + 1)),
+                   default=0)
+    return dict(grid=len(runs), own=max(hi - lo for lo, hi, _ in runs), most=max(hi - lo + warm for lo, hi, warm in runs),
+                least=min(hi - lo + warm for lo, hi, warm in runs), warm=sum(1 for lo, hi, warm in runs if warm),
+                cross=sum(1 for lo, hi, _ in runs if lo < hi and lo // per_pair != (hi - 1) // per_pair),
+                inside=max(inside(lo, hi) for lo, hi, _ in runs))
+
+
+def pool_runs(b_pairs: int, h: int, w: int, cus: int, nct: int):
+    """launch_conv_pool and conv3x3_regw128_pool_kernel: per block (u_lo, u_hi, warm-up step) of its contiguous run of
+    units in [pair][channel tile][strip][row] order, and (strips, rows)."""
+    strips, rows = cdiv(w, 16), cdiv(h, 4)
+    units = b_pairs * nct * strips * rows
+    return unit_runs(units, min(units, cus, PART_BLOCKS), rows), strips, rows
 
 
 def pool_regime(b_pairs: int, h: int, w: int, cus: int, nct: int) -> dict:
     runs, strips, rows = pool_runs(b_pairs, h, w, cus, nct)
     per_pair = nct * strips * rows
-    return dict(kernel="regw128_pool", pairs=b_pairs, units=b_pairs * per_pair, grid=len(runs),
-                most=max(hi - lo + warm for lo, hi, warm in runs), least=min(hi - lo + warm for lo, hi, warm in runs),
-                warm=sum(1 for lo, hi, warm in runs if warm),
-                cross=sum(1 for lo, hi, _ in runs if lo < hi and lo // per_pair != (hi - 1) // per_pair))
+    return dict(kernel="regw128_pool", pairs=b_pairs, units=b_pairs * per_pair, **runs_regime(runs, per_pair))
 
 
 def pool_in_regime(r: dict) -> bool:
@@ -198,6 +224,45 @@ def pool_owner(img_pair: int, ct: int, sx: int, ty: int, b_pairs: int, h: int, w
         if lo <= u < hi:
             return blk, u - lo + warm
     return None
+
+
+def s1_runs(b_pairs: int, h: int, w: int, cus: int):
+    """launch_conv1_pool and conv1_pool_kernel: per block (u_lo, u_hi, warm-up step) of its contiguous run of units of
+    4 rows x 32 columns in [pair][strip pair][row] order, and (strip pairs, rows).  Two partial rows per block."""
+    spairs, rows = cdiv(w, 32), cdiv(h, 4)
+    units = b_pairs * spairs * rows
+    return unit_runs(units, min(units, cus, PART_BLOCKS_S1 // 2), rows), spairs, rows
+
+
+def s1_regime(b_pairs: int, h: int, w: int, cus: int) -> dict:
+    runs, spairs, rows = s1_runs(b_pairs, h, w, cus)
+    return dict(kernel="conv1_pool", pairs=b_pairs, units=b_pairs * spairs * rows, **runs_regime(runs, spairs * rows))
+
+
+def s1_in_regime(r: dict) -> bool:
+    """pool_in_regime (a warm-up step, a statistics flush inside the loop, a run of at least 4 steps) with at least 4
+    units of the run's own (both halo slots, both raw patches and both exchange buffers are reused by units whose
+    outputs count, the counted vmcnt(2 * NST) runs behind two pooled rows' stores) and uneven runs."""
+    return pool_in_regime(r) and r["own"] >= 4 and r["least"] < r["most"]
+
+
+def s1_batch_for(h: int, w: int, cus: int) -> int:
+    """The smallest number of pairs that is a multiple of 3 and s1_in_regime."""
+    for b in range(3, 600, 3):
+        if s1_in_regime(s1_regime(b, h, w, cus)):
+            return b
+    raise AssertionError(f"no batch of {h} x {w} pairs reaches the fused stage 1's regime on {cus} CUs")
+
+
+def s1_owners(b_pairs: int, h: int, w: int, cus: int) -> dict:
+    """{(pair, strip pair, row): [(block, step), ...]} of the fused stage 1's units (the model of a correct launch gives
+    every unit one owner; a run's warm-up unit is not owned by it)."""
+    runs, spairs, rows = s1_runs(b_pairs, h, w, cus)
+    own = {}
+    for blk, (lo, hi, warm) in enumerate(runs):
+        for u in range(lo, hi):
+            own.setdefault((u // (spairs * rows), u // rows % spairs, u % rows), []).append((blk, u - lo + warm))
+    return own
 
 
 # ---- (b), (c) integer operands --------------------------------------------------------------------------------------------
@@ -294,3 +359,94 @@ def five_sums(tap_x64: torch.Tensor, tap_y64: torch.Tensor) -> torch.Tensor:
     """(B, C, 5) float64: sum x, sum y, sum x^2, sum y^2, sum xy over the pixels of the half-rounded taps (NHWC)."""
     x, y = tap_x64.half().double(), tap_y64.half().double()
     return torch.stack([x.sum((1, 2)), y.sum((1, 2)), (x * x).sum((1, 2)), (y * y).sum((1, 2)), (x * y).sum((1, 2))], -1)
+
+
+# ---- the fused stage 1 (csrc/nqa_conv1_pool.hip) on integers -------------------------------------------------------------
+# A raw pixel float32(mean_c + std_c v), v in S1_LEVELS, normalises to a float32 within 5e-7 of v by either form the
+# kernels use, i.e. to exactly v in half (and bfloat16); v = 0 is float32(mean_c) itself and gives exactly 0, as the zero
+# padding does.  With sparse integer conv1_1 and conv1_2, relu1_1 and relu1_2 (in [0, 63] on these frames) are integers,
+# and so is everything the fused kernel makes of them, as for the fused conv2_2 above.
+def s1_pixel(c: int, v: int) -> np.float32:
+    """The raw pixel of channel c that normalises to the integer v."""
+    return S1_MEAN[c] if v == 0 else np.float32(np.float64(S1_MEAN[c]) + np.float64(S1_STD[c]) * v)
+
+
+def _fma32(a, b, c) -> np.float32:
+    """fmaf through float64: the product of two float32 is exact there, the sum is rounded twice (the callers' margin)."""
+    return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+def s1_normalise(x: np.float32, c: int, form: str) -> np.float32:
+    """(x - mean) / std in float32 as conv1_pool_kernel ("fused": a multiplication by 1 / std with one residual
+    correction) or conv1_regw_kernel ("div") computes it."""
+    mean, std = S1_MEAN[c], S1_STD[c]
+    d = np.float32(x - mean)
+    if form == "div":
+        return np.float32(d / std)
+    isd = np.float32(np.float32(1.0) / std)
+    q0 = np.float32(d * isd)
+    return _fma32(_fma32(-q0, std, d), isd, q0)
+
+
+def _sparse_rows(seed: int, cout: int, k: int, terms: int, cover: int) -> np.ndarray:
+    """(cout, k) weights, `terms` of +-1 in each row: row o takes `cover` consecutive entries of a permutation of the k
+    positions, from entry o * cover on (cout * cover >= k: every position is used by some row), then its smallest draws."""
+    from nerf_qa_amd import synth
+    assert cout * cover >= k and cover <= terms
+    u = synth.uniform(seed, cout * k).reshape(cout, k)
+    perm = np.argsort(synth.uniform(seed + 1, k))
+    for o in range(cout):
+        u[o, perm[(o * cover + np.arange(cover)) % k]] = -1.0
+    sign = np.where(synth.uniform(seed + 2, cout * k).reshape(cout, k) < 0.5, -1.0, 1.0)
+    w = np.zeros((cout, k), dtype=np.float32)
+    pick = np.argsort(u, axis=1)[:, :terms]
+    np.put_along_axis(w, pick, np.take_along_axis(sign, pick, axis=1).astype(np.float32), axis=1)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def s1_convs():
+    """int_convs with conv1_1 and conv1_2 (layers 0, 1) replaced by sparse integer layers: S1_TERMS weights of +-1 per
+    output channel; conv1_1's bias in {-1 .. 2} (a halo pixel outside the image that is left at relu(bias) instead of
+    zero shows), conv1_2's in {-1, 0, 1}; every (input channel, tap) position of either layer is used by some output."""
+    from nerf_qa_amd import synth
+    convs = list(int_convs())
+    w0 = _sparse_rows(2900, 64, 27, S1_TERMS[0], 1).reshape(64, 3, 3, 3)
+    b0 = np.floor(synth.uniform(2903, 64) * 4.0).clip(0, 3).astype(np.float32) - 1.0
+    w1 = _sparse_rows(2910, 64, 576, S1_TERMS[1], 9).reshape(64, 64, 3, 3)
+    b1 = np.floor(synth.uniform(2913, 64) * 3.0).clip(0, 2).astype(np.float32) - 1.0
+    convs[0], convs[1] = (w0, b0), (w1, b1)
+    return convs
+
+
+@functools.lru_cache(maxsize=None)
+def s1_levels(h: int, w: int, seed: int = 0) -> torch.Tensor:
+    """Three base frames as their integer levels: float64 NCHW (3, 3, h, w) in S1_LEVELS.  Never modified."""
+    from nerf_qa_amd import synth
+    v = np.floor(synth.uniform(4100 + 7 * h + w + 1000 * seed, 9 * h * w) * len(S1_LEVELS)).clip(0, len(S1_LEVELS) - 1)
+    return torch.from_numpy(v.reshape(3, 3, h, w) + float(S1_LEVELS[0]))
+
+
+@functools.lru_cache(maxsize=None)
+def s1_frames(h: int, w: int, seed: int = 0) -> torch.Tensor:
+    """The raw frames of s1_levels: float32 NCHW (3, 3, h, w), pixels in [0, 1].  Never modified."""
+    lv = s1_levels(h, w, seed).numpy().astype(np.int64) - S1_LEVELS[0]
+    table = np.array([[s1_pixel(c, v) for v in S1_LEVELS] for c in range(3)], dtype=np.float32)
+    out = np.stack([table[c][lv[:, c]] for c in range(3)], axis=1)
+    assert out.dtype == np.float32 and 0.0 <= out.min() and out.max() <= 1.0
+    return torch.from_numpy(out)
+
+
+@functools.lru_cache(maxsize=None)
+def s1_ref(h: int, w: int, seed: int = 0) -> torch.Tensor:
+    """relu1_2 of the three base frames in float64 from their integer levels, NHWC (3, h, w, 64): integers in [0, 63],
+    asserted together with the integrality of relu1_1 and a bound below 2^24 on every partial sum of either layer."""
+    (w0, b0), (w1, b1) = (tuple(torch.from_numpy(t).double() for t in wb) for wb in s1_convs()[:2])
+    a = s1_levels(h, w, seed)
+    r11 = F.relu(F.conv2d(a, w0, b0, padding=1))
+    r12 = F.relu(F.conv2d(r11, w1, b1, padding=1))
+    for inp, wq, b in ((a, w0, b0), (r11, w1, b1)):
+        assert F.conv2d(inp.abs(), wq.abs(), b.abs(), padding=1).max().item() < 2 ** 24
+    assert bool((r11 == r11.round()).all()) and bool((r12 == r12.round()).all())
+    assert r11.max().item() <= 2048 and r12.max().item() <= 63, (r11.max().item(), r12.max().item())
+    return r12.permute(0, 2, 3, 1).contiguous()

@@ -1,5 +1,5 @@
-"""The persistent register-weights convolutions (nqa_conv.hip) and the fused conv2_2 + pool + statistics kernel
-(nqa_conv_pool.hip) against exact references IN THE REGIME IN WHICH THEIR SCHEDULING CODE RUNS (GPU box only).
+"""The persistent register-weights convolutions (nqa_conv.hip), the fused conv2_2 + pool + statistics kernel
+(nqa_conv_pool.hip) and the fused stage 1 (nqa_conv1_pool.hip) against exact references IN THE REGIME IN WHICH THEIR SCHEDULING CODE RUNS (GPU box only).
 
 Their grid is min(tiles, CUs); a block walks its tiles through a two- or three-slot LDS-DMA ring that it retires with one
 counted vmcnt per tile, and takes its tile list from an XCD-aware split.  With at most one tile per block -- all that the
@@ -29,11 +29,28 @@ grid on every 70-wide map), so ops.mixed_grid_launches() == 0 shows that no impl
 A failure names the pixels, rows, columns and channels hit and, from the model, the blocks that own the failing tiles and
 the step (and ring slot) of their walk: a ring bug follows the step, an address bug the position.
 
-Stage 1 (no integers: the normalisation), 150 x 130 frames, image k = base[k % 3]: the copies of a base image sit at
-different tile indices, owned by different blocks at different ring positions, and must be bit-equal within the launch;
-the three distinct images meet the bars these kernels are held to at small sizes (tests/test_gpu_ops.py: 3 x OUT_RTOL
-against F.conv2d in f16 / bf16, 2e-6 of the largest activation against float64 in f32s; tests/test_gpu_mixed_layers.py:
-the float64 replay of mixed_refs with 4 x the float32 replay's own distance and share in f16w).
+Stage 1 on random frames, 150 x 130, image k = base[k % 3]: the copies of a base image sit at different tile indices,
+owned by different blocks at different ring positions, and must be bit-equal within the launch; the three distinct images
+meet the bars these kernels are held to at small sizes (tests/test_gpu_ops.py: 3 x OUT_RTOL against F.conv2d in f16 /
+bf16, 2e-6 of the largest activation against float64 in f32s; tests/test_gpu_mixed_layers.py: the float64 replay of
+mixed_refs with 4 x the float32 replay's own distance and share in f16w).
+
+Stage 1 on integers.  The normalisation does not stand in the way: a raw pixel float32(mean_c + std_c v), v in {-1, 0, 1,
+2}, normalises to a float32 within 5e-7 of v by the fused kernel's corrected reciprocal and by conv1_regw_kernel's
+division alike (tests/test_persistent_refs.py replays both), i.e. to exactly v in half and bfloat16.  With the sparse
+integer conv1_1 and conv1_2 of persistent_refs.s1_convs (relu1_2 in [0, 63]):
+  conv1_regw_kernel<P> (f16, bf16), <PrecF16, 2> (f16w) through ops.conv1_fused, batches of batch_for("conv1_regw"):
+    BIT-EQUAL to relu1_2 in float64 rounded once (f32s stays on the random frames: its normalised pixel is a float32);
+  conv1_pool_kernel<RAGGED> + pool_seam_kernel + part_reduce_kernel (nqa_conv1_pool.hip) through ops.conv1_pool_stats,
+    x and y from two base triples, 150 x 130 (H % 4 = 2, W % 32 = 2: the last unit's second half-strip wholly outside),
+    37 x 70 (H odd: the last pooled row from one tap row), 64 x 96 (full units: the other instance) and 36 x 70 (the
+    ragged instance with a live last row in every strip: the reset of the carried row above), a batch in which
+    some run starts inside a strip (the warm-up unit), some run crosses a pair (flush_stats inside the loop), some run has
+    at least 4 units of its own (both halo slots, raw patches and exchange buffers reused, the counted vmcnt(2 * NST))
+    and runs are uneven; and one pair of 150 x 130, one unit per block, most behind a warm-up.  The bars of the fused
+    conv2_2 below: pooled halves within one unit in the last place of half(sqrt(S / 16 + 1e-12)) in float64, at most 2e-2
+    of them differing at all, copies bit-equal, the sums EXACTLY the float64 sums (a lane's moments: 4 samples per unit,
+    |deviation| <= 63, below 2^24 by the model's longest run inside a pair).
 
 The fused conv2_2 on the sparse integer set (tap in [0, 63]), x images then y images from another base triple, a batch in
 which some block's run starts inside a strip (warm-up step) and some block's run crosses an image pair (statistics flush
@@ -80,7 +97,7 @@ def blob(np_convs, dev):
     def get(kind, prec):
         if (kind, prec) not in made:
             from nerf_qa_amd import ops
-            convs = {"int": P.int_convs, "sparse": P.sparse_convs, "random": lambda: np_convs}[kind]()
+            convs = {"int": P.int_convs, "sparse": P.sparse_convs, "s1": P.s1_convs, "random": lambda: np_convs}[kind]()
             made[kind, prec] = ops.pack_vgg_weights(convs, prec).to(dev)
         return made[kind, prec]
     return get
@@ -313,3 +330,117 @@ def test_fused_conv_pool_stats_on_integers_past_one_unit(prec, nct, pool_refs, b
         raise AssertionError(f"{what}: {bad.shape[0]} sums differ from the exact float64 sums; first (pair, channel, sum) "
                              f"{bad[:6].tolist()}: got {g}, expected {e}; pairs hit {sorted(set(bad[:, 0].tolist()))}; sums hit "
                              f"{sorted(set(bad[:, 2].tolist()))}")
+
+
+# ---- stage 1 on integers: conv1_regw_kernel and the fused conv1_pool_kernel -----------------------------------------------
+@pytest.fixture(scope="module")
+def s1_refs():
+    """refs(h, w): relu1_2 of the two base triples on the integer set, the pooled references (three x frames, three y
+    frames) and the five sums of pair k = (x base k, y base k); made on first use, once for all tests."""
+    made = {}
+
+    def get(h, w):
+        if (h, w) not in made:
+            tx, ty = P.s1_ref(h, w, 0), P.s1_ref(h, w, 1)
+            assert tx.max() <= 63 and ty.max() <= 63
+            made[h, w] = (tx, P.pooled_refs(tx)[0], P.pooled_refs(ty)[0], P.five_sums(tx, ty))
+        return made[h, w]
+    return get
+
+
+@pytest.mark.parametrize("prec", ["f16", "bf16", "f16w"])
+@pytest.mark.parametrize("h,w", P.S1_SHAPES, ids=_ID)
+def test_stage1_integer_frames_are_bit_exact_past_one_tile(h, w, prec, s1_refs, blob, cus, dev):
+    """conv1_regw_kernel<P> (f16, bf16) and conv1_regw_kernel<PrecF16, 2> (f16w) through ops.conv1_fused."""
+    from nerf_qa_amd import ops
+    n = P.batch_for("conv1_regw", h, w, cus)
+    r = P.regime("conv1_regw", n, h, w, cus)
+    print(f"\n stage 1 on integers [{prec}] conv1_regw: {n}x{h}x{w}, {r['total']} tiles on {r['grid']} blocks of {cus} CUs, "
+          f"{r['least']}..{r['most']} tiles per block, ring of {r['ring']}")
+    assert P.in_regime(r) and r["most"] >= 4 and r["least"] < r["most"] and r["dummy_halo"], r
+    out = _nan_filled((n, h, w, 64), DT[prec], dev)
+    assert ops.conv1_fused(P.batch_of(P.s1_frames(h, w, 0), n).to(dev), blob("s1", prec), prec, out=out) is out
+    what = f"stage 1 on integers [{prec}] {n}x{h}x{w}"
+    _no_nan_left(out, what)
+    ref = P.batch_of(P.round_to(s1_refs(h, w)[0], DT[prec]), n)
+    _assert_bit_equal(out.cpu(), ref, what, "conv1_regw", n, h, w, cus, 1, 64)
+
+
+S1_POOL_CASES = [(h, w, None) for h, w in P.S1_SHAPES] + [(P.S1_H, P.S1_W, 1)]  # (None: the model's batch)
+
+
+@pytest.mark.parametrize("h,w,pairs", S1_POOL_CASES, ids=_ID)
+def test_fused_stage1_pool_stats_on_integers_past_one_unit(h, w, pairs, s1_refs, blob, cus, dev):
+    """conv1_pool_kernel<RAGGED> (RAGGED = false at 64 x 96 only) + pool_seam_kernel + part_reduce_kernel through
+    ops.conv1_pool_stats."""
+    from nerf_qa_amd import ops
+    ho, wo, spairs, rows = (h + 1) // 2, (w + 1) // 2, P.cdiv(w, 32), P.cdiv(h, 4)
+    b = P.s1_batch_for(h, w, cus) if pairs is None else pairs
+    r = P.s1_regime(b, h, w, cus)
+    print(f"\n fused stage 1: {b} pairs of {h}x{w}, {r['units']} units on {r['grid']} blocks of {cus} CUs, {r['least']}..{r['most']} "
+          f"steps per block (at most {r['own']} units of its own, {r['inside']} of one pair), {r['warm']} runs start inside a strip, "
+          f"{r['cross']} cross an image pair")
+    if pairs is None:
+        assert P.s1_in_regime(r) and r["warm"] >= 1 and r["cross"] >= 1 and r["most"] >= 4 and r["own"] >= 4 \
+            and r["least"] < r["most"], r
+    else:  # one unit per block where the device has a CU for each; most runs start with the warm-up unit
+        assert r["grid"] == min(r["units"], cus, P.PART_BLOCKS_S1 // 2) and 2 * r["warm"] > r["grid"], r
+        assert cus < r["units"] or (r["own"] == 1 and r["most"] == 2 and r["warm"] == r["units"] - spairs), r
+    assert 4 * r["inside"] * 63 ** 2 < 2 ** 24  # a lane's float32 moments between two flushes stay exact
+    _, px, py, want = s1_refs(h, w)
+    x, y = (P.batch_of(P.s1_frames(h, w, s), b).to(dev) for s in (0, 1))
+    pooled, sums = _nan_filled((2 * b, ho, wo, 64), torch.float16, dev), _nan_filled((b, 64, 5), torch.float64, dev)
+    res = ops.conv1_pool_stats(x, y, blob("s1", "f16"), "f16", pooled=pooled, sums=sums)
+    assert res[0] is pooled and res[1] is sums
+    what = f"fused stage 1, {b} pairs of {h}x{w}"
+    _no_nan_left(pooled, what)
+    nan = torch.isnan(sums).any(dim=2).nonzero().cpu()
+    assert nan.shape[0] == 0, f"{what}: {nan.shape[0]} (pair, channel) sums were never written; first {nan[:8].tolist()}"
+    own = P.s1_owners(b, h, w, cus)
+
+    def owners_of(bad):  # bad: rows of (image, pooled row, pooled column, channel); tap rows 2 y - 1 and 2 y feed pooled row y
+        units = {(i % b, min(2 * c // 32, spairs - 1), min(max(t, 0) // 4, rows - 1))
+                 for i, yy, c, _ in bad.tolist() for t in (2 * yy - 1, 2 * yy)}
+        hit = sorted({bs for u in units for bs in own[u]})
+        return f"(block, step) of the units behind them: first {hit[:8]}; steps hit {sorted({s for _, s in hit})}"
+
+    def report(mask, verb):
+        bad = mask.nonzero()
+        ch = sorted(set(bad[:, 3].tolist()))
+        return (f"{what}: {bad.shape[0]} pooled values {verb} (seam columns {int(mask[:, :, seam].sum())}, others "
+                f"{int(mask[:, :, ~seam].sum())}); first (image, row, column, channel) {bad[:6].tolist()}; rows hit "
+                f"{sorted(set(bad[:, 1].tolist()))}; columns hit {sorted(set(bad[:, 2].tolist()))}; channels hit {ch[:8]} .. "
+                f"{ch[-1]}; " + owners_of(bad[:4096]))
+
+    got = pooled.cpu()
+    seam = torch.zeros(wo, dtype=torch.bool)
+    seam[::8] = True  # pooled column 8 * s16: pool_seam_kernel's
+    bits = got.view(torch.int16)
+    copy_of = torch.cat([torch.arange(b) % 3, b + torch.arange(b) % 3]) if b >= 3 else torch.arange(2 * b)
+    unlike = bits != bits[copy_of]
+    print(f"   copies: {int(unlike.sum())} of {unlike.numel()} halves differ from the first three pairs'")
+    assert not bool(unlike.any()), report(unlike, "of the copies differ from images 0..2")
+    ref = torch.cat([P.batch_of(px, b), P.batch_of(py, b)])
+    d = (got.float() - ref.float()).abs()
+    ulp = ref.float().abs().clamp_min(6.1e-5) * 2.0 ** -10
+    differ, over = d > 0, d > ulp
+    frac = float(differ.float().mean())
+    print(f"   pooled: {int(differ.sum())} of {differ.numel()} halves differ from the float64 reference ({frac:.2e}; seam columns "
+          f"{int(differ[:, :, seam].sum())}, others {int(differ[:, :, ~seam].sum())}); beyond one unit in the last place: "
+          f"{int(over.sum())}")
+    assert not bool(over.any()), report(over, "are more than one unit in the last place from the float64 reference")
+    assert frac <= 2e-2, report(differ, f"({frac:.2e} of all) differ from the float64 reference")
+    ref_sums = want[torch.arange(b) % 3]
+    wrong = (sums.cpu() != ref_sums)
+    print(f"   sums: {int(wrong.sum())} of {wrong.numel()} differ from the exact float64 sums")
+    if bool(wrong.any()):
+        bad = wrong.nonzero()
+        g, e = sums.cpu()[wrong][:4].tolist(), ref_sums[wrong][:4].tolist()
+        runs = P.s1_runs(b, h, w, cus)[0]
+        per = spairs * rows
+        blocks = {p: [k for k, (lo, hi, _) in enumerate(runs) if lo < (p + 1) * per and hi > p * per][:12]
+                  for p in sorted(set(bad[:, 0].tolist()))[:4]}
+        raise AssertionError(f"{what}: {bad.shape[0]} sums differ from the exact float64 sums; first (pair, channel, sum) "
+                             f"{bad[:6].tolist()}: got {g}, expected {e}; pairs hit {sorted(set(bad[:, 0].tolist()))}; channels hit "
+                             f"{sorted(set(bad[:, 1].tolist()))[:16]}; sums hit {sorted(set(bad[:, 2].tolist()))}; blocks whose runs "
+                             f"hold units of the first pairs hit (at most 12 each): {blocks}")

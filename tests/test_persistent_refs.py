@@ -1,6 +1,8 @@
 """tests/persistent_refs.py without a GPU: the schedule model partitions every launch's tiles, the batches it chooses reach
 the persistent regime on every CU count the kernels may meet, and the integer references are exact where the GPU tests
-(tests/test_gpu_conv_persistent.py) rely on it.  Every precondition is printed."""
+(tests/test_gpu_conv_persistent.py) rely on it -- for the fused stage 1 too: its frames normalise to their integer levels
+exactly in half, its sparse weight set keeps relu1_2 in [0, 63], the model of launch_conv1_pool gives every unit one
+owner and its batches reach the kernel's regime.  Every precondition is printed."""
 import numpy as np
 import pytest
 import torch
@@ -121,3 +123,105 @@ def test_the_float32_replay_of_the_pool_equals_the_float64_one():
     x, y = tap, P.conv_ref(P.SPARSE_LAYER, P.H, P.W, sparse=True, seed=1)
     sums = P.five_sums(x, y)
     assert sums.shape == (3, 128, 5) and bool((sums == sums.round()).all()) and sums.max().item() < 2 ** 53
+
+
+# ---- the fused stage 1 ------------------------------------------------------------------------------------------------------
+def test_integer_frames_normalise_to_their_levels_exactly_in_half():
+    """Both forms of (x - mean) / std the kernels use, replayed in float32 (the fmas through float64: one further rounding
+    of ~6e-8 at most, far inside the margin): within 2^-13 of the level -- a quarter of half's spacing below 2, a
+    sixteenth of bfloat16's -- so the half (and the bfloat16) is the level itself; level 0 gives exactly 0."""
+    for c in range(3):
+        for v in P.S1_LEVELS:
+            x = P.s1_pixel(c, v)
+            assert x.dtype == np.float32 and 0.0 <= x <= 1.0
+            assert v != 0 or x == P.S1_MEAN[c]
+            for form in ("fused", "div"):
+                q = P.s1_normalise(x, c, form)
+                print(f" channel {c} level {v:2d}: pixel {x:.9g} -> {form:5s} {q:.9g} (off by {float(q) - v:+.2e})")
+                assert q.dtype == np.float32 and abs(float(q) - v) <= 2.0 ** -13 and abs(float(q) - v) <= 5e-7
+                assert float(np.float16(q)) == v and float(torch.tensor(float(q)).bfloat16()) == v
+                assert v != 0 or q == 0.0
+
+
+def test_stage1_integer_set_and_references():
+    from nerf_qa_amd import ops
+    convs = P.s1_convs()
+    assert len(convs) == ops.NUM_CONVS and all(np.array_equal(a[0], b[0]) for a, b in zip(convs[2:], P.int_convs()[2:]))
+    (w0, b0), (w1, b1) = convs[:2]
+    for w, b, terms in ((w0, b0, P.S1_TERMS[0]), (w1, b1, P.S1_TERMS[1])):
+        flat = w.reshape(64, -1)
+        assert set(np.unique(w)) <= {-1.0, 0.0, 1.0} and bool(((flat != 0).sum(1) == terms).all())
+        assert bool((flat != 0).any(0).all())  # every (input channel, tap) position is used by some output channel
+        assert bool((b == np.round(b)).all())
+    assert int((b0 >= 1).sum()) >= 8 and int((b0 < 0).sum()) >= 8 and set(np.unique(b1)) <= {-1.0, 0.0, 1.0}
+    for h, w in P.S1_SHAPES:
+        lv = [P.s1_levels(h, w, s) for s in (0, 1)]
+        assert not torch.equal(lv[0], lv[1]) and not torch.equal(lv[0][0], lv[0][1])
+        assert set(lv[0].unique().tolist()) == set(float(v) for v in P.S1_LEVELS)
+        for s in (0, 1):
+            fr = P.s1_frames(h, w, s)
+            assert fr.dtype == torch.float32 and fr.shape == (3, 3, h, w) and 0.0 <= fr.min() and fr.max() <= 1.0
+            for c in range(3):  # the frame is the level's pixel, bit for bit
+                for v in P.S1_LEVELS:
+                    assert bool((fr[:, c][lv[s][:, c] == v] == float(P.s1_pixel(c, v))).all())
+            tap = P.s1_ref(h, w, s)  # (asserts integrality, the partial-sum bounds and relu1_2 <= 63 itself)
+            print(f"\n {h}x{w} base triple {s}: relu1_2 in [{tap.min().item():.0f}, {tap.max().item():.0f}], "
+                  f"{float((tap > 0).double().mean()):.2f} of it positive")
+            assert tap.shape == (3, h, w, 64) and tap.min() >= 0 and tap.max() <= 63 and bool((tap == tap.round()).all())
+            assert float((tap > 0).double().mean()) > 0.2 and tap.max() >= 16
+            assert torch.equal(tap.half().double(), tap) and torch.equal(tap.bfloat16().double(), tap)
+            win = P.pool_window_sums(tap)
+            assert bool((win == win.round()).all()) and win.max().item() <= 16 * 3969 < 2 ** 24
+            p64, p32 = P.pooled_refs(tap)
+            share = float((p64.view(torch.int16) != p32.view(torch.int16)).double().mean())
+            print(f"   pooled halves of the float32 replay that differ from the float64 reference: {share:.2e} of {p64.numel()}")
+            assert share <= 2e-2 and p64.shape == (3, (h + 1) // 2, (w + 1) // 2, 64)
+        sums = P.five_sums(P.s1_ref(h, w, 0), P.s1_ref(h, w, 1))
+        assert sums.shape == (3, 64, 5) and bool((sums == sums.round()).all()) and sums.max().item() < 2 ** 53
+
+
+@pytest.mark.parametrize("cus", P.CU_COUNTS)
+def test_every_stage1_unit_has_exactly_one_owner(cus):
+    for h, w in P.S1_SHAPES + ((4, 32), (5, 33), (1080, 1920)):
+        for b in (1, 2, 3, 7) if h < 1080 else (1,):
+            runs, spairs, rows = P.s1_runs(b, h, w, cus)
+            units = b * spairs * rows
+            assert len(runs) == min(units, cus, 256) and (spairs, rows) == (P.cdiv(w, 32), P.cdiv(h, 4))
+            own = P.s1_owners(b, h, w, cus)
+            assert len(own) == units and all(len(v) == 1 for v in own.values()), (h, w, b, cus)
+            assert set(own) == {(n, sp, ty) for n in range(b) for sp in range(spairs) for ty in range(rows)}
+            blk, step = own[(b - 1, spairs - 1, rows - 1)][0]
+            lo, hi, warm = runs[blk]
+            assert hi == units and step == hi - lo - 1 + warm
+            assert all(warm == (lo < hi and lo % rows != 0) for lo, hi, warm in runs)
+    # pool_runs is the same rule with other units: its runs are unit_runs'
+    runs, strips, rows = P.pool_runs(6, P.H, P.W, cus, 2)
+    assert runs == P.unit_runs(6 * 2 * strips * rows, min(6 * 2 * strips * rows, cus, P.PART_BLOCKS), rows)
+
+
+@pytest.mark.parametrize("cus", P.CU_COUNTS)
+def test_stage1_batches_reach_the_fused_kernels_regime(cus):
+    for h, w in P.S1_SHAPES:
+        b = P.s1_batch_for(h, w, cus)
+        r = P.s1_regime(b, h, w, cus)
+        print(f"\n {cus} CUs fused stage 1 {h}x{w}: {b} pairs, {r['units']} units on {r['grid']} blocks, {r['least']}..{r['most']} "
+              f"steps per block (at most {r['own']} units of its own, {r['inside']} of one pair), {r['warm']} runs start inside a "
+              f"strip, {r['cross']} cross an image pair")
+        assert b % 3 == 0 and P.s1_in_regime(r)
+        assert r["warm"] >= 1 and r["cross"] >= 1 and r["most"] >= 4 and r["own"] >= 4 and r["least"] < r["most"]
+        assert b == 3 or not P.s1_in_regime(P.s1_regime(b - 3, h, w, cus))  # the smallest such batch
+        assert cus < 256 or 2 * b * h * w <= 64 * 150 * 130  # (a launch of well under a second)
+        # a lane's float32 moments take one sample per pass, four per unit, |deviation| <= 63, between two flushes
+        assert 1 <= r["inside"] <= r["own"] and 4 * r["inside"] * 63 ** 2 < 2 ** 24
+        # the conv1_regw companions of the same frames
+        if (h, w, cus) == (64, 96, 8):  # 24 tiles per image on 8 blocks: every batch is dealt evenly, no uneven tail
+            with pytest.raises(AssertionError, match="no batch"):
+                P.batch_for("conv1_regw", h, w, cus)
+            continue
+        n = P.batch_for("conv1_regw", h, w, cus)
+        assert n % 3 == 0 and P.in_regime(P.regime("conv1_regw", n, h, w, cus))
+    # one pair of 150 x 130: one unit per block where the device has the CUs, most runs start with a warm-up
+    r = P.s1_regime(1, P.S1_H, P.S1_W, cus)
+    assert r["units"] == 190 and r["grid"] == min(190, cus, 256)
+    if cus >= 190:
+        assert r["own"] == 1 and r["most"] == 2 and r["warm"] == 190 - 5 and r["cross"] == 0
