@@ -592,6 +592,26 @@ int nqa_dists_stats_nhwc_backward_from(const float *tx_nhwc, const float *ty_nhw
                                        long g_stride, void *coef, size_t coef_bytes, float *gx_nhwc, float *gy_nhwc,
                                        void *stream);
 
+/* ---- DISTS and A-DISTS as ONE loss against a prepared target (nerf_qa_amd/pair.py forward_target,
+ * autograd.PairTargetLoss): the backward chain is linear in the tap gradients, so the two metrics' tap gradients are
+ * summed and walked down once.  A-DISTS writes its NHWC tap gradient first (nqa_adists_ts_backward, out_nhwc = 1); the
+ * DISTS term is then added IN PLACE, instead of being written to a map of its own and added by a third pass.
+ *
+ *   nqa_dists_stats_nhwc_grad_y_add   the y side of nqa_dists_stats_nhwc_backward_from, accumulated: tx, ty, partials,
+ *       g_s1, g_s2, g_stride, coef as there; gy_inout dev float NHWC (B, H, W, C), read and written.
+ *       gy_inout[e] = gy_inout[e] + u[e] in float, u[e] exactly the float nqa_dists_stats_nhwc_backward_from writes to
+ *       gy_nhwc[e] (the fp64 fma chain rounded to float once, 0 where ty[e] <= 0): the result equals that call followed
+ *       by one float add, bit for bit.  One reader-writer per element, no atomics, bitwise repeatable; no pair reads
+ *       another pair's numbers; nothing is read back to the host.  Two launches (the coefficients as there, the
+ *       accumulating gradient), counted as NQA_K_STATS.
+ * The argument rules of nqa_dists_stats_nhwc_backward_from, refused on the host before any launch: C a power of two in
+ * 16..1024 and H * W <= 2^30 (else NQA_E_SHAPE); no null pointer, gy_inout included, B in 1..65535, H, W > 0,
+ * g_stride >= C, maps 16-byte and fp64 buffers 8-byte aligned (else NQA_E_ARG); a short partials or coefficient buffer is
+ * NQA_E_WORKSPACE (sizes: nqa_dists_stats_target_bytes, nqa_dists_stats_nhwc_backward_from_bytes). */
+int nqa_dists_stats_nhwc_grad_y_add(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C,
+                                    const void *partials, size_t partials_bytes, const float *g_s1, const float *g_s2,
+                                    long g_stride, void *coef, size_t coef_bytes, float *gy_inout, void *stream);
+
 /* ---- windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments;
  * nqa_window_moments.hip).  x, y: dev float NCHW maps taken as P = B * C independent planes of H x W; the window is the
  * normalised 21-tap Gaussian of sigma 7 as an outer product, valid correlation: h = H - 20, w = W - 20.

@@ -22,7 +22,8 @@ adists_backward_y, the head's backward in csrc/nqa_adists_backward.hip on top of
 Against a PREPARED TARGET (nerf_qa_amd/target.py: the fixed frame's taps computed once for the whole optimisation) both
 losses run one kept pyramid of y per step and nothing of x: DistsTargetSimilarities keeps the statistics' fp64 partials
 from its forward and starts the backward from them, AdistsTargetLoss runs adists_backward_y's two halves in its forward
-and its backward.
+and its backward.  PairTargetLoss is the two together for a loss that sums both metrics (nerf_qa_amd/pair.py,
+forward_target): one kept pyramid serves both heads, and the sum of their tap gradients goes down one chain.
 """
 from __future__ import annotations
 
@@ -309,14 +310,17 @@ def adists_backward_y(module, x, y, u):
 
 
 @torch.no_grad()
-def adists_y_forward(module, x, tx, y, keep=True):
+def adists_y_forward(module, x, tx, y, keep=True, kept=None):
     """The first half of adists_backward_y, up to D: x, y float32 contiguous (B,3,H,W), tx the five float NHWC taps of x
     (pyramid_taps).  Returns (D (B,), state) with state = (q, wgt, maps, acts, ty, pooled), what adists_y_backward
     needs; keep=False runs y through pyramid_taps instead of pyramid_keep (acts and pooled are then None: a value
-    without a gradient to follow)."""
+    without a gradient to follow).  kept = (acts, ty, pooled): y's pyramid as a caller already holds it (the pair loss,
+    which shares it with DISTS); no pyramid launch runs here then, and `keep` is not looked at."""
     b, _, h, w = x.shape
     prec, dev, ws = "f32s", x.device, module._ws
-    if keep:
+    if kept is not None:
+        acts, ty, pooled = kept
+    elif keep:
         acts, ty, pooled = pyramid_keep(module, y)
     else:
         acts, ty, pooled = None, pyramid_taps(module, y), None
@@ -342,7 +346,15 @@ def adists_y_forward(module, x, tx, y, keep=True):
 def adists_y_backward(module, x, tx, y, state, u):
     """The second half of adists_backward_y: dL/dy for dL/dD = u (B,) from what adists_y_forward(keep=True) returned:
     the six stages' gradients towards y's maps, then the chain."""
-    q, wgt, maps, acts, ty, pooled = state
+    acts, ty, pooled = state[3:]
+    g0, g_taps = _adists_y_tap_grads(module, x, tx, y, state, u)
+    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + g0
+
+
+def _adists_y_tap_grads(module, x, tx, y, state, u):
+    """(g0, g_taps) of adists_y_backward: the image term (B,3,H,W) and the five masked NHWC tap gradients, each a buffer
+    of its own that the caller may add to."""
+    q, wgt, maps, _, ty, _ = state
     prec, ws = "f32s", module._ws
     g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws)
     off, g_taps = 3, []
@@ -350,7 +362,7 @@ def adists_y_backward(module, x, tx, y, state, u):
         px, py = ops.nhwc_to_nchw_f32(tx[k - 1], prec), ops.nhwc_to_nchw_f32(ty[k - 1], prec)
         g_taps.append(ops.adists_ts_backward(px, py, q, wgt, maps[k][3], u, mask=True, coff=off, nhwc=True, ws=ws))
         off += ops.CHNS[k]
-    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + g0
+    return g0, g_taps
 
 
 class AdistsLossY(torch.autograd.Function):
@@ -374,16 +386,22 @@ class AdistsLossY(torch.autograd.Function):
         return None, adists_backward_y(ctx.module, x, y, u).to(y.dtype), None
 
 
-def adists_target_d(module, target, y, keep):
-    """(D, state) of adists_y_forward for a prepared target (nerf_qa_amd/target.py) as the x side.  A target is used
-    WHOLE: there is no slicing by NQA_MAX_WORKSPACE_GB here, and a batch whose scratch (_adists_y_bytes) would pass that
-    budget is refused with NqaError -- prepare or slice the target in smaller batches."""
+def adists_target_fits(target) -> None:
+    """NqaError for a target whose batch's A-DISTS scratch (_adists_y_bytes) would pass NQA_MAX_WORKSPACE_GB."""
     b, _, h, w = target.shape
     if ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b) < b:
         from ._lib import NqaError
         raise NqaError(f"forward_target: {b} pairs of {h} x {w} need {_adists_y_bytes(b, h, w)} bytes of scratch beside the "
                        "pyramid, more than NQA_MAX_WORKSPACE_GB allows: pass the target in slices (target[i:j])")
-    return adists_y_forward(module, target.x, list(target.taps), y.detach().float().contiguous(), keep=keep)
+
+
+def adists_target_d(module, target, y, keep, kept=None):
+    """(D, state) of adists_y_forward for a prepared target (nerf_qa_amd/target.py) as the x side.  A target is used
+    WHOLE: there is no slicing by NQA_MAX_WORKSPACE_GB here, and a batch whose scratch (_adists_y_bytes) would pass that
+    budget is refused with NqaError -- prepare or slice the target in smaller batches.  kept: y's pyramid where the
+    caller already holds it (adists_y_forward)."""
+    adists_target_fits(target)
+    return adists_y_forward(module, target.x, list(target.taps), y.detach().float().contiguous(), keep=keep, kept=kept)
 
 
 class AdistsTargetLoss(torch.autograd.Function):
@@ -526,6 +544,96 @@ class DistsTargetSimilarities(torch.autograd.Function):
             return None, None, None
         ctx.saved_tensors  # (y itself is in the state; this is autograd's check that it was not changed in place since)
         return dists_target_backward(ctx.module, ctx.target, ctx.state, g1, g2).to(ctx.dtype), None, None
+
+
+def pair_target_values(adists_module, target, y):
+    """(S1, S2, D) of a prepared target against y with no gradient to form: y's taps by pyramid_taps ONCE (the target's
+    owner runs them), then the statistics of dists_target_similarities and the head of adists_target_d on those taps.
+    Nothing is kept."""
+    y = y.detach().float().contiguous()
+    ty = pyramid_taps(target.owner(), y)
+    s1, s2, _ = dists_target_stats(target, y, ty)
+    d, _ = adists_target_d(adists_module, target, y, keep=False, kept=(None, ty, None))
+    return s1, s2, d
+
+
+@torch.no_grad()
+def pair_target_forward(adists_module, target, y):
+    """(S1, S2, D, state) of a prepared target against y (float32 contiguous) WITH what a gradient of either metric
+    needs: ONE kept pyramid of y (pyramid_keep on the target's owner), then dists_target_stats and the A-DISTS half of
+    adists_y_forward on it -- the launches of dists_target_forward and of adists_target_d on the same operands, so the
+    values are theirs bit for bit.  state = (kept, astate): the statistics' partials and tap 0's scratch, and
+    adists_y_forward's state, which holds the pyramid."""
+    kept_pyramid = pyramid_keep(target.owner(), y)
+    s1, s2, kept = dists_target_stats(target, y, kept_pyramid[1])
+    d, astate = adists_target_d(adists_module, target, y, keep=True, kept=kept_pyramid)
+    return s1, s2, d, (kept, astate)
+
+
+@torch.no_grad()
+def pair_target_backward(adists_module, target, y, state, g1, g2, u):
+    """dL/dy from pair_target_forward's state, given dL/dS1, dL/dS2 (each (B, 1475), or both None: DISTS unused) and
+    u = dL/dD (B,) on the device (or None: A-DISTS unused).  The chain is linear in the tap gradients: A-DISTS writes its
+    five masked NHWC tap gradients (_adists_y_tap_grads), DISTS' are ADDED into them in place
+    (ops.dists_stats_nhwc_grad_y_add: no map of their own, no add pass), and ONE pyramid_backward_device carries the sum
+    down; the image terms are added at the end.  An unused metric runs none of its launches, and the result is then
+    dists_target_backward's / adists_y_backward's bit for bit.  The backward's weight blobs are the target's owner's."""
+    kept, astate = state
+    acts, ty, pooled = astate[3:]
+    terms, g_taps = [], None
+    if u is not None:
+        g0, g_taps = _adists_y_tap_grads(adists_module, target.x, list(target.taps), y, astate, u)
+        terms.append(g0)
+    if g1 is not None:
+        parts, fx0, fy0, scratch = kept
+        g1, g2 = ops._f32c(g1), ops._f32c(g2)
+        off, fresh = 3, g_taps is None
+        if fresh:
+            g_taps = []
+        for k, (fx, fy, part) in enumerate(zip(target.taps, ty, parts)):
+            if fresh:
+                g_taps.append(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
+            else:
+                ops.dists_stats_nhwc_grad_y_add(fx, fy, part, g1, g2, off, g_taps[k])
+            off += fx.shape[-1]
+        terms.append(_image_stats_grad_from(fx0, fy0, scratch, g1, g2, (False, True))[1])
+    gy = pyramid_backward_device(target.owner(), acts, ty, pooled, g_taps, masked=True)
+    for term in terms:
+        gy = gy + term
+    return gy
+
+
+class PairTargetLoss(torch.autograd.Function):
+    """(prepared target, y) -> (S1, S2, a): DISTS' similarities, each (B, 1475), and A-DISTS' 1 - mean(D) (as_loss) or
+    1 - D (B,), all differentiable in y and hanging on ONE node: DistsTargetSimilarities and AdistsTargetLoss for a loss
+    that sums the two metrics (nerf_qa_amd/pair.py, forward_target).  forward = pair_target_forward, whose state the
+    Function keeps; backward = pair_target_backward with u = dL/dD formed on the device.  A value the loss never used
+    arrives as None and runs nothing.  No device -> host read in either direction."""
+
+    @staticmethod
+    def forward(ctx, y, target, adists_module, as_loss):
+        yf = y.detach().float().contiguous()
+        s1, s2, d, state = pair_target_forward(adists_module, target, yf)
+        ctx.owner = target.owner()  # (the target holds it weakly; the backward needs its weights)
+        ctx.adists, ctx.target, ctx.state, ctx.as_loss, ctx.dtype = adists_module, target, state, as_loss, y.dtype
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(yf)
+        return s1, s2, (1 - d.mean() if as_loss else 1 - d)
+
+    @staticmethod
+    def backward(ctx, g1, g2, ga):
+        if not ctx.needs_input_grad[0] or (g1 is None and g2 is None and ga is None):
+            return None, None, None, None
+        (y,) = ctx.saved_tensors
+        b, u = y.shape[0], None
+        if ga is not None:
+            g = ga.detach().float()
+            u = (g.reshape(1) * (-1.0 / b)).expand(b).contiguous() if ctx.as_loss else (-g).contiguous()
+        if (g1 is None) != (g2 is None):  # a loss over one of S1 / S2 alone: the other's upstream is zero
+            zero = torch.zeros((b, ops.TOTAL_CHNS), dtype=torch.float32, device=y.device)
+            g1, g2 = (zero if g1 is None else g1), (zero if g2 is None else g2)
+        gy = pair_target_backward(ctx.adists, ctx.target, y, ctx.state, g1, g2, u)
+        return gy.to(ctx.dtype), None, None, None
 
 
 class FeatsSimilarities(torch.autograd.Function):

@@ -25,6 +25,7 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_igemm_mixed_kernel", "conv3x3_reg
               "conv1_fused_kernel", "conv1_tile_kernel", "conv1_split_kernel", "conv1_regw_split_kernel", "conv3x3_regw_split_kernel", "pool_stats_kernel",
               "adists_window_lds_kernel", "adists_window_planar_kernel", "l2pool_kernel", "stats_nhwc_kernel",
               "stats_coef_kernel", "stats_grad_kernel", "loss_stats_sums_kernel", "loss_stats_fold_kernel", "loss_stats_coef_kernel", "loss_stats_grad_kernel",
+              "loss_stats_grad_y_add_kernel",
               "absmax_partial_kernel", "exponent_finish_kernel", "relu_mask_split16_kernel", "l2pool_backward_kernel",
               "conv1_1_backward_kernel", "window_moments_fwd_kernel", "window_moments_bwd_kernel",
               "group_stats_nhwc_kernel", "group_stats_nchw_kernel",

@@ -1064,6 +1064,29 @@ int nqa_dists_stats_nhwc_backward_from(const float *tx_nhwc, const float *ty_nhw
                                   static_cast<double *>(coef), gx_nhwc, gy_nhwc, static_cast<hipStream_t>(stream));
 }
 
+int nqa_dists_stats_nhwc_grad_y_add(const float *tx_nhwc, const float *ty_nhwc, int B, int H, int W, int C,
+                                    const void *partials, size_t partials_bytes, const float *g_s1, const float *g_s2,
+                                    long g_stride, void *coef, size_t coef_bytes, float *gy_inout, void *stream) {
+  const char *who = "dists_stats_nhwc_grad_y_add";
+  if (int rc = loss_target_bad(who, !tx_nhwc || !ty_nhwc || !partials || !g_s1 || !g_s2 || !coef || !gy_inout, B, H, W, C,
+                               g_stride,
+                               (uintptr_t)tx_nhwc | (uintptr_t)ty_nhwc | (uintptr_t)gy_inout |
+                                   (((uintptr_t)partials | (uintptr_t)coef) & 7)))
+    return rc;
+  const size_t need_part = nqa_dists_stats_target_bytes(B, H, W, C);
+  if (partials_bytes < need_part) {
+    set_error("%s: partials %zu < %zu bytes", who, partials_bytes, need_part);
+    return NQA_E_WORKSPACE;
+  }
+  const size_t need = nqa_dists_stats_nhwc_backward_from_bytes(B, C);
+  if (coef_bytes < need) {
+    set_error("%s: coefficient buffer %zu < %zu bytes", who, coef_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return loss_stats_grad_y_add(tx_nhwc, ty_nhwc, B, H * W, C, static_cast<const double *>(partials), g_s1, g_s2, g_stride,
+                               static_cast<double *>(coef), gy_inout, static_cast<hipStream_t>(stream));
+}
+
 size_t nqa_grad_exponent_bytes(int n, long per_image) {
   if (n <= 0 || per_image <= 0 || per_image % 4) return 0;
   return align_up((size_t)n * grad_exponent_nblk(per_image) * sizeof(unsigned), 256);

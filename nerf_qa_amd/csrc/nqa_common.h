@@ -335,6 +335,9 @@ int loss_stats_target(const float *tx, const float *ty, int B, int HW, int C, do
                       long s_stride, hipStream_t st);
 int loss_stats_backward_from(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
                              const float *g_s2, long g_stride, double *coef, float *gx, float *gy, hipStream_t st);
+// loss_stats_backward_from for the y side alone, added into the gradient gy already holds (gy += u, one float add)
+int loss_stats_grad_y_add(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
+                          const float *g_s2, long g_stride, double *coef, float *gy, hipStream_t st);
 int grad_exponent_nblk(long per_image);
 int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
 // ---- windowed moments of the A-DISTS head and their backward (nqa_window_moments.hip) ----

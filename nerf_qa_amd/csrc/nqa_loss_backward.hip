@@ -8,6 +8,8 @@
 //                            six fp64 numbers {mx, my, a, b, ox, oy} of nqa_stats_backward.hip
 //   loss_stats_grad_kernel   gx = (x > 0) * (ox + a (x - mx) + b (y - my)), gy likewise with x and y swapped: the affine
 //                            map centred and combined in fp64 and rounded to float once, the tap's own ReLU folded in
+//   loss_stats_grad_y_add_kernel   gy += that kernel's gy: the DISTS term of a tap gradient that already holds another
+//                            metric's (the pair loss of nerf_qa_amd/pair.py), one float add on top of the same fp64 chain
 //   absmax_partial_kernel    per (image, block) the largest |g| as its bit pattern (which orders like the value)
 //   exponent_finish_kernel   per image: k with max|g| 2^k in [128, 256) (0 for a zero or non-finite maximum), and the
 //                            running total of the chain
@@ -161,6 +163,46 @@ __global__ __launch_bounds__(256) void loss_stats_grad_kernel(const float *__res
   }
 }
 
+// grid (nblk, B), the plan and thread layout of loss_stats_grad_kernel.  gy += u, u the float that kernel writes for the y
+// side (the same fp64 chain, rounded to float once, 0 where y <= 0), then ONE float add: a tap gradient that is already
+// there (A-DISTS' for the same tap) takes the DISTS term without a pass of its own.  Each thread reads and writes its own
+// 16 bytes of gy and nobody else's.
+__global__ __launch_bounds__(256) void loss_stats_grad_y_add_kernel(const float *__restrict__ tx,
+                                                                    const float *__restrict__ ty, int HW, int C, int ppb,
+                                                                    const double *__restrict__ coef, float *__restrict__ gy) {
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y, blk = blockIdx.x;
+  const int G = C / 4, PL = 256 / G;
+  const int g = tid % G, pl = tid / G;
+  const int p_begin = blk * ppb;
+  const int p_end = min(HW, p_begin + ppb);
+  double mx[4], my[4], ca[4], cb[4], oy[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double *q = coef + ((size_t)b * C + g * 4 + e) * NQA_COEF;
+    mx[e] = q[0];
+    my[e] = q[1];
+    ca[e] = q[2];
+    cb[e] = q[3];
+    oy[e] = q[5];
+  }
+  const size_t base = (size_t)b * HW * C + g * 4;
+#pragma unroll 4
+  for (int p = p_begin + pl; p < p_end; p += PL) {
+    const size_t at = base + (size_t)p * C;
+    const f32x4 xv = *reinterpret_cast<const f32x4 *>(tx + at);
+    const f32x4 yv = *reinterpret_cast<const f32x4 *>(ty + at);
+    f32x4 acc = *reinterpret_cast<const f32x4 *>(gy + at);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double dx = (double)xv[e] - mx[e], dy = (double)yv[e] - my[e];
+      const float u = yv[e] > 0.f ? (float)fma(cb[e], dx, fma(ca[e], dy, oy[e])) : 0.f;
+      acc[e] = acc[e] + u;
+    }
+    *reinterpret_cast<f32x4 *>(gy + at) = acc;
+  }
+}
+
 // ---- the renormalisation exponents ----------------------------------------------------------------------------------
 // |float| as an unsigned integer orders like the value, every NaN above +inf: the maximum needs no float compare.
 // grid (nblk, n); g: n images of `units` 16-byte units each.
@@ -251,19 +293,33 @@ int loss_stats_target(const float *tx, const float *ty, int B, int HW, int C, do
   return check_launch("loss_stats_fold");
 }
 
+static int loss_stats_coef(int B, int HW, int C, const double *part, const float *g_s1, const float *g_s2, long g_stride,
+                           double *coef, hipStream_t st) {
+  TimedLaunch t(NQA_K_STATS, st);
+  loss_stats_coef_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, loss_stage_desc(HW, C), g_s1, g_s2, g_stride, coef);
+  return check_launch("loss_stats_coef");
+}
+
 // the coefficients from partials that are already there, then the gradient
 int loss_stats_backward_from(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
                              const float *g_s2, long g_stride, double *coef, float *gx, float *gy, hipStream_t st) {
   int rc;
-  {
-    TimedLaunch t(NQA_K_STATS, st);
-    loss_stats_coef_kernel<<<dim3(cdiv(C, 4), B), 256, 0, st>>>(part, loss_stage_desc(HW, C), g_s1, g_s2, g_stride, coef);
-    if ((rc = check_launch("loss_stats_coef"))) return rc;
-  }
+  if ((rc = loss_stats_coef(B, HW, C, part, g_s1, g_s2, g_stride, coef, st))) return rc;
   const int PL = 256 / (C / 4), gppb = PL * 8;
   TimedLaunch t(NQA_K_STATS, st);
   loss_stats_grad_kernel<<<dim3(cdiv(HW, gppb), B), 256, 0, st>>>(tx, ty, HW, C, gppb, coef, gx, gy);
   return check_launch("loss_stats_grad");
+}
+
+// the same for the y side alone, ADDED into a gradient that is already in gy
+int loss_stats_grad_y_add(const float *tx, const float *ty, int B, int HW, int C, const double *part, const float *g_s1,
+                          const float *g_s2, long g_stride, double *coef, float *gy, hipStream_t st) {
+  int rc;
+  if ((rc = loss_stats_coef(B, HW, C, part, g_s1, g_s2, g_stride, coef, st))) return rc;
+  const int PL = 256 / (C / 4), gppb = PL * 8;
+  TimedLaunch t(NQA_K_STATS, st);
+  loss_stats_grad_y_add_kernel<<<dim3(cdiv(HW, gppb), B), 256, 0, st>>>(tx, ty, HW, C, gppb, coef, gy);
+  return check_launch("loss_stats_grad_y_add");
 }
 
 int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,

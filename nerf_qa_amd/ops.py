@@ -1073,6 +1073,24 @@ def dists_stats_nhwc_backward_from(tx: torch.Tensor, ty: torch.Tensor, part: tor
     return gx, gy
 
 
+def dists_stats_nhwc_grad_y_add(tx: torch.Tensor, ty: torch.Tensor, part: torch.Tensor, g_s1: torch.Tensor,
+                                g_s2: torch.Tensor, col: int, gy: torch.Tensor) -> torch.Tensor:
+    """gy += the gy of dists_stats_nhwc_backward_from(tx, ty, part, g_s1, g_s2, col, need_x=False), in place: that call
+    followed by one float add, bit for bit, without the map and the pass of its own.  gy: contiguous float, ty's shape
+    (another metric's gradient of the same tap).  Returns gy."""
+    dev = _tap_pair("dists_stats_nhwc_grad_y_add", tx, ty, g_s1, g_s2, col)
+    assert part.dtype == torch.uint8 and part.is_contiguous() and part.device == dev
+    assert gy.shape == ty.shape and gy.dtype == torch.float32 and gy.is_contiguous() and gy.device == dev
+    b, h, w, c = tx.shape
+    nbytes = lib().nqa_dists_stats_nhwc_backward_from_bytes(b, c)
+    if not nbytes:
+        raise _lib.NqaError(f"dists_stats_nhwc_grad_y_add: unsupported tap shape {tuple(tx.shape)}")
+    coef = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_dists_stats_nhwc_grad_y_add, ptr(tx), ptr(ty), b, h, w, c, ptr(part), part.numel(),
+          ptr(g_s1) + 4 * col, ptr(g_s2) + 4 * col, g_s1.shape[1], ptr(coef), coef.numel(), ptr(gy), stream_ptr(dev))
+    return gy
+
+
 def grad_exponent(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
     """k[i] (int32, on the device) = the exponent with max|g[i]| * 2^k[i] in [128, 256), 0 where that maximum is 0 or
     not finite; k_total[i] += k[i].  g: float, image i = g[i].  Nothing comes back to the host."""

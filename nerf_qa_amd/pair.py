@@ -11,7 +11,9 @@ moments, the fp64 per-(pair, channel) sums of all six taps with the statistics k
 one finalisation launch on those sums (include/nqa.h, nqa_adists_dists_forward).  score_pair returns what the two
 modules' own forward calls return, for the cost of the A-DISTS call.
 
-What it does not do: image gradients (use the modules separately), and the DISTS fast rungs -- the pair runs in A-DISTS'
+What score_pair and score_group do not do: image gradients (that is forward_target below: both metrics as ONE loss
+against a prepared target, one kept pyramid of the render and one backward chain per step; for any other gradient use
+the modules separately), and the DISTS fast rungs -- the pair runs in A-DISTS'
 precision (f32 / f32s under its `auto`, or its named mode), which is at least as accurate as any rung DISTS' `auto`
 would pick; the DISTS calibration and the flat-frame guard are not consulted, and nothing here waits on the host after
 the first call for a (device, weights, size), so the call can be captured into a hipGraph.
@@ -40,7 +42,7 @@ def pair_precision(dists_model, adists_model, h: int, w: int) -> str:
     return prec
 
 
-def _check_same_weights(dists_model, adists_model, dev) -> None:
+def _check_same_weights(dists_model, adists_model, dev, who="score_pair") -> None:
     """Both modules must hold the same thirteen conv layers: compared on the device once per (device, weights of both
     modules) -- one host wait, on the first call only -- and remembered."""
     key = (dists_model._weights_key(dev), adists_model._weights_key(dev))
@@ -54,7 +56,7 @@ def _check_same_weights(dists_model, adists_model, dev) -> None:
             and torch.equal(a.bias.detach().to(dev), b.bias.detach().to(dev))
             for a, b in zip(dists_model._conv_modules(), adists_model._conv_modules()))
     if not same:
-        raise NqaError("score_pair: the DISTS and the A-DISTS module hold different VGG-16 weights "
+        raise NqaError(f"{who}: the DISTS and the A-DISTS module hold different VGG-16 weights "
                        f"({getattr(dists_model, 'vgg_source', '?')} vs {getattr(adists_model, 'vgg_source', '?')}); "
                        "one shared pyramid cannot serve both -- score with the modules separately")
 
@@ -108,3 +110,31 @@ def score_group(dists_model, adists_model, ref, renders):
         d, s1, s2 = ops.adists_forward_group(ref, renders, adists_model._packed_weights(dev, prec), prec, adists_model._ws,
                                              with_dists=True)
     return dists_model._weighted(s1, s2, False).reshape(r, k), (1 - d).reshape(r, k)
+
+
+def forward_target(dists_model, adists_model, target, y, batch_average=False, as_loss=True):
+    """(dists_model.forward_target(target, y, require_grad=True, batch_average=batch_average),
+    adists_model.forward_target(target, y, as_loss=as_loss)) for a loss that uses BOTH metrics against one prepared
+    target: each value has the shape, dtype and meaning of that module's own call, bit for bit.  Always in f32s; the
+    DISTS half goes through the module's own alpha / beta weighting, so alpha and beta receive gradients as everywhere.
+
+    Where y requires grad (grad mode on) both values hang on ONE autograd node (autograd.PairTargetLoss): a step is one
+    kept pyramid of y for both heads and, whatever loss is built from the two values, ONE backward chain over the sum
+    of their tap gradients -- against two pyramids and two chains for the two modules' calls.  A value the loss does not
+    use costs nothing in the backward, and y.grad is then the other module's own bit for bit.  Nothing is read back to
+    the host.  Without a gradient to form, y gives its taps once and both heads run on them; nothing is kept.
+
+    `target` comes from the prepare_target of EITHER module (with equal VGG weights both prepare the same taps).
+    ValueError for a target of a third module, one prepared before its owner's VGG weights changed, and a shape that
+    does not fit; NqaError for modules with different VGG weights, tensors off the GPU, and a batch whose A-DISTS
+    scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices)."""
+    from . import autograd, target as tgt
+    tgt.check_pair(dists_model, adists_model, target, y)
+    _check_same_weights(dists_model, adists_model, y.device, "forward_target")
+    autograd.adists_target_fits(target)
+    if torch.is_grad_enabled() and y.requires_grad:
+        s1, s2, a = autograd.PairTargetLoss.apply(y, target, adists_model, bool(as_loss))
+    else:
+        s1, s2, d = autograd.pair_target_values(adists_model, target, y)
+        a = 1 - d.mean() if as_loss else 1 - d
+    return dists_model._weighted(s1, s2, batch_average), a

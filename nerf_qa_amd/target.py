@@ -8,7 +8,8 @@ DistsTargetSimilarities / AdistsTargetLoss).
 
 A target belongs to the module that prepared it and to that module's VGG weights as they were then: it carries the
 module's `_weights_key`, and a target whose key no longer matches is refused.  It holds device tensors of one process and
-does not pickle, as the scratch fields of the modules never travel.
+does not pickle, as the scratch fields of the modules never travel.  (pair.forward_target, both metrics as one loss, takes
+a target of either of its two modules: check_pair.)
 """
 from __future__ import annotations
 
@@ -100,6 +101,26 @@ def check(module, target, y, kind: str) -> None:
     if target.kind != kind or target.owner() is not module:
         raise ValueError(f"this target was prepared by another module ({target.kind}): a target belongs to the module "
                          "instance whose prepare_target made it")
+    _check_current(module, target, y)
+
+
+def check_pair(dists_module, adists_module, target, y) -> None:
+    """check for pair.forward_target, which takes a target of EITHER of its two modules (both prepare the same taps when
+    they hold the same VGG weights, which the caller verifies): the target's owner must be one of the two, under its own
+    kind, and the target current for THAT module.  (A module's own forward_target goes on refusing
+    the other module's targets: check is unchanged.)"""
+    if not isinstance(target, PreparedTarget):
+        raise ValueError(f"forward_target expects what prepare_target returned, got {type(target).__name__}")
+    owner = target.owner()
+    if owner is None or not ((target.kind == "DISTS" and owner is dists_module) or
+                             (target.kind == "ADISTS" and owner is adists_module)):
+        raise ValueError(f"this target was prepared by another module ({target.kind}): pair.forward_target takes a target "
+                         "made by the prepare_target of one of its two modules")
+    _check_current(owner, target, y)
+
+
+def _check_current(module, target, y) -> None:
+    """What check and check_pair ask of y and of the target once its owner is settled."""
     _gpu_image("forward_target", y, "y")
     if y.device != target.device:
         raise NqaError("tensors on different devices")
