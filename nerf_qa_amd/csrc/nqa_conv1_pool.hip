@@ -454,8 +454,11 @@ __global__ __launch_bounds__(512) void conv1_pool_kernel(const float *__restrict
     for (int p = 0; p < NP; ++p) {
       const int i = p >> 2, e = p & 3;
       const double pv = piv[p], nn = n_lane, ax = s1x[p], ay = s1y[p];
+      // sum xy: the two cross terms are summed FIRST (nqa_moments.h, ShiftedMoments::raw): each product of two floats is
+      // exact in fp64, so their sum rounds once, and for y == x it is 2 pv ax exactly -- sum xy is then sum x^2 bit for bit
+      // (added one after the other to sxy, its last bit could differ from sum x^2 of the same map)
       double r[5] = {ax + nn * pv, ay + nn * pv, (double)s2x[p] + 2.0 * pv * ax + nn * pv * pv,
-                     (double)s2y[p] + 2.0 * pv * ay + nn * pv * pv, (double)sxy[p] + pv * ax + pv * ay + nn * pv * pv};
+                     (double)s2y[p] + 2.0 * pv * ay + nn * pv * pv, (double)sxy[p] + (pv * ax + pv * ay) + nn * pv * pv};
 #pragma unroll
       for (int s5 = 0; s5 < 5; ++s5) {
 #pragma unroll

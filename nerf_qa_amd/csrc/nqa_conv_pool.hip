@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
   // ---- weights ----
   u32x4 wf[2][G::NKS];
   float bia[NI][4];
-  int cur_ct = -1;
+  int cur_ct = -1, bias_ct = -1;
   auto load_weights = [&](int ct) {
     const int g = ct * 4 + wave;
 #pragma unroll
@@ -91,11 +91,19 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
 #pragma unroll
       for (int ks = 0; ks < G::NKS; ++ks)
         wf[i][ks] = load_wfrag<G::NKS>(wreg, g, i, ks, lane);
+    cur_ct = ct;
+  };
+  // The bias is NOT loaded with the weights: the epilogue of a step's last pass runs inside the NEXT step's first k loop,
+  // so when the channel tile changes between two steps the previous tile's last tap row still needs the previous tile's
+  // bias there (it got the new one: wrong taps in the last row of a (pair, channel tile) wherever that row is live, H % 4
+  // = 0).  The main loop loads it behind that k loop, where it hands the finished (pair, channel tile) over anyway.
+  auto load_bias = [&](int ct) {
+    const int g = ct * 4 + wave;
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int e = 0; e < 4; ++e) bia[i][e] = bias[NTERM == 2 ? g * 16 + 4 * c4 + e : g * 32 + i * 16 + 4 * c4 + e];
-    cur_ct = ct;
+    bias_ct = ct;
   };
   const float winv = NTERM == 2 ? bias[Cout] : 1.f;
 
@@ -298,8 +306,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
     for (int p = 0; p < NP; ++p) {
       const int i = p >> 2, e = p & 3;
       const double pv = piv[p], nn = n_lane, ax = s1x[p], ay = s1y[p];
+      // sum xy: the two cross terms are summed FIRST (nqa_moments.h, ShiftedMoments::raw): each product of two floats is
+      // exact in fp64, so their sum rounds once, and for y == x it is 2 pv ax exactly -- sum xy is then sum x^2 bit for bit
+      // (added one after the other to sxy, its last bit could differ from sum x^2 of the same map)
       double r[5] = {ax + nn * pv, ay + nn * pv, (double)s2x[p] + 2.0 * pv * ax + nn * pv * pv,
-                     (double)s2y[p] + 2.0 * pv * ay + nn * pv * pv, (double)sxy[p] + pv * ax + pv * ay + nn * pv * pv};
+                     (double)s2y[p] + 2.0 * pv * ay + nn * pv * pv, (double)sxy[p] + (pv * ax + pv * ay) + nn * pv * pv};
 #pragma unroll
       for (int s = 0; s < 5; ++s) {
 #pragma unroll
@@ -397,6 +408,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
     const bool warm = warm0 && step == 0;
     if (ct != cur_ct) {  // (block-uniform; compiler-tracked loads, retired with a wait the compiler can see: nqa_conv.hip)
       load_weights(ct);
+      if (step == 0) load_bias(ct);  // (no epilogue of an earlier step is under way)
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     }
     // halo `step` has landed: the only younger operations are the previous step's stores
@@ -419,6 +431,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_regw128_pool_kernel(
       if (pp == (warm ? 1 : 0) && (fresh || change)) {
         if (change) {
           flush_stats(flush_n, flush_ct);
+          if (ct != bias_ct) load_bias(ct);  // (the previous step's last epilogue has run: see load_bias)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (rare; keeps the counted waits of the ring exact)
         }
         if (!warm) {

@@ -26,6 +26,13 @@ import torch.nn.functional as F
 CU_COUNTS = (8, 64, 104, 256, 304)
 H, W = 37, 70                 # ragged under the 8 x 32 and the 4 x 32 tile, and under the pool kernel's 4 x 16 unit
 S1_H, S1_W = 150, 130         # stage-1 frames
+# the fused conv2_2's maps (a unit is 4 rows x 16 columns of an image pair) and what each reaches:
+#   37 x 70: the ragged instance; H % 4 = 1, so a strip's last tile has one live row and its last tap row is masked
+#   36 x 64: the RAGGED = false instance (no masking code, PF = 3 fragment sets in flight), every strip's last tile fully live
+#   36 x 70: the ragged instance with a live last row in every strip (the carried row above must be dropped at the next
+#            strip's top) and a last strip 6 columns wide
+#   38 x 48: the ragged instance where only H is ragged (H % 4 = 2): full strips, the last pooled row completes in pass 1
+POOL_SHAPES = ((37, 70), (36, 64), (36, 70), (38, 48))
 INT_LAYERS = (1, 2, 3, 4)
 IGEMM_INT_LAYERS = (7, 8)     # conv4_1, conv4_2: the same construction, for tests/test_gpu_conv_float_exact.py
 SPARSE_LAYER = 3
@@ -216,6 +223,34 @@ def pool_batch_for(h: int, w: int, cus: int, nct: int) -> int:
     raise AssertionError(f"no batch of {h} x {w} pairs reaches the fused kernel's regime on {cus} CUs")
 
 
+def pool_is_ragged(h: int, w: int) -> bool:
+    """conv_pool_stats_fused's choice of instance: RAGGED = H % 4 or W % 16."""
+    return bool(h % 4 or w % 16)
+
+
+def pool_in_strong_regime(r: dict) -> bool:
+    """What s1_in_regime asks of the fused stage 1, of the fused conv2_2: pool_in_regime (a warm-up step, a statistics
+    flush inside the loop, a run of at least 4 steps) with at least 4 units of the run's own (both ring slots reused by
+    units whose outputs count, the counted vmcnt(2 * NST) behind two pooled rows' stores) and uneven runs."""
+    return pool_in_regime(r) and r["own"] >= 4 and r["least"] < r["most"]
+
+
+def pool_strong_batch_for(h: int, w: int, cus: int, nct: int):
+    """The smallest number of pairs b >= 3 (any such b keeps the k % 3 copy map) in pool_in_strong_regime, or None where
+    no batch of up to 600 pairs is (few CUs under full tiles: every batch is dealt evenly)."""
+    for b in range(3, 601):
+        if pool_in_strong_regime(pool_regime(b, h, w, cus, nct)):
+            return b
+    return None
+
+
+def pool_single_unit_batch(h: int, w: int, cus: int, nct: int) -> int:
+    """The largest number of pairs whose units number at most min(cus, PART_BLOCKS): every block owns one unit, and a run
+    that starts inside a strip is a warm-up step, the wait vmcnt(NST) behind it, one unit and the drain.  0: not even one
+    pair fits."""
+    return min(cus, PART_BLOCKS) // (nct * cdiv(w, 16) * cdiv(h, 4))
+
+
 def pool_owner(img_pair: int, ct: int, sx: int, ty: int, b_pairs: int, h: int, w: int, cus: int, nct: int):
     """(block, step) of the fused kernel's unit (pair, channel tile, strip, tile row)."""
     runs, strips, rows = pool_runs(b_pairs, h, w, cus, nct)
@@ -353,6 +388,24 @@ def pooled_refs(tap64_nhwc: torch.Tensor):
     s32 = s.astype(np.float32)
     p32 = np.sqrt(s32 * np.float32(0.0625) + np.float32(1e-12), dtype=np.float32).astype(np.float16)
     return torch.from_numpy(p64), torch.from_numpy(p32)
+
+
+def leaked_window_sums(tap64_nhwc: torch.Tensor) -> torch.Tensor:
+    """pool_window_sums as a fused conv2_2 whose carried row is NOT dropped at a strip change would form it (c_keep stuck
+    at 1, one block walking an image's strips in run order): the squares of the last tap row of a strip's last tile (row
+    4 * ceil(H / 4) - 1; outside the image, i.e. zero, unless H % 4 = 0) at columns [16 s, 16 s + 16) stand as row -1 above
+    columns [16 (s + 1), 16 (s + 2)) of the same image.  A model of a WRONG kernel, used only to show on the references
+    which shapes can tell it from the right one; never compared with a kernel's output."""
+    n, h, w, c = tap64_nhwc.shape
+    sq = (tap64_nhwc * tap64_nhwc).permute(0, 3, 1, 2)
+    above = torch.zeros(n, c, 1, w, dtype=torch.float64)
+    last = 4 * cdiv(h, 4) - 1
+    if last < h:
+        above[:, :, 0, 16:] = sq[:, :, last, : w - 16]
+    k = torch.tensor([1.0, 2.0, 1.0], dtype=torch.float64)
+    ext = F.pad(torch.cat([above, sq], dim=2), (1, 1, 0, 1))  # row -1 in place of the top padding; zero right, left, below
+    s = F.conv2d(ext, (k[:, None] * k[None, :]).expand(c, 1, 3, 3).contiguous(), None, stride=2, groups=c)
+    return s.permute(0, 2, 3, 1).contiguous()
 
 
 def five_sums(tap_x64: torch.Tensor, tap_y64: torch.Tensor) -> torch.Tensor:

@@ -52,12 +52,27 @@ integer conv1_1 and conv1_2 of persistent_refs.s1_convs (relu1_2 in [0, 63]):
     of them differing at all, copies bit-equal, the sums EXACTLY the float64 sums (a lane's moments: 4 samples per unit,
     |deviation| <= 63, below 2^24 by the model's longest run inside a pair).
 
-The fused conv2_2 on the sparse integer set (tap in [0, 63]), x images then y images from another base triple, a batch in
-which some block's run starts inside a strip (warm-up step) and some block's run crosses an image pair (statistics flush
-inside the loop).  Pooled map: within one unit in the last place of half of sqrt(S / 16 + 1e-12) in float64, at most 2e-2
-of the values differing at all (the cap of test_gpu_conv_pool.py; the reference's float32 replay differs in none).  Sums:
-EXACTLY the float64 sums -- read off the kernel: the pivot, the deviations, their float32 moments (below 3969 H W <
-2^24), the float64 conversion in flush_stats, the shuffles and part_reduce_kernel all stay on integers below 2^53."""
+The fused conv2_2 on the sparse integer set (tap in [0, 63]), x images then y images from another base triple, at the
+maps of persistent_refs.POOL_SHAPES.  The instance conv_pool_stats_fused reaches (RAGGED = H % 4 or W % 16; NTERM = 1 in
+f16, one channel tile of 128; NTERM = 2 in f16w and f32m, two of 64):
+  37 x 70  conv3x3_regw128_pool_kernel<NTERM, true, false>   a strip's last tile has ONE live row, its last tap row is masked
+  36 x 64  conv3x3_regw128_pool_kernel<NTERM, false, false>  what 256^2 and 1080p frames run: no masking code, PF = 3
+                                                             fragment sets in flight; every strip's last tile fully live
+  36 x 70  conv3x3_regw128_pool_kernel<NTERM, true, false>   a live last row in every strip, a last strip 6 columns wide
+  38 x 48  conv3x3_regw128_pool_kernel<NTERM, true, false>   only H ragged (H % 4 = 2): the last pooled row completes in pass 1
+At 37 x 70 the batch is pool_batch_for's: some block's run starts inside a strip (warm-up step), some block's run crosses
+an image pair (statistics flush inside the loop), some run has 4 steps.  At the other three it is the stronger regime the
+fused stage 1 is held in: in addition some run has at least 4 units of its own and runs are uneven.  Only where a strip's
+last tap row is live (H % 4 = 0) can a carried row that is not dropped at a strip change (c_keep) show: at 37 x 70 that row
+is masked to zero (tests/test_persistent_refs.py shows both on the references alone).  (What these maps found in the
+two-term instances: the last tap row of a channel tile took the NEXT tile's bias, loaded with its weights before the
+previous step's last epilogue had run -- the last pooled row of the last strip, in f16w and f32m.)  36 x 64 also runs with the largest
+batch that leaves every block ONE unit: most runs are a warm-up step, the wait vmcnt(NST) behind it, one unit and the
+drain.  Pooled map: within one unit in the last place of half of sqrt(S / 16 + 1e-12) in float64, at most 2e-2 of the
+values differing at all (the cap of test_gpu_conv_pool.py; the reference's float32 replay differs in none), image k
+bit-equal to image k % 3 within each half of the batch.  Sums: EXACTLY the float64 sums -- read off the kernel: the pivot,
+the deviations, their float32 moments (4 samples per unit, |deviation| <= 63, below 2^24 by the model's longest run inside
+a pair), the float64 conversion in flush_stats, the shuffles and part_reduce_kernel all stay on integers below 2^53."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -269,67 +284,108 @@ def test_stage1_copies_are_bit_equal_and_each_meets_its_small_size_bar(prec, sta
 # ---- the fused conv2_2 + pool + statistics ----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def pool_refs():
-    """Taps of the two base triples on the sparse set, the pooled references (three x images, three y images) and the
-    five sums of pair k = (x base k, y base k), once for all modes."""
-    tx, ty = (P.conv_ref(P.SPARSE_LAYER, P.H, P.W, sparse=True, seed=s) for s in (0, 1))
-    assert tx.max() <= 63 and ty.max() <= 63
-    return P.pooled_refs(tx)[0], P.pooled_refs(ty)[0], P.five_sums(tx, ty)
+    """refs(h, w): taps of the two base triples on the sparse set, the pooled references (three x images, three y images)
+    and the five sums of pair k = (x base k, y base k); made on first use, once for all modes."""
+    made = {}
+
+    def get(h, w):
+        if (h, w) not in made:
+            tx, ty = (P.conv_ref(P.SPARSE_LAYER, h, w, sparse=True, seed=s) for s in (0, 1))
+            assert tx.max() <= 63 and ty.max() <= 63
+            made[h, w] = (P.pooled_refs(tx)[0], P.pooled_refs(ty)[0], P.five_sums(tx, ty))
+        return made[h, w]
+    return get
+
+
+# (H, W, batch): "regime" = the model's batch (37 x 70: pool_batch_for, as ever; the others: the stronger regime);
+# "single" = the largest batch that leaves every block one unit
+POOL_CASES = [(h, w, "regime") for h, w in P.POOL_SHAPES] + [(36, 64, "single")]
 
 
 @pytest.mark.parametrize("prec,nct", [("f16", 1), ("f16w", 2), ("f32m", 2)], ids=_ID)
-def test_fused_conv_pool_stats_on_integers_past_one_unit(prec, nct, pool_refs, blob, cus, dev):
-    """conv3x3_regw128_pool_kernel<NTERM, true, false> + pool_seam_kernel<false> + part_reduce_kernel through
-    ops.conv_pool_stats (NTERM = 1 in f16: one channel tile; 2 in the mixed modes: two)."""
+@pytest.mark.parametrize("h,w,batch", POOL_CASES, ids=_ID)
+def test_fused_conv_pool_stats_on_integers_past_one_unit(h, w, batch, prec, nct, pool_refs, blob, cus, dev):
+    """conv3x3_regw128_pool_kernel<NTERM, RAGGED, false> + pool_seam_kernel<false> + part_reduce_kernel through
+    ops.conv_pool_stats (NTERM = 1 in f16: one channel tile; 2 in the mixed modes: two; RAGGED = false at 36 x 64 only)."""
     from nerf_qa_amd import ops
-    h, w, ho, wo = P.H, P.W, (P.H + 1) // 2, (P.W + 1) // 2
-    b = P.pool_batch_for(h, w, cus, nct)
+    ho, wo, strips, rows = (h + 1) // 2, (w + 1) // 2, P.cdiv(w, 16), P.cdiv(h, 4)
+    if batch == "single":
+        b = P.pool_single_unit_batch(h, w, cus, nct)
+        assert b >= 1, f"not one pair of {h} x {w} fits {cus} CUs with a unit per block"
+    elif (h, w) == (P.H, P.W):
+        b = P.pool_batch_for(h, w, cus, nct)
+    else:
+        b = P.pool_strong_batch_for(h, w, cus, nct)
+        assert b is not None, f"no batch of {h} x {w} pairs reaches the fused conv2_2's stronger regime on {cus} CUs"
     r = P.pool_regime(b, h, w, cus, nct)
-    print(f"\n conv2_2 + pool + statistics [{prec}]: {b} pairs of {h}x{w}, {r['units']} units on {r['grid']} blocks of {cus} CUs, "
-          f"{r['least']}..{r['most']} steps per block, {r['warm']} runs start inside a strip, {r['cross']} cross an image pair")
-    assert P.pool_in_regime(r) and r["warm"] >= 1 and r["cross"] >= 1 and r["most"] >= 4, r
-    px, py, want = pool_refs
+    print(f"\n conv2_2 + pool + statistics [{prec}] conv3x3_regw128_pool_kernel<{2 if nct == 2 else 1}, "
+          f"{str(P.pool_is_ragged(h, w)).lower()}, false>: {b} pairs of {h}x{w}, {r['units']} units on {r['grid']} blocks of {cus} CUs, "
+          f"{r['least']}..{r['most']} steps per block (at most {r['own']} units of its own, {r['inside']} of one pair), "
+          f"{r['warm']} runs start inside a strip, {r['cross']} cross an image pair")
+    if batch == "single":  # one unit per block; every run but a strip's first starts with the warm-up step
+        assert r["grid"] == r["units"] <= min(cus, P.PART_BLOCKS) and r["own"] == 1 and r["most"] == 2, r
+        assert r["warm"] == r["units"] - b * nct * strips and 2 * r["warm"] > r["grid"], r
+    else:
+        assert P.pool_in_regime(r) and r["warm"] >= 1 and r["cross"] >= 1 and r["most"] >= 4, r
+        if (h, w) != (P.H, P.W):
+            assert P.pool_in_strong_regime(r) and r["own"] >= 4 and r["least"] < r["most"], r
+    assert 4 * r["inside"] * 63 ** 2 < 2 ** 24  # a lane's float32 moments between two flushes stay exact
+    px, py, want = pool_refs(h, w)
     inp = torch.cat([P.batch_of(P.int_base(P.SPARSE_LAYER, h, w, 0), b), P.batch_of(P.int_base(P.SPARSE_LAYER, h, w, 1), b)])
     pooled, sums = _nan_filled((2 * b, ho, wo, 128), torch.float16, dev), _nan_filled((b, 128, 5), torch.float64, dev)
     res = ops.conv_pool_stats(inp.half().to(dev), P.SPARSE_LAYER, blob("sparse", prec), prec, pooled=pooled, sums=sums)
     assert res[0] is pooled and res[1] is sums
-    what = f"conv2_2 + pool + statistics [{prec}] {b} pairs"
+    what = f"conv2_2 + pool + statistics [{prec}] {b} pairs of {h}x{w}"
     _no_nan_left(pooled, what)
     nan = torch.isnan(sums).any(dim=2).nonzero().cpu()
     assert nan.shape[0] == 0, f"{what}: {nan.shape[0]} (pair, channel) sums were never written; first {nan[:8].tolist()}"
 
-    def owners_of(bad):  # bad: rows of (image, pooled row, pooled column, channel)
-        hit = sorted({P.pool_owner(i % b, ch // (128 // nct), min(2 * c // 16, P.cdiv(w, 16) - 1), min(2 * y // 4, P.cdiv(h, 4) - 1),
-                                   b, h, w, cus, nct) for i, y, c, ch in bad.tolist()} - {None})
+    def owners_of(bad):  # bad: rows of (image, pooled row, pooled column, channel); tap rows 2 y - 1 and 2 y feed pooled row y
+        hit = sorted({P.pool_owner(i % b, ch // (128 // nct), min(2 * c // 16, strips - 1), min(max(t, 0) // 4, rows - 1),
+                                   b, h, w, cus, nct) for i, y, c, ch in bad.tolist() for t in (2 * y - 1, 2 * y)} - {None})
         return f"(block, step) of the units behind them: first {hit[:8]}; steps hit {sorted({s for _, s in hit})}"
 
+    def report(mask, verb):
+        bad = mask.nonzero()
+        ch = sorted(set(bad[:, 3].tolist()))
+        return (f"{what}: {bad.shape[0]} pooled values {verb} (seam columns {int(mask[:, :, seam].sum())}, others "
+                f"{int(mask[:, :, ~seam].sum())}); first (image, row, column, channel) {bad[:6].tolist()}; rows hit "
+                f"{sorted(set(bad[:, 1].tolist()))}; columns hit {sorted(set(bad[:, 2].tolist()))}; channels hit {ch[:8]} .. "
+                f"{ch[-1]}; " + owners_of(bad[:4096]))
+
     got = pooled.cpu()
+    seam = torch.zeros(wo, dtype=torch.bool)
+    seam[::8] = True  # pooled column 8 * sx: pool_seam_kernel's
+    # image k = base image k % 3 within each half of the batch: the copies sit at other units, blocks and ring slots
+    bits = got.view(torch.int16)
+    copy_of = torch.cat([torch.arange(b) % 3, b + torch.arange(b) % 3]) if b >= 3 else torch.arange(2 * b)
+    unlike = bits != bits[copy_of]
+    print(f"   copies: {int(unlike.sum())} of {unlike.numel()} halves differ from the first three pairs'")
+    assert not bool(unlike.any()), report(unlike, "of the copies differ from images 0..2")
     ref = torch.cat([P.batch_of(px, b), P.batch_of(py, b)])
     d = (got.float() - ref.float()).abs()
     ulp = ref.float().abs().clamp_min(6.1e-5) * 2.0 ** -10
     differ, over = d > 0, d > ulp
-    seam = torch.zeros(wo, dtype=torch.bool)
-    seam[::8] = True  # pooled column 8 * sx: pool_seam_kernel's
     frac = float(differ.float().mean())
     print(f"   pooled: {int(differ.sum())} of {differ.numel()} halves differ from the float64 reference ({frac:.2e}; seam columns "
           f"{int(differ[:, :, seam].sum())}, others {int(differ[:, :, ~seam].sum())}); beyond one unit in the last place: "
           f"{int(over.sum())}")
-    if bool(over.any()):
-        bad = over.nonzero()
-        raise AssertionError(f"{what}: {bad.shape[0]} pooled values are more than one unit in the last place from the float64 "
-                             f"reference (seam columns {int(over[:, :, seam].sum())}, others {int(over[:, :, ~seam].sum())}); first "
-                             f"(image, row, column, channel) {bad[:6].tolist()}; rows hit {sorted(set(bad[:, 1].tolist()))}; "
-                             f"columns hit {sorted(set(bad[:, 2].tolist()))}; " + owners_of(bad[:4096]))
-    assert frac <= 2e-2, (f"{what}: {frac:.2e} of the pooled values differ from the float64 reference (seam columns "
-                          f"{int(differ[:, :, seam].sum())}, others {int(differ[:, :, ~seam].sum())})")
+    assert not bool(over.any()), report(over, "are more than one unit in the last place from the float64 reference")
+    assert frac <= 2e-2, report(differ, f"({frac:.2e} of all) differ from the float64 reference")
     ref_sums = want[torch.arange(b) % 3]
     wrong = (sums.cpu() != ref_sums)
     print(f"   sums: {int(wrong.sum())} of {wrong.numel()} differ from the exact float64 sums")
     if bool(wrong.any()):
         bad = wrong.nonzero()
         g, e = sums.cpu()[wrong][:4].tolist(), ref_sums[wrong][:4].tolist()
+        runs = P.pool_runs(b, h, w, cus, nct)[0]
+        per = nct * strips * rows
+        blocks = {p: [k for k, (lo, hi, _) in enumerate(runs) if lo < (p + 1) * per and hi > p * per][:12]
+                  for p in sorted(set(bad[:, 0].tolist()))[:4]}
         raise AssertionError(f"{what}: {bad.shape[0]} sums differ from the exact float64 sums; first (pair, channel, sum) "
-                             f"{bad[:6].tolist()}: got {g}, expected {e}; pairs hit {sorted(set(bad[:, 0].tolist()))}; sums hit "
-                             f"{sorted(set(bad[:, 2].tolist()))}")
+                             f"{bad[:6].tolist()}: got {g}, expected {e}; pairs hit {sorted(set(bad[:, 0].tolist()))}; channels hit "
+                             f"{sorted(set(bad[:, 1].tolist()))[:16]}; sums hit {sorted(set(bad[:, 2].tolist()))}; blocks whose runs "
+                             f"hold units of the first pairs hit (at most 12 each): {blocks}")
 
 
 # ---- stage 1 on integers: conv1_regw_kernel and the fused conv1_pool_kernel -----------------------------------------------

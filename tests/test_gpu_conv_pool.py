@@ -226,3 +226,70 @@ def test_repeated_launches_are_bit_equal_on_ragged_maps(n, h, w, dev, blobs):
         q1, r1 = ops.conv1_pool_stats(x, y, blobs["f16"], "f16", pooled=_nan_filled_like(p1), sums=_nan_filled_like(s1))
         q2, r2 = ops.conv_pool_stats(t, 3, blobs["f16"], "f16", pooled=_nan_filled_like(p2), sums=_nan_filled_like(s2))
         assert torch.equal(p1, q1) and torch.equal(s1, r1) and torch.equal(p2, q2) and torch.equal(s2, r2)
+
+
+# ---- y = x: a map scored against itself ---------------------------------------------------------------------------------------
+def _assert_y_equals_x(pooled, sums, b, what):
+    """pooled (2b, ho, wo, C) halves, sums (b, C, 5) float64 of a launch whose y images ARE its x images: no tolerance."""
+    assert not bool(torch.isnan(pooled).any()) and not bool(torch.isnan(sums).any()), f"{what}: the NaN fill is still there"
+    for lhs, rhs, name in ((0, 1, "sum x != sum y"), (2, 3, "sum x^2 != sum y^2"), (2, 4, "sum x^2 != sum xy")):
+        unlike = (sums[..., lhs] != sums[..., rhs]).nonzero().cpu()
+        print(f"   {name}: {unlike.shape[0]} of {sums.shape[0] * sums.shape[1]} (pair, channel)")
+        if unlike.shape[0]:
+            p, c = unlike[0].tolist()
+            raise AssertionError(f"{what}: {name} in {unlike.shape[0]} (pair, channel), first {unlike[:6].tolist()}: "
+                                 f"{sums[p, c, lhs].item()!r} against {sums[p, c, rhs].item()!r}; channels hit "
+                                 f"{sorted(set(unlike[:, 1].tolist()))[:16]}")
+    assert torch.equal(sums[..., 0], sums[..., 1]) and torch.equal(sums[..., 2], sums[..., 3])
+    assert torch.equal(sums[..., 2], sums[..., 4])
+    assert torch.equal(pooled[:b].view(torch.int16), pooled[b:].view(torch.int16)), f"{what}: the y half of the pooled map differs"
+    assert float(sums[..., 2].min()) >= 0.0 and float(sums[..., 2].max()) > 0.0
+
+
+@pytest.mark.parametrize("h,w", [(36, 64), (37, 70)], ids=["36x64", "37x70"])
+@pytest.mark.parametrize("prec", ["f16", "f16w", "f32m"])
+def test_fused_conv_pool_stats_of_a_map_with_itself(h, w, prec, dev, blobs):
+    """y = x through conv3x3_regw128_pool_kernel on realistic values (the nearly constant channel 5 included), both
+    instances, a batch in which lane sums are flushed inside the loop and at the drain: sum x = sum y, sum x^2 = sum y^2 =
+    sum xy and the two halves of the pooled map, bit for bit.  With y == x a lane's moments of x and y are the same
+    numbers; flush_stats must then round sum xy as it rounds sum x^2 (the two cross terms summed first, as
+    ShiftedMoments::raw does; added one after the other they gave sum x^2 != sum xy in 1 of 2 816 (pair, channel) at 36 x 64
+    in f16).  There is NO x <-> y swap property here: the fused kernels pivot both images on the x
+    image's first activation, so a swap changes the pivot and the float moments -- bit-equality under a swap is
+    pool_stats_kernel's contract (separate pivots), not theirs."""
+    import persistent_refs as P
+    from nerf_qa_amd import ops
+    cus, nct = torch.cuda.get_device_properties(dev).multi_processor_count, 1 if prec == "f16" else 2
+    b = P.pool_strong_batch_for(h, w, cus, nct) or P.pool_batch_for(h, w, cus, nct)
+    r = P.pool_regime(b, h, w, cus, nct)
+    print(f"\n conv2_2 + pool + statistics [{prec}] y = x, RAGGED = {P.pool_is_ragged(h, w)}: {b} pairs of {h}x{w}, {r['units']} units "
+          f"on {r['grid']} blocks, {r['least']}..{r['most']} steps per block, {r['cross']} runs cross an image pair")
+    assert P.pool_in_regime(r) and r["cross"] >= 1, r
+    t = _input(b, h, w, dev, seed=h * 1000 + w + b)
+    pooled = _nan_filled_like(torch.empty(2 * b, (h + 1) // 2, (w + 1) // 2, 128, dtype=torch.float16, device=dev))
+    sums = _nan_filled_like(torch.empty(b, 128, 5, dtype=torch.float64, device=dev))
+    res = ops.conv_pool_stats(torch.cat([t, t]), 3, blobs[prec], prec, pooled=pooled, sums=sums)
+    assert res[0] is pooled and res[1] is sums
+    _assert_y_equals_x(pooled, sums, b, f"conv2_2 + pool + statistics [{prec}] {b} pairs of {h}x{w}, y = x")
+
+
+@pytest.mark.parametrize("h,w", [(64, 96), (37, 70)], ids=["64x96", "37x70"])
+def test_fused_stage1_pool_stats_of_a_frame_with_itself(h, w, dev, blobs):
+    """The same property of conv1_pool_kernel (both instances) on random frames with a constant region; no swap property
+    either, for the same reason."""
+    import persistent_refs as P
+    from nerf_qa_amd import ops
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    b = P.s1_batch_for(h, w, cus)
+    r = P.s1_regime(b, h, w, cus)
+    print(f"\n fused stage 1 y = x: {b} pairs of {h}x{w}, {r['units']} units on {r['grid']} blocks, {r['least']}..{r['most']} steps "
+          f"per block, {r['cross']} runs cross an image pair")
+    assert P.s1_in_regime(r) and r["cross"] >= 1, r
+    g = torch.Generator(device=dev).manual_seed(h * 977 + w + b)
+    x = torch.rand(b, 3, h, w, device=dev, generator=g)
+    x[:, :, : h // 2, : w // 3] = 1.0  # a constant region: exactly dead / constant channels
+    pooled = _nan_filled_like(torch.empty(2 * b, (h + 1) // 2, (w + 1) // 2, 64, dtype=torch.float16, device=dev))
+    sums = _nan_filled_like(torch.empty(b, 64, 5, dtype=torch.float64, device=dev))
+    res = ops.conv1_pool_stats(x, x.clone(), blobs["f16"], "f16", pooled=pooled, sums=sums)
+    assert res[0] is pooled and res[1] is sums
+    _assert_y_equals_x(pooled, sums, b, f"fused stage 1, {b} pairs of {h}x{w}, y = x")
