@@ -564,6 +564,48 @@ int nqa_l2pool_backward_scaled(const float *tap_nhwc, const float *g_pooled_nhwc
 int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16, const float *w_oihw_dev, const int *k,
                                 const int *k_total, int n, int H, int W, float *g_image_nchw, void *stream);
 
+/* ---- The same chain on HALF gradient maps: the loss path's second rung (grad_precision="f16" of DISTS / ADISTS,
+ * nerf_qa_amd/autograd.py, pyramid_backward_device).  The forward of a step, its values and its ReLU masks are untouched;
+ * the gradient between layers is a plain f16 NHWC map (2 bytes per element) instead of split16 records, the weights are
+ * halves, and a data-gradient convolution is ONE f16 MFMA per product with a float32 accumulator.  The per-image
+ * exponents put max|g| * 2^k in [8, 16), four octaves below the split16 chain's window, because a convolution's OUTPUT
+ * is a half here: |out| <= 16 * (largest L1 norm of a data-gradient filter) has to stay below 65504.
+ *
+ *   nqa_pack_conv_half               one 3x3 layer (float32 OIHW host array; cout % 64 == 0, cin % 32 == 0) as f16 rows,
+ *       each weight rounded to nearest even, zero bias: nqa_packed_conv_half_bytes = the rows (cout * cin * 9 * 2 bytes,
+ *       rounded up to 256) + the bias section ((cout + 1) * 4 bytes, rounded up to 256); 0 for a shape it refuses.  Rows
+ *       as in the packed blob's 16-bit layers: tiles [cout/64][cin/32] of [9 taps][64 rows][4 positions of 16 bytes],
+ *       chunk c (input channels 8c .. 8c+7 of the tile) of row n at position c ^ 2*((n>>2)&1) where cout % 128 == 0 (the
+ *       16x16x32 MFMA's swizzle), else c ^ ((n>>2)&3) (the 32x32x16 one's).
+ *   nqa_conv3x3_half                 that layer without bias or ReLU: f16 NHWC (n, H, W, cin) in, f16 NHWC (n, H, W, cout)
+ *       out (float32 accumulation, rounded to half once).  The implicit GEMM's f16 instances: 128-channel tiles where
+ *       cout % 128 == 0, else 64-channel tiles; 16-wide pixel tiles for W <= 16.  Maps and layer 16-byte aligned,
+ *       H * W * max(cin, cout) * 2 < 2^31.  Counted as NQA_K_CONV.
+ *   nqa_relu_mask_f16_scaled         out = (half)(g * 2^k[image]) where act > 0, else 0: g float or half NHWC
+ *       (g_is_half), act a float tapped map or split16 records, out a plain half NHWC map; the scaling is exact, the
+ *       conversion rounds to nearest even once.  C % 16 == 0, maps 16-byte aligned.  One launch (NQA_K_POOL).
+ *   nqa_grad_exponent_half           nqa_grad_exponent for this chain: k[i] with max|g_i| * 2^k[i] in [8, 16) (that
+ *       function's k minus 4), g float (per_image % 4 == 0) or half (per_image % 8 == 0), 16-byte aligned; the workspace
+ *       is nqa_grad_exponent_bytes(n, per_image).
+ *   nqa_l2pool_backward_scaled_half  nqa_l2pool_backward_scaled with a half g_pooled (8-byte aligned): taps, the tap's own
+ *       gradient and the output stay float; the result is that function's on the halves converted to float, bit for bit.
+ *   nqa_conv1_1_backward_scaled_half nqa_conv1_1_backward_scaled with a half g, likewise bit for bit.
+ * NQA_E_ARG for null pointers, non-positive sizes and misaligned maps, NQA_E_SHAPE for channel counts (or per_image) the
+ * kernels do not take, NQA_E_WORKSPACE for a short workspace. */
+size_t nqa_packed_conv_half_bytes(int cout, int cin);
+int nqa_pack_conv_half(const float *w_oihw, int cout, int cin, void *packed_host);
+int nqa_conv3x3_half(const void *in_f16_nhwc, int n, int H, int W, int cin, int cout, const void *packed_conv,
+                     void *out_f16_nhwc, void *stream);
+int nqa_relu_mask_f16_scaled(const void *g_nhwc, int g_is_half, const void *act_nhwc, int act_is_split16, int n,
+                             long pixels_per_image, int C, const int *k, void *out_f16, void *stream);
+int nqa_grad_exponent_half(const void *g, int g_is_half, int n, long per_image, void *workspace, size_t workspace_bytes,
+                           int *k, int *k_total, void *stream);
+int nqa_l2pool_backward_scaled_half(const float *tap_nhwc, const void *g_pooled_f16, const float *g_tap_nhwc,
+                                    const int *k_total, int n, int H, int W, int C, float *out_nhwc, void *stream);
+int nqa_conv1_1_backward_scaled_half(const void *g_f16_nhwc, const void *relu1_1_split16, const float *w_oihw_dev,
+                                     const int *k, const int *k_total, int n, int H, int W, float *g_image_nchw,
+                                     void *stream);
+
 /* ---- DISTS as a loss against a PREPARED TARGET (nerf_qa_amd/autograd.py, DistsTargetSimilarities): the statistics of
  * one tap pair split where the forward ends.  nqa_dists_stats_nhwc_backward is "sums, coefficients, gradient"; here the
  * forward runs the sums, keeps their per-block fp64 partials and forms S1 / S2 from them, and the backward starts from

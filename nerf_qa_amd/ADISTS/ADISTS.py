@@ -69,8 +69,12 @@ TWO_STREAM_MIN_PIXELS = 512 * 512  # ... of frames this large run as two half-ba
 
 
 class ADISTS(torch.nn.Module):
-    def __init__(self, window_size=21, precision=None, vgg16_path=None, loss_head=None):
+    def __init__(self, window_size=21, precision=None, vgg16_path=None, loss_head=None, grad_precision=None):
         super().__init__()
+        from ..DISTS_pytorch.DISTS_pt import resolve_grad_precision
+        # the precision of the gradient chain of a loss step ("f32s" | "f16": DISTS_pt.DEFAULT_GRAD_PRECISION); the
+        # forward, the head and the head's backward do not depend on it
+        self.grad_precision = resolve_grad_precision(grad_precision)
         self.loss_head = _check_loss_head(loss_head or os.environ.get("NQA_ADISTS_LOSS_HEAD", DEFAULT_LOSS_HEAD))
         if window_size != 21:
             raise NotImplementedError("the HIP windowed-statistics kernel is built for the 21x21 window "
@@ -140,6 +144,7 @@ class ADISTS(torch.nn.Module):
         d.setdefault("precision", os.environ.get("NQA_ADISTS_PRECISION", DEFAULT_PRECISION))
         d.setdefault("vgg_source", "unpickled module (Conv2d weights of stage1..5)")
         d.setdefault("loss_head", _check_loss_head(os.environ.get("NQA_ADISTS_LOSS_HEAD", DEFAULT_LOSS_HEAD)))
+        d.setdefault("grad_precision", "f32s")  # (a module pickled before the keyword existed)
         d.pop("_packed_key", None)
         d["_packed"], d["_ws"], d["_side"] = {}, ops.Workspace(), {}
 
@@ -235,8 +240,9 @@ class ADISTS(torch.nn.Module):
         """forward(x, y, as_loss) for x = a prepared target: 1 - mean(D), or 1 - D (B,) with as_loss=False (as_map is not
         offered).  Where y requires grad (grad mode on) a step is ONE kept pyramid of y, the head and its HIP backward
         (autograd.AdistsTargetLoss): nothing of x's pyramid runs and nothing is read back to the host; y.grad is that
-        of forward(x, y) with loss_head="auto" bit for bit.  Always in f32s, the precision of every gradient path (the
-        value is the staged head's, not the fused kernel's).  The target is used whole: NqaError if its batch does not
+        of forward(x, y) with loss_head="auto" bit for bit.  The forward and the head's backward always run in f32s
+        (the value is the staged head's, not the fused kernel's); the conv chain behind them in the module's
+        grad_precision ("f32s", or "f16": half gradient maps, the same value).  The target is used whole: NqaError if its batch does not
         fit NQA_MAX_WORKSPACE_GB (pass target[i:j] slices), and for tensors off the GPU; ValueError for a target of
         another module, one prepared before the VGG weights changed, and a shape that does not fit."""
         from .. import autograd, target as tgt

@@ -59,6 +59,20 @@ _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (profiles/r03_cal_classes.txt): gain 1.0 -> f16w below 224x224 pixels (f16: max 6.5e-5, tail 4.8 -- refused) and plain
 # f16 from there up (3.5e-5, tail 3.0); gain 1.3 -> f32m2 / f32m / f32m / f32m4 by class; gain 1.6 -> f32s everywhere.
 DEFAULT_PRECISION = "auto"
+# The precision of the GRADIENT chain of a loss step (autograd.pyramid_backward_device), apart from `precision`, which is
+# the forward's: "f32s" (the default: split16 gradient records, three-term products, a second accumulator) or "f16" (plain
+# half gradient maps, half weights, one MFMA per product; per-image power-of-two renormalisation into [8, 16)).  The
+# forward of a loss step, its values, its ReLU masks and the statistics' / A-DISTS head's backward are the same in both.
+DEFAULT_GRAD_PRECISION = "f32s"
+GRAD_PRECISIONS = ("f32s", "f16")
+
+
+def resolve_grad_precision(grad_precision=None) -> str:
+    """The argument, else $NQA_GRAD_PRECISION, else "f32s"; ValueError for anything but "f32s" / "f16"."""
+    v = grad_precision or os.environ.get("NQA_GRAD_PRECISION") or DEFAULT_GRAD_PRECISION
+    if v not in GRAD_PRECISIONS:
+        raise ValueError(f"grad_precision must be one of {GRAD_PRECISIONS}, got {v!r}")
+    return v
 AUTO_MIN_PIXELS = 128 * 128
 AUTO_F16_BUDGET = 6e-5  # on max |score_mode - score_f32s| over the calibration pairs ...
 AUTO_TAIL = 4.2         # ... and then only if max / rms looks like noise (384 Gaussian samples: 3.2 +- 0.3), not outliers;
@@ -263,8 +277,9 @@ def _build_stages(convs):
 
 
 class DISTS(torch.nn.Module):
-    def __init__(self, load_weights=True, from_feats=False, precision=None, vgg16_path=None):
+    def __init__(self, load_weights=True, from_feats=False, precision=None, vgg16_path=None, grad_precision=None):
         super().__init__()
+        self.grad_precision = resolve_grad_precision(grad_precision)  # (refused before anything is loaded)
         convs, self.vgg_source = load_vgg16_convs(vgg16_path)
         self.stage1, self.stage2, self.stage3, self.stage4, self.stage5 = _build_stages(convs)
         for param in self.parameters():
@@ -507,6 +522,7 @@ class DISTS(torch.nn.Module):
         super().__setstate__(state)
         d = self.__dict__
         d.setdefault("precision", os.environ.get("NQA_PRECISION", DEFAULT_PRECISION))
+        d.setdefault("grad_precision", DEFAULT_GRAD_PRECISION)  # (a module pickled before the keyword existed)
         d.setdefault("vgg_source", "unpickled module (Conv2d weights of stage1..5)")
         d["_packed"], d["_ws"], d["_auto"], d["_deltas"], d["_agreed"] = {}, ops.Workspace(), None, {}, {}
         d["_guard_streams"] = {}
@@ -603,8 +619,9 @@ class DISTS(torch.nn.Module):
         """forward(x, y, require_grad, batch_average) for x = a prepared target: the same shapes and return.  With
         require_grad=True and a y that requires grad (grad mode on) a step is ONE kept pyramid of y plus the backward
         chain (autograd.DistsTargetSimilarities) -- nothing of x runs, nothing is computed twice, nothing is read back
-        to the host -- and y.grad is forward's own bit for bit.  Otherwise y gives its taps and nothing is kept.  Always
-        in f32s, the precision of every gradient path.  alpha / beta get their gradients as in forward.  ValueError for
+        to the host -- and y.grad is forward's own bit for bit.  Otherwise y gives its taps and nothing is kept.  The
+        forward always runs in f32s; the backward chain in the module's grad_precision ("f32s", or "f16": half gradient
+        maps, the same values).  alpha / beta get their gradients as in forward.  ValueError for
         a target of another module, one prepared before the VGG weights changed, and a shape that does not fit;
         NqaError for tensors off the GPU."""
         from .. import autograd, target as tgt

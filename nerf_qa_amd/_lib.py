@@ -112,6 +112,13 @@ _SIGNATURES = {
     "nqa_relu_mask_split16_scaled": (_i, [_vp, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
     "nqa_l2pool_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "nqa_conv1_1_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "nqa_packed_conv_half_bytes": (_sz, [_i, _i]),
+    "nqa_pack_conv_half": (_i, [_vp, _i, _i, _vp]),
+    "nqa_conv3x3_half": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "nqa_relu_mask_f16_scaled": (_i, [_vp, _i, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
+    "nqa_grad_exponent_half": (_i, [_vp, _i, _i, C.c_long, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_l2pool_backward_scaled_half": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "nqa_conv1_1_backward_scaled_half": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "nqa_window_moments_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "nqa_window_moments_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nqa_adists_ts_backward_bytes": (_sz, [_i, _i, _i, _i]),

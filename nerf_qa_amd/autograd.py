@@ -75,17 +75,21 @@ def _stats_grad(fx, fy, g1, g2, dims):
     return gx, gy
 
 
-def _backward_blobs(module, dev):
-    """Per conv layer 1..12 the data-gradient layer: W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], packed once per weights."""
+def _backward_blobs(module, dev, grad_precision="f32s"):
+    """Per conv layer 1..12 the data-gradient layer: W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], packed once per weights
+    in the format of `grad_precision` ("f32s": split rows, ops.pack_conv_split; "f16": half rows, ops.pack_conv_half).
+    Only the set that is asked for is packed and kept: the other one (60 / 30 MB) is never built unasked."""
     key = module._weights_key(dev)
     cache = getattr(module, "_bwd_blobs", None)
     if cache is None or cache[0] != key:
-        convs = module._conv_modules()
-        blobs = {l: ops.pack_conv_split(convs[l].weight.detach().flip(2, 3).transpose(0, 1).contiguous()).to(dev)
-                 for l in range(1, 13)}
-        cache = (key, blobs, convs[0].weight.detach().float().contiguous().to(dev))
+        cache = (key, {}, module._conv_modules()[0].weight.detach().float().contiguous().to(dev))
         module.__dict__["_bwd_blobs"] = cache
-    return cache[1], cache[2]
+    if grad_precision not in cache[1]:
+        convs = module._conv_modules()
+        pack = ops.pack_conv_half if grad_precision == "f16" else ops.pack_conv_split
+        cache[1][grad_precision] = {l: pack(convs[l].weight.detach().flip(2, 3).transpose(0, 1).contiguous()).to(dev)
+                                    for l in range(1, 13)}
+    return cache[1][grad_precision], cache[2]
 
 
 @torch.no_grad()
@@ -118,7 +122,7 @@ def pyramid_backward(module, acts, taps, pooled, g_taps):
     gradients of a mean-type score are tiny (~1/N per pixel: 1e-8 at a few thousand pixels, where a half is already
     subnormal).  Everything here is LINEAR in g, so g is renormalised by an exact power of two before every layer
     (max |g| into [128, 256)) and the accumulated exponent taken out of the final image gradient."""
-    blobs, w0 = _backward_blobs(module, taps[0].device)
+    blobs, w0 = _backward_blobs(module, taps[0].device)  # (the host-scaled first form is f32s only)
     # A tapped map is a ReLU output: where it is 0 the gradient stops (torch's own rule, grad * (out > 0)).  Applied HERE,
     # before anything is renormalised: A-DISTS' F.normalize gives an exactly dead channel a gradient of the order of
     # 1 / eps = 1e12 times its upstream (5e8 measured on a 40 x 56 pair), which the mask discards -- but a renormalisation
@@ -166,13 +170,26 @@ def pyramid_taps(module, imgs):
     return taps
 
 
+def _grad_precision(module, grad_precision=None):
+    """The gradient chain's precision: the argument, else the module's setting ("f32s" for a module that has none)."""
+    v = grad_precision or getattr(module, "grad_precision", "f32s")
+    if v not in ("f32s", "f16"):
+        raise ValueError(f"grad_precision must be 'f32s' or 'f16', got {v!r}")
+    return v
+
+
 @torch.no_grad()
-def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False):
+def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False, grad_precision=None):
     """pyramid_backward with the renormalisation on the device: the exponents are taken per IMAGE by a reduction kernel
     and read by the scaled forms of the chain's kernels (csrc/nqa_loss_backward.hip, nqa_backward.hip), so nothing comes
     back to the host between the first and the last launch -- the step can be enqueued ahead, and the gradient of an
     image does not depend on what else is in the batch.  With one image the exponents are the host path's and the result
-    is pyramid_backward's bit for bit.  masked=True: g_taps already carry their taps' ReLU masks (g * (t > 0))."""
+    is pyramid_backward's bit for bit.  masked=True: g_taps already carry their taps' ReLU masks (g * (t > 0)).
+
+    grad_precision (None: the module's own, DISTS(grad_precision=) / ADISTS(grad_precision=)): "f32s" is the chain
+    above; "f16" is _pyramid_backward_half, the same walk on plain half gradient maps."""
+    if _grad_precision(module, grad_precision) == "f16":
+        return _pyramid_backward_half(module, acts, taps, g_taps, masked)
     blobs, w0 = _backward_blobs(module, taps[0].device)
     if not masked:  # BEFORE the first exponent is taken (see pyramid_backward)
         g_taps = [g * (t > 0) for g, t in zip(g_taps, taps)]
@@ -189,6 +206,32 @@ def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False):
             g = ops.l2pool_backward_scaled(taps[s - 1], g, g_taps[s - 1], K)  # the tap's own gradient * 2^K + pool gradient
         ops.grad_exponent(g, k, K)
     return ops.conv1_1_backward_scaled(g, acts[0], w0, k, K)  # d(ReLU) of relu1_1 and 2^-K inside
+
+
+def _pyramid_backward_half(module, acts, taps, g_taps, masked):
+    """The "f16" rung of pyramid_backward_device: the same activations, masks and walk, with the gradient between layers
+    as a plain half NHWC map.  Per layer and image: k with max|g| 2^k in [8, 16) (ops.grad_exponent_half), the masked,
+    scaled gradient rounded to half once (ops.relu_mask_f16_scaled), the data-gradient convolution on half weights with
+    one MFMA per product and a float32 accumulator, half out (ops.conv3x3_half).  g is float at the top and behind a pool
+    seam (whose taps, tap gradients and output stay float), half everywhere else; conv1_1's step takes the last half map
+    and applies 2^-K.  The window is four octaves below the split16 chain's because a convolution's output is a half
+    here: 16 times the largest L1 norm of a data-gradient filter has to stay below 65504."""
+    blobs, w0 = _backward_blobs(module, taps[0].device, "f16")
+    if not masked:
+        g_taps = [g * (t > 0) for g, t in zip(g_taps, taps)]
+    n, dev = taps[0].shape[0], taps[0].device
+    k = torch.empty(n, dtype=torch.int32, device=dev)
+    K = torch.zeros(n, dtype=torch.int32, device=dev)
+    g = ops._f32c(g_taps[4])
+    ops.grad_exponent_half(g, k, K)
+    for l in range(12, 0, -1):
+        gm = ops.relu_mask_f16_scaled(g, acts[l], l not in ops.TAP_LAYERS, k)
+        g = ops.conv3x3_half(gm, blobs[l], ops.CONV_CIN[l])
+        if l in (2, 4, 7, 10):
+            s = ops.CONV_STAGE[l]
+            g = ops.l2pool_backward_scaled_half(taps[s - 1], g, g_taps[s - 1], K)
+        ops.grad_exponent_half(g, k, K)
+    return ops.conv1_1_backward_scaled_half(g, acts[0], w0, k, K)
 
 
 def _image_stats(x, y):

@@ -28,6 +28,8 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_igemm_mixed_kernel", "conv3x3_reg
               "loss_stats_grad_y_add_kernel",
               "absmax_partial_kernel", "exponent_finish_kernel", "relu_mask_split16_kernel", "l2pool_backward_kernel",
               "conv1_1_backward_kernel", "window_moments_fwd_kernel", "window_moments_bwd_kernel",
+              "absmax_partial_half_kernel", "exponent_finish_half_kernel", "relu_mask_f16_kernel",
+              "l2pool_backward_half_kernel", "conv1_1_backward_half_kernel",
               "group_stats_nhwc_kernel", "group_stats_nchw_kernel",
               "adists_window_lds_group_kernel", "adists_window_planar_group_kernel",
               "adists_ts_coef_kernel", "adists_ts_dot_kernel", "adists_ts_fold_kernel", "adists_ts_apply_kernel",

@@ -1143,6 +1143,104 @@ int nqa_conv1_1_backward_scaled(const float *g_nhwc, const void *relu1_1_split16
                                  static_cast<hipStream_t>(stream));
 }
 
+// ---- the half gradient chain (grad_precision "f16"; nqa_backward.hip, nqa_loss_backward.hip, conv3x3_half_generic) ----
+int nqa_conv3x3_half(const void *in_f16_nhwc, int n, int H, int W, int cin, int cout, const void *packed_conv,
+                     void *out_f16_nhwc, void *stream) {
+  if (!in_f16_nhwc || !packed_conv || !out_f16_nhwc) {
+    set_error("conv3x3_half: null pointer");
+    return NQA_E_ARG;
+  }
+  if (cout <= 0 || cin <= 0 || cout % 64 || cin % 32) {
+    set_error("conv3x3_half: cout %d must be a multiple of 64, cin %d of 32", cout, cin);
+    return NQA_E_SHAPE;
+  }
+  if (bad_dims("conv3x3_half", n, H, W, NQA_PREC_F16, cin > cout ? cin : cout)) return NQA_E_ARG;
+  if (((uintptr_t)in_f16_nhwc | (uintptr_t)out_f16_nhwc | (uintptr_t)packed_conv) & 15) {
+    set_error("conv3x3_half: the maps and the packed layer must be 16-byte aligned");
+    return NQA_E_ARG;
+  }
+  return conv3x3_half_generic(in_f16_nhwc, n, H, W, cin, cout, packed_conv, conv_half_bias_off(cout, cin), out_f16_nhwc,
+                              static_cast<hipStream_t>(stream));
+}
+
+int nqa_relu_mask_f16_scaled(const void *g_nhwc, int g_is_half, const void *act_nhwc, int act_is_split16, int n,
+                             long pixels_per_image, int C, const int *k, void *out_f16, void *stream) {
+  if (!g_nhwc || !act_nhwc || !k || !out_f16 || n <= 0 || pixels_per_image <= 0) {
+    set_error("relu_mask_f16_scaled: bad argument (null pointer, n %d or %ld pixels per image not positive)", n,
+              pixels_per_image);
+    return NQA_E_ARG;
+  }
+  if (C <= 0 || C % 16) {
+    set_error("relu_mask_f16_scaled: C %d must be a positive multiple of 16", C);
+    return NQA_E_SHAPE;
+  }
+  if (((uintptr_t)g_nhwc | (uintptr_t)act_nhwc | (uintptr_t)out_f16) & 15) {
+    set_error("relu_mask_f16_scaled: the maps must be 16-byte aligned");
+    return NQA_E_ARG;
+  }
+  if ((long)n * pixels_per_image > (1L << 31) * 256 / (C / 8)) {  // (the grid is one 32-bit count of 256-thread blocks)
+    set_error("relu_mask_f16_scaled: %d x %ld pixels of %d channels are more than one launch takes", n, pixels_per_image, C);
+    return NQA_E_SHAPE;
+  }
+  return relu_mask_f16_scaled(g_nhwc, g_is_half != 0, act_nhwc, act_is_split16, n, pixels_per_image, C, k, out_f16,
+                              static_cast<hipStream_t>(stream));
+}
+
+int nqa_grad_exponent_half(const void *g, int g_is_half, int n, long per_image, void *workspace, size_t workspace_bytes,
+                           int *k, int *k_total, void *stream) {
+  if (!g || !workspace || !k || n <= 0 || n > 65535 || per_image <= 0 || ((uintptr_t)g & 15)) {
+    set_error("grad_exponent_half: bad argument (null pointer, g not 16-byte aligned, n %d outside 1..65535 or per_image "
+              "%ld <= 0)", n, per_image);
+    return NQA_E_ARG;
+  }
+  if (per_image % (g_is_half ? 8 : 4)) {
+    set_error("grad_exponent_half: per_image %ld must be a multiple of %d", per_image, g_is_half ? 8 : 4);
+    return NQA_E_SHAPE;
+  }
+  const size_t need = nqa_grad_exponent_bytes(n, per_image);
+  if (workspace_bytes < need) {
+    set_error("grad_exponent_half: workspace %zu < %zu bytes", workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return grad_exponent_half(g, g_is_half != 0, n, per_image, static_cast<unsigned *>(workspace), k, k_total,
+                            static_cast<hipStream_t>(stream));
+}
+
+int nqa_l2pool_backward_scaled_half(const float *tap_nhwc, const void *g_pooled_f16, const float *g_tap_nhwc,
+                                    const int *k_total, int n, int H, int W, int C, float *out_nhwc, void *stream) {
+  if (!tap_nhwc || !g_pooled_f16 || !g_tap_nhwc || !k_total || !out_nhwc) {
+    set_error("l2pool_backward_scaled_half: null pointer");
+    return NQA_E_ARG;
+  }
+  if (C <= 0 || C % 16) {
+    set_error("l2pool_backward_scaled_half: C %d must be a positive multiple of 16", C);
+    return NQA_E_SHAPE;
+  }
+  if (bad_dims("l2pool_backward_scaled_half", n, H, W, NQA_PREC_F32, 0)) return NQA_E_ARG;
+  if ((((uintptr_t)tap_nhwc | (uintptr_t)g_tap_nhwc | (uintptr_t)out_nhwc) & 15) || ((uintptr_t)g_pooled_f16 & 7)) {
+    set_error("l2pool_backward_scaled_half: the float maps must be 16-byte aligned, the half map 8-byte");
+    return NQA_E_ARG;
+  }
+  return l2pool_backward_scaled_half(tap_nhwc, g_pooled_f16, g_tap_nhwc, k_total, n, H, W, C, out_nhwc,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int nqa_conv1_1_backward_scaled_half(const void *g_f16_nhwc, const void *relu1_1_split16, const float *w_oihw_dev,
+                                     const int *k, const int *k_total, int n, int H, int W, float *g_image_nchw,
+                                     void *stream) {
+  if (!g_f16_nhwc || !w_oihw_dev || !k || !k_total || !g_image_nchw) {
+    set_error("conv1_1_backward_scaled_half: null pointer");
+    return NQA_E_ARG;
+  }
+  if (bad_dims("conv1_1_backward_scaled_half", n, H, W, NQA_PREC_F32, 0)) return NQA_E_ARG;
+  if ((uintptr_t)g_f16_nhwc & 1) {
+    set_error("conv1_1_backward_scaled_half: the half map must be 2-byte aligned");
+    return NQA_E_ARG;
+  }
+  return conv1_1_backward_scaled_half(g_f16_nhwc, relu1_1_split16, w_oihw_dev, k, k_total, n, H, W, g_image_nchw,
+                                      static_cast<hipStream_t>(stream));
+}
+
 // ---- windowed moments of the A-DISTS head (nqa_window_moments.hip) ---------------------------------------------------
 static int window_bad_shape(const char *who, int P, int H, int W) {
   if (P <= 0) {

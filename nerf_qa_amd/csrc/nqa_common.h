@@ -222,6 +222,8 @@ size_t regw_offset(int layer, int prec);        // section 5, layer 1..4
 size_t layer0_m16_offset(int prec);             // section 6
 // a layer packed alone by nqa_pack_conv_split: f32s rows, then (at this offset) a zero bias[cout] and 1/s
 size_t conv_split_bias_off(int cout, int cin);
+// a layer packed alone by nqa_pack_conv_half: f16 rows (kRows16), then (at this offset) a zero bias[cout]
+size_t conv_half_bias_off(int cout, int cin);
 
 // Where each stage's partial sums live and how to fold them (finalize_kernel).
 struct StageDesc {
@@ -323,6 +325,17 @@ int l2pool_backward_scaled(const float *x, const float *gy, const float *g_tap, 
                            int C, float *out, hipStream_t st);
 int conv1_1_backward_scaled(const float *g, const void *act0_split16, const float *w_oihw, const int *kexp,
                             const int *ktot, int n, int H, int W, float *gimg, hipStream_t st);
+// the half gradient chain (grad_precision "f16"): plain half NHWC gradient maps, per-image exponents with max|g| 2^k in
+// [8, 16); g_half: whether g is a half map (else float)
+int relu_mask_f16_scaled(const void *g, int g_half, const void *act, int act_split, int n, long pix_per_image, int C,
+                         const int *kexp, void *out, hipStream_t st);
+int l2pool_backward_scaled_half(const float *x, const void *gy_f16, const float *g_tap, const int *ktot, int n, int H, int W,
+                                int C, float *out, hipStream_t st);
+int conv1_1_backward_scaled_half(const void *g_f16, const void *act0_split16, const float *w_oihw, const int *kexp,
+                                 const int *ktot, int n, int H, int W, float *gimg, hipStream_t st);
+int grad_exponent_half(const void *g, int g_half, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
+int conv3x3_half_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off, void *out,
+                         hipStream_t st);
 // ---- the loss path (nqa_loss_backward.hip): statistics' gradient on NHWC taps, renormalisation exponents ----
 size_t loss_stats_backward_doubles(int B, int HW, int C);
 int loss_stats_backward(const float *tx, const float *ty, int B, int HW, int C, const float *g_s1, const float *g_s2,

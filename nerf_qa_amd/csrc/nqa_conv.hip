@@ -2636,6 +2636,24 @@ int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout
                 : launch_igemm<PrecF32S, 1, 4, 2, 2, 32, false, 1, true>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
 }
 
+// The same for the half gradient chain (grad_precision "f16"): plain f16 NHWC in and out, weights as one f16-format layer
+// blob (kRows16 rows + zero bias, nqa_pack_conv_half), no ReLU, ONE MFMA per product.  These are the forward's own f16
+// instances of the implicit GEMM and conv3x3_split_generic's tile choices: 128-channel tiles on the 16x16x32 MFMA where
+// cout % 128 == 0 (rows packed with its swizzle), else 64-channel tiles on the 32x32x16 one; 16-wide tiles for W <= 16.
+int conv3x3_half_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off,
+                         void *out, hipStream_t st) {
+  const char *wpk = static_cast<const char *>(blob);
+  const float *bias = reinterpret_cast<const float *>(wpk + bias_off);
+  const float fl = -INFINITY;
+  const bool narrow = W <= 16;
+  if (cout % 128 == 0) {
+    return narrow ? launch_igemm<PrecF16, 2, 2, 2, 2, 16, true, 1>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
+                  : launch_igemm<PrecF16, 2, 2, 2, 2, 32, true, 1>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
+  }
+  return narrow ? launch_igemm<PrecF16, 1, 4, 2, 2, 16, false, 1>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl)
+                : launch_igemm<PrecF16, 1, 4, 2, 2, 32, false, 1>(in, n, H, W, cin, cout, wpk, bias, out, 0, st, fl);
+}
+
 int conv3x3(const void *in, int n, int H, int W, int layer, const void *packed, int prec, void *out, hipStream_t st) {
   const char *p = static_cast<const char *>(packed);
   const int kp = stage_prec(prec, kConvs[layer].stage);

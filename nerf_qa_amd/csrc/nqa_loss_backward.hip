@@ -13,6 +13,8 @@
 //   absmax_partial_kernel    per (image, block) the largest |g| as its bit pattern (which orders like the value)
 //   exponent_finish_kernel   per image: k with max|g| 2^k in [128, 256) (0 for a zero or non-finite maximum), and the
 //                            running total of the chain
+//   absmax_partial_half_kernel, exponent_finish_half_kernel   the same for the half gradient chain (grad_precision "f16"):
+//                            half maps read as such, and k with max|g| 2^k in [8, 16)
 //
 // The statistics' gradient is the NHWC counterpart of stats_coef_kernel + stats_grad_kernel and keeps their arithmetic
 // contract; the exponents replace the host's float(t.abs().max()) of autograd.pyramid_backward, so a loss step enqueues
@@ -206,8 +208,10 @@ __global__ __launch_bounds__(256) void loss_stats_grad_y_add_kernel(const float 
 // ---- the renormalisation exponents ----------------------------------------------------------------------------------
 // |float| as an unsigned integer orders like the value, every NaN above +inf: the maximum needs no float compare.
 // grid (nblk, n); g: n images of `units` 16-byte units each.
-__global__ __launch_bounds__(256) void absmax_partial_kernel(const u32x4 *__restrict__ g, long units,
-                                                             unsigned *__restrict__ part) {
+// G: the element type of g.  A half's |bits| order like its value too (every NaN above +inf); the partial is then the
+// 15-bit pattern of the largest |half|.
+template <typename G>
+__device__ __forceinline__ void absmax_partial_body(const u32x4 *__restrict__ g, long units, unsigned *__restrict__ part) {
   __shared__ unsigned red[4];
   const int img = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
   const u32x4 *p = g + (size_t)img * units;
@@ -215,7 +219,12 @@ __global__ __launch_bounds__(256) void absmax_partial_kernel(const u32x4 *__rest
 #pragma unroll 4
   for (long u = (long)blk * 256 + threadIdx.x; u < units; u += (long)nblk * 256) {
     const u32x4 v = p[u];
-    m = max(max(m, v[0] & 0x7fffffffu), max(v[1] & 0x7fffffffu, max(v[2] & 0x7fffffffu, v[3] & 0x7fffffffu)));
+    if constexpr (sizeof(G) == 4) {
+      m = max(max(m, v[0] & 0x7fffffffu), max(v[1] & 0x7fffffffu, max(v[2] & 0x7fffffffu, v[3] & 0x7fffffffu)));
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) m = max(m, max(v[e] & 0x7fffu, (v[e] >> 16) & 0x7fffu));
+    }
   }
   for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -223,23 +232,55 @@ __global__ __launch_bounds__(256) void absmax_partial_kernel(const u32x4 *__rest
   if (threadIdx.x == 0) part[(size_t)img * nblk + blk] = max(max(red[0], red[1]), max(red[2], red[3]));
 }
 
+__global__ __launch_bounds__(256) void absmax_partial_kernel(const u32x4 *__restrict__ g, long units,
+                                                             unsigned *__restrict__ part) {
+  absmax_partial_body<float>(g, units, part);
+}
+// 16-byte units of eight halves
+__global__ __launch_bounds__(256) void absmax_partial_half_kernel(const u32x4 *__restrict__ g, long units,
+                                                                  unsigned *__restrict__ part) {
+  absmax_partial_body<_Float16>(g, units, part);
+}
+
 // grid n, one wave per image.  kexp[img] = k; ktot[img] += k when ktot is given (one writer per image).
-__global__ __launch_bounds__(64) void exponent_finish_kernel(const unsigned *__restrict__ part, int nblk,
-                                                             int *__restrict__ kexp, int *__restrict__ ktot) {
+// G: whose bit patterns the partials are; TOP: max|g| 2^k lies in [2^(TOP-1), 2^TOP) -- 8 for the split16 chain's
+// [128, 256), 4 for the half chain's [8, 16).
+template <typename G, int TOP>
+__device__ __forceinline__ void exponent_finish_body(const unsigned *__restrict__ part, int nblk, int *__restrict__ kexp,
+                                                     int *__restrict__ ktot) {
   const int img = blockIdx.x;
   unsigned m = 0;
   for (int i = threadIdx.x; i < nblk; i += 64) m = max(m, part[(size_t)img * nblk + i]);
   for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
   if (threadIdx.x) return;
   int k = 0;
-  if (m != 0 && m < 0x7f800000u) {
-    // max = f 2^e with f in [0.5, 1) (frexp), from the bits: a normal float's biased exponent - 126; a subnormal one is
-    // m 2^-149 with its highest set bit at 31 - clz(m)
-    const int e = (m >> 23) ? (int)(m >> 23) - 126 : (31 - __clz((int)m)) - 148;
-    k = 8 - e;
+  if constexpr (sizeof(G) == 4) {
+    if (m != 0 && m < 0x7f800000u) {
+      // max = f 2^e with f in [0.5, 1) (frexp), from the bits: a normal float's biased exponent - 126; a subnormal one is
+      // m 2^-149 with its highest set bit at 31 - clz(m)
+      const int e = (m >> 23) ? (int)(m >> 23) - 126 : (31 - __clz((int)m)) - 148;
+      k = TOP - e;
+    }
+  } else {
+    if (m != 0 && m < 0x7c00u) {
+      // the same from a half's bits: a normal half's biased exponent - 14; a subnormal one is m 2^-24
+      const int e = (m >> 10) ? (int)(m >> 10) - 14 : (31 - __clz((int)m)) - 23;
+      k = TOP - e;
+    }
   }
   kexp[img] = k;
   if (ktot) ktot[img] += k;
+}
+
+__global__ __launch_bounds__(64) void exponent_finish_kernel(const unsigned *__restrict__ part, int nblk,
+                                                             int *__restrict__ kexp, int *__restrict__ ktot) {
+  exponent_finish_body<float, 8>(part, nblk, kexp, ktot);
+}
+// the half chain's window [8, 16), from a float or a half map's partials
+template <typename G>
+__global__ __launch_bounds__(64) void exponent_finish_half_kernel(const unsigned *__restrict__ part, int nblk,
+                                                                  int *__restrict__ kexp, int *__restrict__ ktot) {
+  exponent_finish_body<G, 4>(part, nblk, kexp, ktot);
 }
 
 // ---------------------------------------------------------------------------------
@@ -346,6 +387,23 @@ int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp
   TimedLaunch t(NQA_K_POOL, st);
   exponent_finish_kernel<<<n, 64, 0, st>>>(ws, nblk, kexp, ktot);
   return check_launch("exponent_finish");
+}
+
+// the half chain's exponents: max|g| 2^k in [8, 16); g float (per_image % 4 == 0) or half (per_image % 8 == 0)
+int grad_exponent_half(const void *g, int g_half, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st) {
+  const int nblk = grad_exponent_nblk(per_image);
+  const u32x4 *units = static_cast<const u32x4 *>(g);
+  int rc;
+  {
+    TimedLaunch t(NQA_K_POOL, st);
+    if (g_half) absmax_partial_half_kernel<<<dim3(nblk, n), 256, 0, st>>>(units, per_image / 8, ws);
+    else absmax_partial_kernel<<<dim3(nblk, n), 256, 0, st>>>(units, per_image / 4, ws);
+    if ((rc = check_launch("absmax_partial"))) return rc;
+  }
+  TimedLaunch t(NQA_K_POOL, st);
+  if (g_half) exponent_finish_half_kernel<_Float16><<<n, 64, 0, st>>>(ws, nblk, kexp, ktot);
+  else exponent_finish_half_kernel<float><<<n, 64, 0, st>>>(ws, nblk, kexp, ktot);
+  return check_launch("exponent_finish_half");
 }
 
 }  // namespace nqa

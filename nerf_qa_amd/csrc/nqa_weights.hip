@@ -79,6 +79,7 @@ size_t layer0_mfma_offset(int prec) { return blob_layout(prec).w1_mfma; }
 size_t regw_offset(int layer, int prec) { return blob_layout(prec).regw[layer]; }
 size_t layer0_m16_offset(int prec) { return blob_layout(prec).w1_m16; }
 size_t conv_split_bias_off(int cout, int cin) { return rows_bytes(cout, cin, 4); }
+size_t conv_half_bias_off(int cout, int cin) { return rows_bytes(cout, cin, 2); }
 
 // ---- elements ------------------------------------------------------------------------------------------------------------
 static uint16_t f32_to_bf16(float f) {
@@ -302,6 +303,24 @@ int nqa_pack_conv_split(const float *w_oihw, int cout, int cin, void *packed_hos
   const float inv = ldexpf(1.f, -k);
   pack_rows(w_oihw, cout, cin, kRowsSplit, false, 0, ldexpf(1.f, k), blob);
   memcpy(blob + conv_split_bias_off(cout, cin) + (size_t)cout * 4, &inv, 4);
+  return NQA_OK;
+}
+
+// one 3x3 layer in the f16 row format, zero bias (nqa_conv3x3_half)
+size_t nqa_packed_conv_half_bytes(int cout, int cin) {
+  if (cout <= 0 || cin <= 0 || cout % 64 || cin % 32) return 0;
+  return conv_half_bias_off(cout, cin) + bias_bytes(cout);
+}
+
+int nqa_pack_conv_half(const float *w_oihw, int cout, int cin, void *packed_host) {
+  if (!w_oihw || !packed_host || cout <= 0 || cin <= 0 || cout % 64 || cin % 32) {
+    set_error("pack_conv_half: bad argument (cout %d must be a multiple of 64, cin %d of 32)", cout, cin);
+    return NQA_E_ARG;
+  }
+  char *blob = static_cast<char *>(packed_host);
+  memset(blob, 0, nqa_packed_conv_half_bytes(cout, cin));  // (bias = 0; the float behind it, a scale elsewhere, is not read)
+  // the swizzle of the MFMA that nqa_conv3x3_half runs the layer on: 16x16x32 on 128-channel tiles, else 32x32x16
+  pack_rows(w_oihw, cout, cin, kRows16, cout % 128 == 0, NQA_PREC_F16, 1.f, blob);
   return NQA_OK;
 }
 

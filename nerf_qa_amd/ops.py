@@ -1154,6 +1154,99 @@ def conv1_1_backward_scaled(g: torch.Tensor, relu1_1_split16: torch.Tensor | Non
     return out
 
 
+# ---- the half gradient chain: grad_precision="f16" (include/nqa.h, "The same chain on HALF gradient maps") ----------
+def pack_conv_half(w) -> torch.Tensor:
+    """One 3x3 layer (float32 OIHW, cout % 64 == 0, cin % 32 == 0) as f16 rows, zero bias -> CPU uint8 blob."""
+    w = np.ascontiguousarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32)
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    assert w.shape[2:] == (3, 3)
+    nbytes = lib().nqa_packed_conv_half_bytes(cout, cin)
+    if not nbytes:
+        raise ValueError(f"pack_conv_half: unsupported layer shape {w.shape}")
+    blob = torch.empty(nbytes, dtype=torch.uint8)
+    check(lib().nqa_pack_conv_half(w.ctypes.data, cout, cin, blob.data_ptr()))
+    return blob
+
+
+def _is_grad_map(g: torch.Tensor) -> bool:
+    """Whether g is a half map (else it must be float); contiguous either way."""
+    assert g.dtype in (torch.float16, torch.float32) and g.is_contiguous()
+    return g.dtype == torch.float16
+
+
+def conv3x3_half(inp: torch.Tensor, blob: torch.Tensor, cout: int) -> torch.Tensor:
+    """f16 NHWC (n,H,W,cin) -> f16 NHWC (n,H,W,cout) through a layer packed by pack_conv_half: no bias, no ReLU."""
+    dev = _need_cuda(inp, blob)
+    assert inp.dtype == torch.float16 and inp.is_contiguous()
+    n, h, w, cin = inp.shape
+    out = torch.empty((n, h, w, cout), dtype=torch.float16, device=dev)
+    _call(dev, lib().nqa_conv3x3_half, ptr(inp), n, h, w, cin, cout, ptr(blob), ptr(out), stream_ptr(dev))
+    return out
+
+
+def grad_exponent_half(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
+    """grad_exponent for the half chain: k[i] with max|g[i]| * 2^k[i] in [8, 16); g float or half, image i = g[i]."""
+    dev = _need_cuda(g, k)
+    n, half = g.shape[0], _is_grad_map(g)
+    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
+    assert k_total is None or (k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
+                               and k_total.device == dev)
+    per = g.numel() // n
+    nbytes = lib().nqa_grad_exponent_bytes(n, per)
+    if not nbytes:
+        raise _lib.NqaError(f"grad_exponent_half: unsupported shape {tuple(g.shape)}")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, lib().nqa_grad_exponent_half, ptr(g), int(half), n, per, ptr(buf), buf.numel(), ptr(k),
+          None if k_total is None else ptr(k_total), stream_ptr(dev))
+
+
+def relu_mask_f16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16: bool, k: torch.Tensor) -> torch.Tensor:
+    """(g * 2^k[image]) * (act > 0) rounded to half once, as a plain f16 NHWC map of g's shape; g float or half, act a
+    float map or split16 records; the exponents (int32, one per image g[i]) are read on the device."""
+    dev = _need_cuda(g, act, k)
+    half = _is_grad_map(g)
+    assert act.dtype == torch.float32 and act.is_contiguous() and act.shape == g.shape
+    n, c = g.shape[0], g.shape[-1]
+    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
+    out = torch.empty(g.shape, dtype=torch.float16, device=dev)
+    _call(dev, lib().nqa_relu_mask_f16_scaled, ptr(g), int(half), ptr(act), int(act_is_split16), n, g.numel() // (n * c), c,
+          ptr(k), ptr(out), stream_ptr(dev))
+    return out
+
+
+def l2pool_backward_scaled_half(tap: torch.Tensor, g_pooled: torch.Tensor, g_tap: torch.Tensor,
+                                k_total: torch.Tensor) -> torch.Tensor:
+    """l2pool_backward_scaled with a half g_pooled: a new float (n,H,W,C) tensor."""
+    dev = _need_cuda(tap, g_pooled, g_tap, k_total)
+    n, h, w, c = tap.shape
+    assert tap.dtype == torch.float32 and tap.is_contiguous()
+    assert g_tap.shape == tap.shape and g_tap.dtype == torch.float32 and g_tap.is_contiguous()
+    assert g_pooled.shape == (n, (h + 1) // 2, (w + 1) // 2, c) and g_pooled.dtype == torch.float16 and g_pooled.is_contiguous()
+    assert k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
+    out = torch.empty_like(tap)
+    _call(dev, lib().nqa_l2pool_backward_scaled_half, ptr(tap), ptr(g_pooled), ptr(g_tap), ptr(k_total), n, h, w, c, ptr(out),
+          stream_ptr(dev))
+    return out
+
+
+def conv1_1_backward_scaled_half(g: torch.Tensor, relu1_1_split16: torch.Tensor | None, w0: torch.Tensor, k: torch.Tensor,
+                                 k_total: torch.Tensor) -> torch.Tensor:
+    """conv1_1_backward_scaled with a half g (n,H,W,64) -> float NCHW (n,3,H,W)."""
+    dev = _need_cuda(g, w0, k, k_total)
+    w0 = _f32c(w0)
+    assert g.dtype == torch.float16 and g.is_contiguous()
+    n, h, w, c = g.shape
+    assert c == 64 and tuple(w0.shape) == (64, 3, 3, 3)
+    assert relu1_1_split16 is None or (relu1_1_split16.shape == g.shape and relu1_1_split16.dtype == torch.float32
+                                       and relu1_1_split16.is_contiguous() and relu1_1_split16.device == dev)
+    for t in (k, k_total):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_conv1_1_backward_scaled_half, ptr(g), None if relu1_1_split16 is None else ptr(relu1_1_split16),
+          ptr(w0), ptr(k), ptr(k_total), n, h, w, ptr(out), stream_ptr(dev))
+    return out
+
+
 # ---- windowed moments of the A-DISTS head (include/nqa.h, nqa_window_moments.hip) ---------------------------------
 WINDOW = 21  # the library's window: the normalised 21-tap Gaussian of sigma 7, as head.gauss_1d(21, .)
 

@@ -125,10 +125,15 @@ def forward_target(dists_model, adists_model, target, y, batch_average=False, as
     the host.  Without a gradient to form, y gives its taps once and both heads run on them; nothing is kept.
 
     `target` comes from the prepare_target of EITHER module (with equal VGG weights both prepare the same taps).
-    ValueError for a target of a third module, one prepared before its owner's VGG weights changed, and a shape that
-    does not fit; NqaError for modules with different VGG weights, tensors off the GPU, and a batch whose A-DISTS
+    The gradient chain runs in the two modules' grad_precision, which must be the same ("f32s" | "f16").
+    ValueError for modules that name different ones, a target of a third module, one prepared before its owner's VGG
+    weights changed, and a shape that does not fit; NqaError for modules with different VGG weights, tensors off the GPU, and a batch whose A-DISTS
     scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices)."""
     from . import autograd, target as tgt
+    gp = [getattr(m, "grad_precision", "f32s") for m in (dists_model, adists_model)]
+    if gp[0] != gp[1]:  # (one chain carries both metrics' gradients: the same kind of rule as pair_precision)
+        raise ValueError(f"forward_target runs ONE gradient chain for both metrics, but the DISTS module asks for "
+                         f"grad_precision={gp[0]!r} and the A-DISTS module for {gp[1]!r}: give both the same")
     tgt.check_pair(dists_model, adists_model, target, y)
     _check_same_weights(dists_model, adists_model, y.device, "forward_target")
     autograd.adists_target_fits(target)

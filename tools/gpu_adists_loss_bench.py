@@ -22,7 +22,9 @@ to OUT when given (profiles/adists_loss_step_bench.txt holds such reports).  --l
 gradient on y, default against hip (a minute instead of the whole report; also what a baseline tree is measured with).
 --target: only the hip loss step with the gradient on y against the step on a prepared target (ADISTS.prepare_target
 once, then forward_target(target, y) per step: one kept pyramid of y, nothing of x's), same pairs, one process, with the
-time of prepare_target itself; that report is APPENDED to OUT."""
+time of prepare_target itself; that report is APPENDED to OUT.  With --target, --grad-precision f16 builds the module with
+grad_precision="f16" (the half gradient chain, to be set beside a run without it) and --shape HxWxB runs that one shape,
+so that every shape can have a process of its own."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import functools
 import re
@@ -81,10 +83,10 @@ def stream_gbs():
     return best
 
 
-def target_report(model, dev, say):
+def target_report(model, dev, say, shapes=SHAPES):
     """The one-sided hip step (x fixed, gradient on y) against the step on a prepared target, same pairs, one process."""
     model.loss_head = "auto"
-    for h, w, b in SHAPES:
+    for h, w, b in shapes:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
         target = model.prepare_target(x0)
@@ -120,13 +122,17 @@ def target_report(model, dev, say):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    quick = "--loss-y-only" in sys.argv[1:]
-    with_target = "--target" in sys.argv[1:]
+    flags = sys.argv[1:]
+    valued = {flags[i + 1] for i, a in enumerate(flags[:-1]) if a in ("--grad-precision", "--shape")}
+    args = [a for a in flags if not a.startswith("--") and a not in valued]
+    quick = "--loss-y-only" in flags
+    with_target = "--target" in flags
+    grad_precision = flags[flags.index("--grad-precision") + 1] if "--grad-precision" in flags else None
+    shapes = (tuple(int(v) for v in flags[flags.index("--shape") + 1].split("x")),) if "--shape" in flags else SHAPES
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        model = ADISTS().to(dev).eval()
+        model = ADISTS(**({"grad_precision": grad_precision} if grad_precision else {})).to(dev).eval()
     stream = stream_gbs()
     lines = [f"# tools/gpu_adists_loss_bench.py  ({torch.cuda.get_device_name(dev)}; torch {torch.__version__}; commit {commit()}; "
              f"HIP sources {build.source_hash()})",
@@ -143,9 +149,9 @@ def main():
     slices = functools.partial(plain, window_impl="slices")
     if with_target:
         lines[1] = ("# --target: ADISTS(x, y) (as_loss=True, loss_head auto) with x fixed against forward_target on a prepared "
-                    f"target, stand-in weights; device events, median [min, max] of {REPS} windows of {ITERS} steps after "
-                    f"{WARMUP} warm-up steps")
-        target_report(model, dev, say)
+                    f"target, gradient chain {model.grad_precision}, stand-in weights; device events, median [min, max] of "
+                    f"{REPS} windows of {ITERS} steps after {WARMUP} warm-up steps")
+        target_report(model, dev, say, shapes)
     for h, w, b in () if with_target else SHAPES:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)

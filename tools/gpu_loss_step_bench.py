@@ -15,8 +15,12 @@ a render y against a ground-truth frame x) against the step on a prepared target
 forward_target(target, y, require_grad=True, batch_average=True) per step: one kept pyramid of y, nothing of x), on the same
 pairs in the same process, with the time of prepare_target itself.
 
-Usage: python tools/gpu_loss_step_bench.py [OUT] [--target]  -- prints the report, and also writes it to OUT when given
-(profiles/loss_step_bench.txt holds such reports; a --target report is APPENDED to OUT)."""
+--grad-precision f16 (with --target) builds the module with grad_precision="f16": the same steps with the half gradient
+chain, to be set beside a run without it; --shape HxWxB (with --target) runs that one shape, so that every shape can have a
+process of its own.
+
+Usage: python tools/gpu_loss_step_bench.py [OUT] [--target [--grad-precision f16] [--shape HxWxB]]  -- prints the report,
+and also writes it to OUT when given (profiles/loss_step_bench.txt holds such reports; a --target report is APPENDED to OUT)."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import subprocess
 import sys
@@ -81,9 +85,9 @@ def commit():
         return "unknown"
 
 
-def target_report(model, dev, say):
+def target_report(model, dev, say, shapes=SHAPES):
     """The one-sided step (x fixed, gradient on y) against the step on a prepared target, same pairs, one process."""
-    for h, w, b in SHAPES:
+    for h, w, b in shapes:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
         target = model.prepare_target(x0)
@@ -119,12 +123,16 @@ def target_report(model, dev, say):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    with_target = "--target" in sys.argv[1:]
+    flags = sys.argv[1:]
+    valued = {flags[i + 1] for i, a in enumerate(flags[:-1]) if a in ("--grad-precision", "--shape")}
+    args = [a for a in flags if not a.startswith("--") and a not in valued]
+    with_target = "--target" in flags
+    grad_precision = flags[flags.index("--grad-precision") + 1] if "--grad-precision" in flags else None
+    shapes = (tuple(int(v) for v in flags[flags.index("--shape") + 1].split("x")),) if "--shape" in flags else SHAPES
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        model = DISTS(precision="f32s").to(dev).eval()
+        model = DISTS(precision="f32s", **({"grad_precision": grad_precision} if grad_precision else {})).to(dev).eval()
     lines = [f"# tools/gpu_loss_step_bench.py  ({torch.cuda.get_device_name(dev)}; torch {torch.__version__}; commit {commit()}; "
              f"HIP sources {build.source_hash()})",
              f"# forward + backward of DISTS(x, y, require_grad=True, batch_average=True), precision f32s, stand-in weights;",
@@ -137,8 +145,8 @@ def main():
 
     if with_target:
         lines[1] = ("# --target: DISTS(x, y, require_grad=True, batch_average=True) with x fixed against forward_target on a "
-                    "prepared target, precision f32s, stand-in weights;")
-        target_report(model, dev, say)
+                    f"prepared target, precision f32s, gradient chain {model.grad_precision}, stand-in weights;")
+        target_report(model, dev, say, shapes)
     for h, w, b in () if with_target else SHAPES:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
         x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)

@@ -17,8 +17,11 @@ their own and added by torch.
 --baseline-only runs (a) alone: it needs nothing this tool's commit added, so the same file times a checkout of the
 parent commit (the parent check of DESIGN.md 4.16: alternate the two in fresh processes and compare the ranges).
 
-Usage: python tools/gpu_pair_loss_bench.py [OUT] [--shape HxWxB] [--baseline-only]  -- prints the report and appends it
-to OUT when given (profiles/pair_loss_step_bench.txt holds such reports)."""
+--grad-precision f16 builds both modules with grad_precision="f16": the same report with the half gradient chain, to be
+set beside a run without it.
+
+Usage: python tools/gpu_pair_loss_bench.py [OUT] [--shape HxWxB] [--baseline-only] [--grad-precision f16]  -- prints the
+report and appends it to OUT when given (profiles/pair_loss_step_bench.txt holds such reports)."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import subprocess
 import sys
@@ -86,7 +89,7 @@ def class_line(kt):
             f"{kt['adists'][1]:8.3f} ms   other timed classes {rest:7.3f} ms")
 
 
-def one_shape(shape, baseline_only, say):
+def one_shape(shape, baseline_only, say, grad_precision=None):
     import torch
     sys.path.insert(0, ROOT)
     from nerf_qa_amd import autograd, build, ops, synth
@@ -96,11 +99,13 @@ def one_shape(shape, baseline_only, say):
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        dm = DISTS(precision="f32s").to(dev).eval()
-        am = ADISTS(loss_head="auto").to(dev).eval()
+        gp = {"grad_precision": grad_precision} if grad_precision else {}
+        dm = DISTS(precision="f32s", **gp).to(dev).eval()
+        am = ADISTS(loss_head="auto", **gp).to(dev).eval()
     say(f"# tools/gpu_pair_loss_bench.py  ({torch.cuda.get_device_name(dev)}; torch {torch.__version__}; commit {commit()}; "
         f"HIP sources {build.source_hash()})")
-    say(f"# L = {WD} * DISTS + {WA} * A-DISTS against a prepared target, f32s, stand-in weights; device events, median "
+    say(f"# L = {WD} * DISTS + {WA} * A-DISTS against a prepared target, f32s, gradient chain "
+        f"{getattr(dm, 'grad_precision', 'f32s')}, stand-in weights; device events, median "
         f"[min, max] of {REPS} windows of {ITERS} steps after {WARMUP} warm-up steps")
     xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
     x0, y0 = torch.from_numpy(xn).to(dev), torch.from_numpy(yn).to(dev)
@@ -184,13 +189,15 @@ def one_shape(shape, baseline_only, say):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
     flags = sys.argv[1:]
+    grad_precision = flags[flags.index("--grad-precision") + 1] if "--grad-precision" in flags else None
+    args = [a for a in flags if not a.startswith("--") and a != grad_precision]
     baseline_only = "--baseline-only" in flags
     shape = flags[flags.index("--shape") + 1] if "--shape" in flags else None
     if shape is None:  # one fresh process per shape
         for s in SHAPES:
-            cmd = [sys.executable, os.path.abspath(__file__), *args[:1], "--shape", s] + (["--baseline-only"] if baseline_only else [])
+            cmd = [sys.executable, os.path.abspath(__file__), *args[:1], "--shape", s] + (["--baseline-only"] if baseline_only else []) \
+                + (["--grad-precision", grad_precision] if grad_precision else [])
             if subprocess.run(cmd).returncode:
                 sys.exit(1)
         return
@@ -201,7 +208,7 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    one_shape(shape, baseline_only, say)
+    one_shape(shape, baseline_only, say, grad_precision)
     if args:
         out = args[0]
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
