@@ -40,7 +40,8 @@ Stage 1 on integers.  The normalisation does not stand in the way: a raw pixel f
 division alike (tests/test_persistent_refs.py replays both), i.e. to exactly v in half and bfloat16.  With the sparse
 integer conv1_1 and conv1_2 of persistent_refs.s1_convs (relu1_2 in [0, 63]):
   conv1_regw_kernel<P> (f16, bf16), <PrecF16, 2> (f16w) through ops.conv1_fused, batches of batch_for("conv1_regw"):
-    BIT-EQUAL to relu1_2 in float64 rounded once (f32s stays on the random frames: its normalised pixel is a float32);
+    BIT-EQUAL to relu1_2 in float64 rounded once (f32s stays on the random frames here: its normalised pixel is a float32,
+    and its exact frames, with lo halves, are those of tests/test_gpu_stage1_split_exact.py);
   conv1_pool_kernel<RAGGED> + pool_seam_kernel + part_reduce_kernel (nqa_conv1_pool.hip) through ops.conv1_pool_stats,
     x and y from two base triples, 150 x 130 (H % 4 = 2, W % 32 = 2: the last unit's second half-strip wholly outside),
     37 x 70 (H odd: the last pooled row from one tap row), 64 x 96 (full units: the other instance) and 36 x 70 (the

@@ -30,7 +30,8 @@ before the launch, with ops.mixed_grid_launches() telling the grid:
                                            <1,4,2,2, 32 | 16, LOACC> for (64,64), (128,64), through ops.pack_conv_split /
                                            ops.conv3x3_split on SIGNED activations: relu=False against the reference, and
                                            relu=True bit-equal to its clamp
-Stage 1 fused (conv1_regw_split_kernel) is not here: its normalisation has no exact operand set."""
+Stage 1 fused (conv1_regw_split_kernel) has a file of its own, tests/test_gpu_stage1_split_exact.py: raw pixels that its
+normalisation maps exactly onto (hi, lo) levels exist (tests/stage1_split_refs.py searches them)."""
 import pytest
 import torch
 
