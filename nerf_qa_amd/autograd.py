@@ -24,10 +24,15 @@ losses run one kept pyramid of y per step and nothing of x: DistsTargetSimilarit
 from its forward and starts the backward from them, AdistsTargetLoss runs adists_backward_y's two halves in its forward
 and its backward.  PairTargetLoss is the two together for a loss that sums both metrics (nerf_qa_amd/pair.py,
 forward_target): one kept pyramid serves both heads, and the sum of their tap gradients goes down one chain.
+
+One walk each way: _pyramid_forward (pyramid_keep keeps all of it, pyramid_taps the five taps) and pyramid_backward_device,
+whose rung of grad_precision is a record of _RUNGS (packer, exponent, mask, data-gradient convolution).  _target_backward
+is the tail of every one-sided loss: the tap gradients of the metrics in use, one chain, the image terms.
 """
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import torch
 
@@ -75,42 +80,74 @@ def _stats_grad(fx, fy, g1, g2, dims):
     return gx, gy
 
 
+# What a forward leaves for its backward, as named records.  KeptPyramid: acts {layer 0..12: NHWC}, taps [5 float NHWC
+# maps], pooled [4 split16 maps]; acts and pooled None where only the taps were kept.  AdistsState: the front's q (8, B,
+# 1475) and wgt (B, 1475), per stage the maps [gamma, tw, sw, ps_prod], y's KeptPyramid.  TargetStats: the five taps'
+# per-block fp64 partials, tap 0's maps and sums.  The pair's one pyramid is its AdistsState's.
+KeptPyramid = namedtuple("KeptPyramid", "acts taps pooled")
+AdistsState = namedtuple("AdistsState", "q wgt maps pyramid")
+TargetStats = namedtuple("TargetStats", "parts fx0 fy0 scratch")
+DistsTargetState = namedtuple("DistsTargetState", "pyramid stats")
+PairTargetState = namedtuple("PairTargetState", "stats adists")
+# The layer facts of the walks, each derived once.  Layer l reads the L2-pool of the previous stage's tap where the stage
+# changes; its own activation is split16 unless it is tapped (a tapped layer's output is a float map).
+_READS_POOL = frozenset(l for l in range(1, 13) if ops.CONV_STAGE[l] != ops.CONV_STAGE[l - 1])
+_SPLIT16_ACT = frozenset(range(1, 13)) - frozenset(ops.TAP_LAYERS)
+# One precision of the device gradient chain: the key of its blob set, how its data-gradient weights are packed, and the
+# three kernels of a layer's step -- exponent(g, k, K), mask(g, act, act_is_split16, k), conv(gm, blob, cout).  (The pool
+# seam and conv1_1's step choose by their operand's dtype in ops and need no entry.)
+_Rung = namedtuple("_Rung", "name pack exponent mask conv")
+# "f32s": split16 operands, float out, max|g| 2^k in [128, 256).  "f16": a plain half map between layers (rounded once by
+# the mask; half weights, float32 accumulator, half out) and the window [8, 16): a convolution's output is a half there,
+# and 16 times the largest L1 norm of a data-gradient filter has to stay below 65504.  g is float at the top and behind
+# a pool seam (whose taps, tap gradients and output stay float) on both rungs.
+_RUNGS = {r.name: r for r in (
+    _Rung("f32s", ops.pack_conv_split, ops.grad_exponent, ops.relu_mask_split16_scaled, ops.conv3x3_split),
+    _Rung("f16", ops.pack_conv_half, ops.grad_exponent_half, ops.relu_mask_f16_scaled, ops.conv3x3_half))}
+
+
 def _backward_blobs(module, dev, grad_precision="f32s"):
     """Per conv layer 1..12 the data-gradient layer: W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], packed once per weights
-    in the format of `grad_precision` ("f32s": split rows, ops.pack_conv_split; "f16": half rows, ops.pack_conv_half).
-    Only the set that is asked for is packed and kept: the other one (60 / 30 MB) is never built unasked."""
+    by the packer of the rung `grad_precision` (_RUNGS).  Only the set that is asked for is packed and kept: the other
+    one (60 / 30 MB) is never built unasked."""
     key = module._weights_key(dev)
     cache = getattr(module, "_bwd_blobs", None)
     if cache is None or cache[0] != key:
         cache = (key, {}, module._conv_modules()[0].weight.detach().float().contiguous().to(dev))
         module.__dict__["_bwd_blobs"] = cache
-    if grad_precision not in cache[1]:
+    rung = _RUNGS[grad_precision]
+    if rung.name not in cache[1]:
         convs = module._conv_modules()
-        pack = ops.pack_conv_half if grad_precision == "f16" else ops.pack_conv_split
-        cache[1][grad_precision] = {l: pack(convs[l].weight.detach().flip(2, 3).transpose(0, 1).contiguous()).to(dev)
-                                    for l in range(1, 13)}
-    return cache[1][grad_precision], cache[2]
+        cache[1][rung.name] = {l: rung.pack(convs[l].weight.detach().flip(2, 3).transpose(0, 1).contiguous()).to(dev)
+                               for l in range(1, 13)}
+    return cache[1][rung.name], cache[2]
 
 
 @torch.no_grad()
-def pyramid_keep(module, imgs):
-    """The pyramid of `imgs` (n,3,H,W float) again, layer by layer in f32s, keeping every activation:
-    (acts {layer: NHWC}, taps [5 float NHWC maps], pooled [4 split16 maps])."""
+def _pyramid_forward(module, imgs, keep):
+    """The one forward walk: conv1_1, layers 1..12 and the four L2-pools of `imgs` (n,3,H,W float) in f32s, as a
+    KeptPyramid of everything (keep) or of the five taps alone -- the same launches in the same order either way."""
     prec = "f32s"
     packed = module._packed_weights(imgs.device, prec)
-    acts = {0: ops.conv1_1(imgs, packed, prec)}  # split16 (n,H,W,64)
-    taps, pooled = [], []
-    inp = acts[0]
+    inp = ops.conv1_1(imgs, packed, prec)  # split16 (n,H,W,64)
+    acts, taps, pooled = ({0: inp}, [], []) if keep else (None, [], None)
     for l in range(1, 13):
-        out = ops.conv3x3_relu(inp, l, packed, prec)  # float for the tapped layers, split16 otherwise
-        acts[l] = out
-        inp = out
+        inp = ops.conv3x3_relu(inp, l, packed, prec)  # float for the tapped layers, split16 otherwise
+        if keep:
+            acts[l] = inp
         if l in ops.TAP_LAYERS:
-            taps.append(out)
-            if l != 12:
-                pooled.append(ops.l2pool(out, prec))  # split16
-                inp = pooled[-1]
-    return acts, taps, pooled
+            taps.append(inp)
+        if l + 1 in _READS_POOL:
+            inp = ops.l2pool(inp, prec)  # split16
+            if keep:
+                pooled.append(inp)
+    return KeptPyramid(acts, taps, pooled)
+
+
+def pyramid_keep(module, imgs):
+    """The pyramid of `imgs` (n,3,H,W float) again, layer by layer in f32s, keeping every activation:
+    KeptPyramid(acts {layer: NHWC}, taps [5 float NHWC maps], pooled [4 split16 maps])."""
+    return _pyramid_forward(module, imgs, keep=True)
 
 
 @torch.no_grad()
@@ -139,9 +176,9 @@ def pyramid_backward(module, acts, taps, pooled, g_taps):
 
     g, K = normalise(g_taps[4], 0)
     for l in range(12, 0, -1):
-        gm = ops.relu_mask_split16(g, acts[l], l not in ops.TAP_LAYERS)
+        gm = ops.relu_mask_split16(g, acts[l], l in _SPLIT16_ACT)
         g = ops.conv3x3_split(gm, blobs[l], ops.CONV_CIN[l], relu=False)  # gradient w.r.t. the layer's input
-        if l in (2, 4, 7, 10):  # the input was the L2-pool of the previous stage's tap
+        if l in _READS_POOL:  # the input was the L2-pool of the previous stage's tap
             s = ops.CONV_STAGE[l]
             gt = g_taps[s - 1] * (2.0 ** K)  # the tap's own gradient, in the running scale
             ops.l2pool_backward(taps[s - 1], pooled[s - 1], g, gt)  # gt += pool gradient
@@ -151,29 +188,18 @@ def pyramid_backward(module, acts, taps, pooled, g_taps):
     return ops.conv1_1_backward(gm, w0) * (2.0 ** -K)  # (n,3,H,W), the input normalisation included
 
 
-@torch.no_grad()
 def pyramid_taps(module, imgs):
     """The five float NHWC taps of `imgs` by pyramid_keep's own launches, keeping nothing else: what the statistics need of
-    an image that takes no gradient.  (The same kernels as pyramid_keep on purpose: the fused forward of ops.vgg_pyramid
+    an image that takes no gradient.  (The same walk as pyramid_keep on purpose: the fused forward of ops.vgg_pyramid
     runs stage 1 in another kernel and agrees with these to a summation order only, and the gradient of a pair must
     not depend on whether its partner asked for one.)"""
-    prec = "f32s"
-    packed = module._packed_weights(imgs.device, prec)
-    inp = ops.conv1_1(imgs, packed, prec)
-    taps = []
-    for l in range(1, 13):
-        inp = ops.conv3x3_relu(inp, l, packed, prec)
-        if l in ops.TAP_LAYERS:
-            taps.append(inp)
-            if l != 12:
-                inp = ops.l2pool(inp, prec)
-    return taps
+    return _pyramid_forward(module, imgs, keep=False).taps
 
 
 def _grad_precision(module, grad_precision=None):
     """The gradient chain's precision: the argument, else the module's setting ("f32s" for a module that has none)."""
     v = grad_precision or getattr(module, "grad_precision", "f32s")
-    if v not in ("f32s", "f16"):
+    if v not in _RUNGS:
         raise ValueError(f"grad_precision must be 'f32s' or 'f16', got {v!r}")
     return v
 
@@ -183,55 +209,28 @@ def pyramid_backward_device(module, acts, taps, pooled, g_taps, masked=False, gr
     """pyramid_backward with the renormalisation on the device: the exponents are taken per IMAGE by a reduction kernel
     and read by the scaled forms of the chain's kernels (csrc/nqa_loss_backward.hip, nqa_backward.hip), so nothing comes
     back to the host between the first and the last launch -- the step can be enqueued ahead, and the gradient of an
-    image does not depend on what else is in the batch.  With one image the exponents are the host path's and the result
-    is pyramid_backward's bit for bit.  masked=True: g_taps already carry their taps' ReLU masks (g * (t > 0)).
+    image does not depend on what else is in the batch.  With one image the f32s exponents are the host path's and the
+    result is pyramid_backward's bit for bit.  masked=True: g_taps already carry their taps' ReLU masks (g * (t > 0)).
 
-    grad_precision (None: the module's own, DISTS(grad_precision=) / ADISTS(grad_precision=)): "f32s" is the chain
-    above; "f16" is _pyramid_backward_half, the same walk on plain half gradient maps."""
-    if _grad_precision(module, grad_precision) == "f16":
-        return _pyramid_backward_half(module, acts, taps, g_taps, masked)
-    blobs, w0 = _backward_blobs(module, taps[0].device)
+    grad_precision (None: the module's own, DISTS(grad_precision=) / ADISTS(grad_precision=)) names the rung of _RUNGS
+    whose packer, exponent, mask and convolution the walk runs.  `pooled` is not read (the seam pools the tap itself)."""
+    rung = _RUNGS[_grad_precision(module, grad_precision)]
+    blobs, w0 = _backward_blobs(module, taps[0].device, rung.name)
     if not masked:  # BEFORE the first exponent is taken (see pyramid_backward)
         g_taps = [g * (t > 0) for g, t in zip(g_taps, taps)]
     n, dev = taps[0].shape[0], taps[0].device
     k = torch.empty(n, dtype=torch.int32, device=dev)   # the exponent of the step, per image
     K = torch.zeros(n, dtype=torch.int32, device=dev)   # the running total
-    g = g_taps[4].contiguous()
-    ops.grad_exponent(g, k, K)
+    g = ops._f32c(g_taps[4])
+    rung.exponent(g, k, K)
     for l in range(12, 0, -1):
-        gm = ops.relu_mask_split16_scaled(g, acts[l], l not in ops.TAP_LAYERS, k)
-        g = ops.conv3x3_split(gm, blobs[l], ops.CONV_CIN[l], relu=False)
-        if l in (2, 4, 7, 10):
+        gm = rung.mask(g, acts[l], l in _SPLIT16_ACT, k)
+        g = rung.conv(gm, blobs[l], ops.CONV_CIN[l])
+        if l in _READS_POOL:
             s = ops.CONV_STAGE[l]
             g = ops.l2pool_backward_scaled(taps[s - 1], g, g_taps[s - 1], K)  # the tap's own gradient * 2^K + pool gradient
-        ops.grad_exponent(g, k, K)
+        rung.exponent(g, k, K)
     return ops.conv1_1_backward_scaled(g, acts[0], w0, k, K)  # d(ReLU) of relu1_1 and 2^-K inside
-
-
-def _pyramid_backward_half(module, acts, taps, g_taps, masked):
-    """The "f16" rung of pyramid_backward_device: the same activations, masks and walk, with the gradient between layers
-    as a plain half NHWC map.  Per layer and image: k with max|g| 2^k in [8, 16) (ops.grad_exponent_half), the masked,
-    scaled gradient rounded to half once (ops.relu_mask_f16_scaled), the data-gradient convolution on half weights with
-    one MFMA per product and a float32 accumulator, half out (ops.conv3x3_half).  g is float at the top and behind a pool
-    seam (whose taps, tap gradients and output stay float), half everywhere else; conv1_1's step takes the last half map
-    and applies 2^-K.  The window is four octaves below the split16 chain's because a convolution's output is a half
-    here: 16 times the largest L1 norm of a data-gradient filter has to stay below 65504."""
-    blobs, w0 = _backward_blobs(module, taps[0].device, "f16")
-    if not masked:
-        g_taps = [g * (t > 0) for g, t in zip(g_taps, taps)]
-    n, dev = taps[0].shape[0], taps[0].device
-    k = torch.empty(n, dtype=torch.int32, device=dev)
-    K = torch.zeros(n, dtype=torch.int32, device=dev)
-    g = ops._f32c(g_taps[4])
-    ops.grad_exponent_half(g, k, K)
-    for l in range(12, 0, -1):
-        gm = ops.relu_mask_f16_scaled(g, acts[l], l not in ops.TAP_LAYERS, k)
-        g = ops.conv3x3_half(gm, blobs[l], ops.CONV_CIN[l])
-        if l in (2, 4, 7, 10):
-            s = ops.CONV_STAGE[l]
-            g = ops.l2pool_backward_scaled_half(taps[s - 1], g, g_taps[s - 1], K)
-        ops.grad_exponent_half(g, k, K)
-    return ops.conv1_1_backward_scaled_half(g, acts[0], w0, k, K)
 
 
 def _image_stats(x, y):
@@ -355,18 +354,14 @@ def adists_backward_y(module, x, y, u):
 @torch.no_grad()
 def adists_y_forward(module, x, tx, y, keep=True, kept=None):
     """The first half of adists_backward_y, up to D: x, y float32 contiguous (B,3,H,W), tx the five float NHWC taps of x
-    (pyramid_taps).  Returns (D (B,), state) with state = (q, wgt, maps, acts, ty, pooled), what adists_y_backward
-    needs; keep=False runs y through pyramid_taps instead of pyramid_keep (acts and pooled are then None: a value
-    without a gradient to follow).  kept = (acts, ty, pooled): y's pyramid as a caller already holds it (the pair loss,
-    which shares it with DISTS); no pyramid launch runs here then, and `keep` is not looked at."""
+    (pyramid_taps).  Returns (D (B,), state: AdistsState), what adists_y_backward needs; keep=False runs y through
+    pyramid_taps instead of pyramid_keep (the pyramid's acts and pooled are then None: a value without a gradient to
+    follow).  kept = (acts, ty, pooled): y's pyramid as a caller already holds it (the pair loss, which shares it with
+    DISTS); no pyramid launch runs here then, and `keep` is not looked at."""
     b, _, h, w = x.shape
     prec, dev, ws = "f32s", x.device, module._ws
-    if kept is not None:
-        acts, ty, pooled = kept
-    elif keep:
-        acts, ty, pooled = pyramid_keep(module, y)
-    else:
-        acts, ty, pooled = None, pyramid_taps(module, y), None
+    pyramid = _pyramid_forward(module, y, keep) if kept is None else KeptPyramid(*kept)
+    ty = pyramid.taps
     # ---- what the head takes from x alone, and the per-channel scalars of both: the forward's own kernels ----
     q = torch.empty((8, b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
     wgt = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
@@ -382,22 +377,13 @@ def adists_y_forward(module, x, tx, y, keep=True, kept=None):
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     ops.adists_chain_into([m[0] for m in maps], [m[1] for m in maps], [m[2] for m in maps], h, w, [m[3] for m in maps], d,
                           None, ws)
-    return d, (q, wgt, maps, acts, ty, pooled)
-
-
-@torch.no_grad()
-def adists_y_backward(module, x, tx, y, state, u):
-    """The second half of adists_backward_y: dL/dy for dL/dD = u (B,) from what adists_y_forward(keep=True) returned:
-    the six stages' gradients towards y's maps, then the chain."""
-    acts, ty, pooled = state[3:]
-    g0, g_taps = _adists_y_tap_grads(module, x, tx, y, state, u)
-    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + g0
+    return d, AdistsState(q, wgt, maps, pyramid)
 
 
 def _adists_y_tap_grads(module, x, tx, y, state, u):
-    """(g0, g_taps) of adists_y_backward: the image term (B,3,H,W) and the five masked NHWC tap gradients, each a buffer
-    of its own that the caller may add to."""
-    q, wgt, maps, _, ty, _ = state
+    """(g0, g_taps) of A-DISTS towards y for dL/dD = u (B,): the image term (B,3,H,W) and the five masked NHWC tap
+    gradients, each a buffer of its own that the caller may add to."""
+    q, wgt, maps, ty = state.q, state.wgt, state.maps, state.pyramid.taps
     prec, ws = "f32s", module._ws
     g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws)
     off, g_taps = 3, []
@@ -406,6 +392,52 @@ def _adists_y_tap_grads(module, x, tx, y, state, u):
         g_taps.append(ops.adists_ts_backward(px, py, q, wgt, maps[k][3], u, mask=True, coff=off, nhwc=True, ws=ws))
         off += ops.CHNS[k]
     return g0, g_taps
+
+
+def _dists_y_tap_grads(target, ty, stats, g1, g2, into=None):
+    """(gy0, g_taps) of the DISTS statistics towards y for dL/dS1, dL/dS2 = g1, g2 (each (B, 1475)), from the forward's
+    kept sums `stats` (no second sums pass): tap 0's image term (B,3,H,W) and the five masked NHWC tap gradients -- fresh
+    maps, or ADDED in place into `into`, another metric's gradients of the same taps (no map of their own, no add pass)."""
+    g1, g2 = ops._f32c(g1), ops._f32c(g2)
+    off, g_taps = 3, []
+    for k, (fx, fy, part) in enumerate(zip(target.taps, ty, stats.parts)):
+        if into is None:
+            g_taps.append(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
+        else:
+            g_taps.append(ops.dists_stats_nhwc_grad_y_add(fx, fy, part, g1, g2, off, into[k]))
+        off += fx.shape[-1]
+    _, gy0 = _image_stats_grad_from(stats.fx0, stats.fy0, stats.scratch, g1, g2, (False, True))
+    return gy0, g_taps
+
+
+def _target_backward(module, pyramid, adists=None, dists=None):
+    """dL/dy over y's kept `pyramid`, the tail of every one-sided loss path: the tap gradients of the metrics in use (adists
+    / dists: the arguments of _adists_y_tap_grads / _dists_y_tap_grads; None runs nothing), DISTS' added into A-DISTS'
+    -- the chain is linear in them -- then ONE pyramid_backward_device on `module`'s blobs, then the image terms."""
+    terms, g_taps = [], None
+    if adists is not None:
+        g0, g_taps = _adists_y_tap_grads(*adists)
+        terms.append(g0)
+    if dists is not None:
+        gy0, g_taps = _dists_y_tap_grads(*dists, into=g_taps)
+        terms.append(gy0)
+    gy = pyramid_backward_device(module, pyramid.acts, pyramid.taps, pyramid.pooled, g_taps, masked=True)
+    for term in terms:
+        gy = gy + term
+    return gy
+
+
+def _loss_u(grad, b, as_loss):
+    """u = dL/dD (B,) on the device from the upstream gradient of 1 - mean(D) (as_loss) or of 1 - D (B,)."""
+    g = grad.detach().float()
+    return (g.reshape(1) * (-1.0 / b)).expand(b).contiguous() if as_loss else (-g).contiguous()
+
+
+@torch.no_grad()
+def adists_y_backward(module, x, tx, y, state, u):
+    """The second half of adists_backward_y: dL/dy for dL/dD = u (B,) from what adists_y_forward(keep=True) returned:
+    the six stages' gradients towards y's maps, then the chain."""
+    return _target_backward(module, state.pyramid, adists=(module, x, tx, y, state, u))
 
 
 class AdistsLossY(torch.autograd.Function):
@@ -424,9 +456,7 @@ class AdistsLossY(torch.autograd.Function):
         x, y = ctx.saved_tensors
         if not ctx.needs_input_grad[1]:
             return None, None, None
-        b = x.shape[0]
-        u = (grad.detach().float().reshape(1) * (-1.0 / b)).expand(b).contiguous()
-        return None, adists_backward_y(ctx.module, x, y, u).to(y.dtype), None
+        return None, adists_backward_y(ctx.module, x, y, _loss_u(grad, x.shape[0], True)).to(y.dtype), None
 
 
 def adists_target_fits(target) -> None:
@@ -465,9 +495,7 @@ class AdistsTargetLoss(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        b = y.shape[0]
-        g = grad.detach().float()
-        u = (g.reshape(1) * (-1.0 / b)).expand(b).contiguous() if ctx.as_loss else (-g).contiguous()
+        u = _loss_u(grad, y.shape[0], ctx.as_loss)
         t = ctx.target
         gy = adists_y_backward(ctx.module, t.x, list(t.taps), y.detach().float().contiguous(), ctx.state, u)
         return gy.to(y.dtype), None, None, None
@@ -518,9 +546,8 @@ class DistsSimilarities(torch.autograd.Function):
 
 @torch.no_grad()
 def dists_target_stats(target, y, ty):
-    """(S1, S2, kept) of a prepared target against y (float32 contiguous) with taps ty: per tap 1..5 the sums kernel and
-    the fold (ops.dists_stats_target), tap 0 through _image_stats.  kept = (the five taps' per-block fp64 partials, tap
-    0's maps and sums): where the backward starts."""
+    """(S1, S2, kept: TargetStats) of a prepared target against y (float32 contiguous) with taps ty: per tap 1..5 the
+    sums kernel and the fold (ops.dists_stats_target), tap 0 through _image_stats."""
     b, dev = y.shape[0], y.device
     s1 = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
     s2 = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
@@ -531,7 +558,7 @@ def dists_target_stats(target, y, ty):
     fx0, fy0, a1, a2, scratch = _image_stats(target.x, y)
     s1[:, :3] = a1[:, :3]
     s2[:, :3] = a2[:, :3]
-    return s1, s2, (parts, fx0, fy0, scratch)
+    return s1, s2, TargetStats(parts, fx0, fy0, scratch)
 
 
 def dists_target_similarities(module, target, y):
@@ -545,10 +572,10 @@ def dists_target_similarities(module, target, y):
 @torch.no_grad()
 def dists_target_forward(module, target, y):
     """(S1, S2, state) of a prepared target against y (float32 contiguous) WITH what a gradient needs: ONE kept pyramid
-    of y (pyramid_keep) and the statistics, whose fp64 partials are kept.  state = (acts, ty, pooled, kept)."""
-    acts, ty, pooled = pyramid_keep(module, y)
-    s1, s2, kept = dists_target_stats(target, y, ty)
-    return s1, s2, (acts, ty, pooled, kept)
+    of y (pyramid_keep) and the statistics, whose fp64 partials are kept.  state: DistsTargetState."""
+    pyramid = pyramid_keep(module, y)
+    s1, s2, stats = dists_target_stats(target, y, pyramid.taps)
+    return s1, s2, DistsTargetState(pyramid, stats)
 
 
 @torch.no_grad()
@@ -557,14 +584,7 @@ def dists_target_backward(module, target, state, g1, g2):
     gradient launches of the loss path started from the kept partials (no second sums pass, no pyramid), tap 0 from its
     kept sums, then pyramid_backward_device.  The same kernels on the same operands as dists_backward(need=(False,
     True)): that path's gradient bit for bit."""
-    acts, ty, pooled, (parts, fx0, fy0, scratch) = state
-    g1, g2 = ops._f32c(g1), ops._f32c(g2)
-    off, g_taps = 3, []
-    for fx, fy, part in zip(target.taps, ty, parts):
-        g_taps.append(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
-        off += fx.shape[-1]
-    _, gy0 = _image_stats_grad_from(fx0, fy0, scratch, g1, g2, (False, True))
-    return pyramid_backward_device(module, acts, ty, pooled, g_taps, masked=True) + gy0
+    return _target_backward(module, state.pyramid, dists=(target, state.pyramid.taps, state.stats, g1, g2))
 
 
 class DistsTargetSimilarities(torch.autograd.Function):
@@ -605,45 +625,23 @@ def pair_target_forward(adists_module, target, y):
     """(S1, S2, D, state) of a prepared target against y (float32 contiguous) WITH what a gradient of either metric
     needs: ONE kept pyramid of y (pyramid_keep on the target's owner), then dists_target_stats and the A-DISTS half of
     adists_y_forward on it -- the launches of dists_target_forward and of adists_target_d on the same operands, so the
-    values are theirs bit for bit.  state = (kept, astate): the statistics' partials and tap 0's scratch, and
-    adists_y_forward's state, which holds the pyramid."""
-    kept_pyramid = pyramid_keep(target.owner(), y)
-    s1, s2, kept = dists_target_stats(target, y, kept_pyramid[1])
-    d, astate = adists_target_d(adists_module, target, y, keep=True, kept=kept_pyramid)
-    return s1, s2, d, (kept, astate)
+    values are theirs bit for bit.  state: PairTargetState."""
+    pyramid = pyramid_keep(target.owner(), y)
+    s1, s2, stats = dists_target_stats(target, y, pyramid.taps)
+    d, astate = adists_target_d(adists_module, target, y, keep=True, kept=pyramid)
+    return s1, s2, d, PairTargetState(stats, astate)
 
 
 @torch.no_grad()
 def pair_target_backward(adists_module, target, y, state, g1, g2, u):
     """dL/dy from pair_target_forward's state, given dL/dS1, dL/dS2 (each (B, 1475), or both None: DISTS unused) and
-    u = dL/dD (B,) on the device (or None: A-DISTS unused).  The chain is linear in the tap gradients: A-DISTS writes its
-    five masked NHWC tap gradients (_adists_y_tap_grads), DISTS' are ADDED into them in place
-    (ops.dists_stats_nhwc_grad_y_add: no map of their own, no add pass), and ONE pyramid_backward_device carries the sum
-    down; the image terms are added at the end.  An unused metric runs none of its launches, and the result is then
-    dists_target_backward's / adists_y_backward's bit for bit.  The backward's weight blobs are the target's owner's."""
-    kept, astate = state
-    acts, ty, pooled = astate[3:]
-    terms, g_taps = [], None
-    if u is not None:
-        g0, g_taps = _adists_y_tap_grads(adists_module, target.x, list(target.taps), y, astate, u)
-        terms.append(g0)
-    if g1 is not None:
-        parts, fx0, fy0, scratch = kept
-        g1, g2 = ops._f32c(g1), ops._f32c(g2)
-        off, fresh = 3, g_taps is None
-        if fresh:
-            g_taps = []
-        for k, (fx, fy, part) in enumerate(zip(target.taps, ty, parts)):
-            if fresh:
-                g_taps.append(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
-            else:
-                ops.dists_stats_nhwc_grad_y_add(fx, fy, part, g1, g2, off, g_taps[k])
-            off += fx.shape[-1]
-        terms.append(_image_stats_grad_from(fx0, fy0, scratch, g1, g2, (False, True))[1])
-    gy = pyramid_backward_device(target.owner(), acts, ty, pooled, g_taps, masked=True)
-    for term in terms:
-        gy = gy + term
-    return gy
+    u = dL/dD (B,) on the device (or None: A-DISTS unused): _target_backward with both metrics, A-DISTS' tap gradients
+    written first and DISTS' added into them, one chain over the sum on the target's owner's weight blobs.  An unused
+    metric runs none of its launches; the result is then dists_target_backward's / adists_y_backward's bit for bit."""
+    pyramid = state.adists.pyramid
+    return _target_backward(target.owner(), pyramid,
+                            None if u is None else (adists_module, target.x, list(target.taps), y, state.adists, u),
+                            None if g1 is None else (target, pyramid.taps, state.stats, g1, g2))
 
 
 class PairTargetLoss(torch.autograd.Function):
@@ -668,10 +666,8 @@ class PairTargetLoss(torch.autograd.Function):
         if not ctx.needs_input_grad[0] or (g1 is None and g2 is None and ga is None):
             return None, None, None, None
         (y,) = ctx.saved_tensors
-        b, u = y.shape[0], None
-        if ga is not None:
-            g = ga.detach().float()
-            u = (g.reshape(1) * (-1.0 / b)).expand(b).contiguous() if ctx.as_loss else (-g).contiguous()
+        b = y.shape[0]
+        u = None if ga is None else _loss_u(ga, b, ctx.as_loss)
         if (g1 is None) != (g2 is None):  # a loss over one of S1 / S2 alone: the other's upstream is zero
             zero = torch.zeros((b, ops.TOTAL_CHNS), dtype=torch.float32, device=y.device)
             g1, g2 = (zero if g1 is None else g1), (zero if g2 is None else g2)

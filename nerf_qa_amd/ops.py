@@ -937,17 +937,22 @@ def split16_decode(a: torch.Tensor) -> torch.Tensor:
 
 
 # ---- backward pass of the DISTS pyramid (require_grad=True; include/nqa.h, nqa_backward.hip) -----------------------
-def pack_conv_split(w) -> torch.Tensor:
-    """One 3x3 layer (float32 OIHW, cout % 64 == 0, cin % 16 == 0) in the f32s row format, zero bias -> CPU uint8 blob."""
+def _pack_conv(fmt: str, w) -> torch.Tensor:
+    """One 3x3 layer (float32 OIHW), zero bias -> CPU uint8 blob by the library's packer of row format `fmt`."""
     w = np.ascontiguousarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32)
     cout, cin = int(w.shape[0]), int(w.shape[1])
     assert w.shape[2:] == (3, 3)
-    nbytes = lib().nqa_packed_conv_split_bytes(cout, cin)
+    nbytes = getattr(lib(), f"nqa_packed_conv_{fmt}_bytes")(cout, cin)
     if not nbytes:
-        raise ValueError(f"pack_conv_split: unsupported layer shape {w.shape}")
+        raise ValueError(f"pack_conv_{fmt}: unsupported layer shape {w.shape}")
     blob = torch.empty(nbytes, dtype=torch.uint8)
-    check(lib().nqa_pack_conv_split(w.ctypes.data, cout, cin, blob.data_ptr()))
+    check(getattr(lib(), f"nqa_pack_conv_{fmt}")(w.ctypes.data, cout, cin, blob.data_ptr()))
     return blob
+
+
+def pack_conv_split(w) -> torch.Tensor:
+    """One 3x3 layer (float32 OIHW, cout % 64 == 0, cin % 16 == 0) in the f32s row format, zero bias -> CPU uint8 blob."""
+    return _pack_conv("split", w)
 
 
 def conv3x3_split(inp: torch.Tensor, blob: torch.Tensor, cout: int, relu: bool = False) -> torch.Tensor:
@@ -995,6 +1000,16 @@ def conv1_1_backward(gm: torch.Tensor, w0: torch.Tensor) -> torch.Tensor:
 
 
 # ---- DISTS as a loss: the same chain without a device -> host read (include/nqa.h, nqa_loss_backward.hip) ----------
+def _tap_grad_maps(tx: torch.Tensor, need_x: bool, need_y: bool, out_x: torch.Tensor | None, out_y: torch.Tensor | None):
+    """(gx, gy) the statistics-gradient wrappers write: per side the caller's out_x / out_y, else a new map like the
+    tap tx, None where it is not needed; contiguous float maps of the tap's shape on its device."""
+    gx = (torch.empty_like(tx) if out_x is None else out_x) if need_x else None
+    gy = (torch.empty_like(tx) if out_y is None else out_y) if need_y else None
+    for g in (gx, gy):
+        assert g is None or (g.shape == tx.shape and g.dtype == torch.float32 and g.is_contiguous() and g.device == tx.device)
+    return gx, gy
+
+
 def dists_stats_nhwc_backward(tx: torch.Tensor, ty: torch.Tensor, g_s1: torch.Tensor, g_s2: torch.Tensor, col: int,
                               need_x: bool = True, need_y: bool = True, out_x: torch.Tensor | None = None,
                               out_y: torch.Tensor | None = None):
@@ -1007,10 +1022,7 @@ def dists_stats_nhwc_backward(tx: torch.Tensor, ty: torch.Tensor, g_s1: torch.Te
     b, h, w, c = tx.shape
     if g_s1.shape != g_s2.shape or g_s1.dim() != 2 or g_s1.shape[0] != b or col < 0 or col + c > g_s1.shape[1]:
         raise ValueError(f"expected gradients of shape ({b}, >= {col + c}), got {tuple(g_s1.shape)} / {tuple(g_s2.shape)}")
-    gx = (torch.empty_like(tx) if out_x is None else out_x) if need_x else None
-    gy = (torch.empty_like(ty) if out_y is None else out_y) if need_y else None
-    for g in (gx, gy):
-        assert g is None or (g.shape == tx.shape and g.dtype == torch.float32 and g.is_contiguous())
+    gx, gy = _tap_grad_maps(tx, need_x, need_y, out_x, out_y)
     if gx is None and gy is None:
         return None, None
     nbytes = lib().nqa_dists_stats_nhwc_backward_bytes(b, h, w, c)
@@ -1057,10 +1069,7 @@ def dists_stats_nhwc_backward_from(tx: torch.Tensor, ty: torch.Tensor, part: tor
     dev = _tap_pair("dists_stats_nhwc_backward_from", tx, ty, g_s1, g_s2, col)
     assert part.dtype == torch.uint8 and part.is_contiguous() and part.device == dev
     b, h, w, c = tx.shape
-    gx = (torch.empty_like(tx) if out_x is None else out_x) if need_x else None
-    gy = (torch.empty_like(ty) if out_y is None else out_y) if need_y else None
-    for g in (gx, gy):
-        assert g is None or (g.shape == tx.shape and g.dtype == torch.float32 and g.is_contiguous())
+    gx, gy = _tap_grad_maps(tx, need_x, need_y, out_x, out_y)
     if gx is None and gy is None:
         return None, None
     nbytes = lib().nqa_dists_stats_nhwc_backward_from_bytes(b, c)
@@ -1080,7 +1089,7 @@ def dists_stats_nhwc_grad_y_add(tx: torch.Tensor, ty: torch.Tensor, part: torch.
     (another metric's gradient of the same tap).  Returns gy."""
     dev = _tap_pair("dists_stats_nhwc_grad_y_add", tx, ty, g_s1, g_s2, col)
     assert part.dtype == torch.uint8 and part.is_contiguous() and part.device == dev
-    assert gy.shape == ty.shape and gy.dtype == torch.float32 and gy.is_contiguous() and gy.device == dev
+    _tap_grad_maps(tx, False, True, None, gy)
     b, h, w, c = tx.shape
     nbytes = lib().nqa_dists_stats_nhwc_backward_from_bytes(b, c)
     if not nbytes:
@@ -1091,22 +1100,28 @@ def dists_stats_nhwc_grad_y_add(tx: torch.Tensor, ty: torch.Tensor, part: torch.
     return gy
 
 
-def grad_exponent(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
-    """k[i] (int32, on the device) = the exponent with max|g[i]| * 2^k[i] in [128, 256), 0 where that maximum is 0 or
-    not finite; k_total[i] += k[i].  g: float, image i = g[i].  Nothing comes back to the host."""
+def _exponent_args(who: str, g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None):
+    """What grad_exponent and grad_exponent_half check and allocate alike: g contiguous, k and k_total int32 with one
+    entry per image g[i] -> (device, images, elements per image, the reduction's scratch, k_total's pointer or None)."""
     dev = _need_cuda(g, k)
     n = g.shape[0]
-    assert g.dtype == torch.float32 and g.is_contiguous()
+    assert g.is_contiguous()
     assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
     assert k_total is None or (k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
                                and k_total.device == dev)
     per = g.numel() // n
     nbytes = lib().nqa_grad_exponent_bytes(n, per)
     if not nbytes:
-        raise _lib.NqaError(f"grad_exponent: unsupported shape {tuple(g.shape)} (elements per image must be a multiple of 4)")
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _call(dev, lib().nqa_grad_exponent, ptr(g), n, per, ptr(buf), buf.numel(), ptr(k), None if k_total is None else ptr(k_total),
-          stream_ptr(dev))
+        raise _lib.NqaError(f"{who}: unsupported shape {tuple(g.shape)} (elements per image must be a multiple of 4)")
+    return dev, n, per, torch.empty(nbytes, dtype=torch.uint8, device=dev), None if k_total is None else ptr(k_total)
+
+
+def grad_exponent(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
+    """k[i] (int32, on the device) = the exponent with max|g[i]| * 2^k[i] in [128, 256), 0 where that maximum is 0 or
+    not finite; k_total[i] += k[i].  g: float, image i = g[i].  Nothing comes back to the host."""
+    assert g.dtype == torch.float32
+    dev, n, per, buf, kt = _exponent_args("grad_exponent", g, k, k_total)
+    _call(dev, lib().nqa_grad_exponent, ptr(g), n, per, ptr(buf), buf.numel(), ptr(k), kt, stream_ptr(dev))
 
 
 def relu_mask_split16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16: bool, k: torch.Tensor) -> torch.Tensor:
@@ -1123,25 +1138,31 @@ def relu_mask_split16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16:
 
 
 def l2pool_backward_scaled(tap: torch.Tensor, g_pooled: torch.Tensor, g_tap: torch.Tensor, k_total: torch.Tensor) -> torch.Tensor:
-    """g_tap * 2^k_total[image] + d(L2-pool)/d(tap) applied to g_pooled, as a new float (n,H,W,C) tensor."""
+    """g_tap * 2^k_total[image] + d(L2-pool)/d(tap) applied to g_pooled, as a new float (n,H,W,C) tensor.  g_pooled: a
+    float map or a half one (the f16 chain's), each through its own entry point; the two agree bit for bit on the halves
+    converted to float (include/nqa.h)."""
     dev = _need_cuda(tap, g_pooled, g_tap, k_total)
     n, h, w, c = tap.shape
     assert tap.dtype == torch.float32 and tap.is_contiguous()
     assert g_tap.shape == tap.shape and g_tap.dtype == torch.float32 and g_tap.is_contiguous()
     assert g_pooled.shape == (n, (h + 1) // 2, (w + 1) // 2, c)
     assert k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
+    half = g_pooled.dtype == torch.float16
+    g_pooled = g_pooled.contiguous() if half else _f32c(g_pooled)
     out = torch.empty_like(tap)
-    _call(dev, lib().nqa_l2pool_backward_scaled, ptr(tap), ptr(_f32c(g_pooled)), ptr(g_tap), ptr(k_total), n, h, w, c, ptr(out),
-          stream_ptr(dev))
+    _call(dev, lib().nqa_l2pool_backward_scaled_half if half else lib().nqa_l2pool_backward_scaled, ptr(tap), ptr(g_pooled),
+          ptr(g_tap), ptr(k_total), n, h, w, c, ptr(out), stream_ptr(dev))
     return out
 
 
 def conv1_1_backward_scaled(g: torch.Tensor, relu1_1_split16: torch.Tensor | None, w0: torch.Tensor, k: torch.Tensor,
                             k_total: torch.Tensor) -> torch.Tensor:
     """conv1_1_backward(g * 2^k[image] * (relu1_1 > 0), w0) * 2^-k_total[image]: float NHWC (n,H,W,64) -> float NCHW
-    (n,3,H,W).  relu1_1_split16: conv1_1's f32s output (None: no mask)."""
+    (n,3,H,W).  relu1_1_split16: conv1_1's f32s output (None: no mask).  g: a float map or a half one (the f16 chain's),
+    each through its own entry point; the two agree bit for bit on the halves converted to float (include/nqa.h)."""
     dev = _need_cuda(g, w0, k, k_total)
-    g, w0 = _f32c(g), _f32c(w0)
+    half = g.dtype == torch.float16
+    g, w0 = (g.contiguous() if half else _f32c(g)), _f32c(w0)
     n, h, w, c = g.shape
     assert c == 64 and tuple(w0.shape) == (64, 3, 3, 3)
     assert relu1_1_split16 is None or (relu1_1_split16.shape == g.shape and relu1_1_split16.dtype == torch.float32
@@ -1149,23 +1170,16 @@ def conv1_1_backward_scaled(g: torch.Tensor, relu1_1_split16: torch.Tensor | Non
     for t in (k, k_total):
         assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
-    _call(dev, lib().nqa_conv1_1_backward_scaled, ptr(g), None if relu1_1_split16 is None else ptr(relu1_1_split16), ptr(w0),
-          ptr(k), ptr(k_total), n, h, w, ptr(out), stream_ptr(dev))
+    _call(dev, lib().nqa_conv1_1_backward_scaled_half if half else lib().nqa_conv1_1_backward_scaled, ptr(g),
+          None if relu1_1_split16 is None else ptr(relu1_1_split16), ptr(w0), ptr(k), ptr(k_total), n, h, w, ptr(out),
+          stream_ptr(dev))
     return out
 
 
 # ---- the half gradient chain: grad_precision="f16" (include/nqa.h, "The same chain on HALF gradient maps") ----------
 def pack_conv_half(w) -> torch.Tensor:
     """One 3x3 layer (float32 OIHW, cout % 64 == 0, cin % 32 == 0) as f16 rows, zero bias -> CPU uint8 blob."""
-    w = np.ascontiguousarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32)
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    assert w.shape[2:] == (3, 3)
-    nbytes = lib().nqa_packed_conv_half_bytes(cout, cin)
-    if not nbytes:
-        raise ValueError(f"pack_conv_half: unsupported layer shape {w.shape}")
-    blob = torch.empty(nbytes, dtype=torch.uint8)
-    check(lib().nqa_pack_conv_half(w.ctypes.data, cout, cin, blob.data_ptr()))
-    return blob
+    return _pack_conv("half", w)
 
 
 def _is_grad_map(g: torch.Tensor) -> bool:
@@ -1186,18 +1200,9 @@ def conv3x3_half(inp: torch.Tensor, blob: torch.Tensor, cout: int) -> torch.Tens
 
 def grad_exponent_half(g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None = None) -> None:
     """grad_exponent for the half chain: k[i] with max|g[i]| * 2^k[i] in [8, 16); g float or half, image i = g[i]."""
-    dev = _need_cuda(g, k)
-    n, half = g.shape[0], _is_grad_map(g)
-    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == n
-    assert k_total is None or (k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
-                               and k_total.device == dev)
-    per = g.numel() // n
-    nbytes = lib().nqa_grad_exponent_bytes(n, per)
-    if not nbytes:
-        raise _lib.NqaError(f"grad_exponent_half: unsupported shape {tuple(g.shape)}")
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _call(dev, lib().nqa_grad_exponent_half, ptr(g), int(half), n, per, ptr(buf), buf.numel(), ptr(k),
-          None if k_total is None else ptr(k_total), stream_ptr(dev))
+    half = _is_grad_map(g)
+    dev, n, per, buf, kt = _exponent_args("grad_exponent_half", g, k, k_total)
+    _call(dev, lib().nqa_grad_exponent_half, ptr(g), int(half), n, per, ptr(buf), buf.numel(), ptr(k), kt, stream_ptr(dev))
 
 
 def relu_mask_f16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16: bool, k: torch.Tensor) -> torch.Tensor:
@@ -1211,39 +1216,6 @@ def relu_mask_f16_scaled(g: torch.Tensor, act: torch.Tensor, act_is_split16: boo
     out = torch.empty(g.shape, dtype=torch.float16, device=dev)
     _call(dev, lib().nqa_relu_mask_f16_scaled, ptr(g), int(half), ptr(act), int(act_is_split16), n, g.numel() // (n * c), c,
           ptr(k), ptr(out), stream_ptr(dev))
-    return out
-
-
-def l2pool_backward_scaled_half(tap: torch.Tensor, g_pooled: torch.Tensor, g_tap: torch.Tensor,
-                                k_total: torch.Tensor) -> torch.Tensor:
-    """l2pool_backward_scaled with a half g_pooled: a new float (n,H,W,C) tensor."""
-    dev = _need_cuda(tap, g_pooled, g_tap, k_total)
-    n, h, w, c = tap.shape
-    assert tap.dtype == torch.float32 and tap.is_contiguous()
-    assert g_tap.shape == tap.shape and g_tap.dtype == torch.float32 and g_tap.is_contiguous()
-    assert g_pooled.shape == (n, (h + 1) // 2, (w + 1) // 2, c) and g_pooled.dtype == torch.float16 and g_pooled.is_contiguous()
-    assert k_total.dtype == torch.int32 and k_total.is_contiguous() and k_total.numel() == n
-    out = torch.empty_like(tap)
-    _call(dev, lib().nqa_l2pool_backward_scaled_half, ptr(tap), ptr(g_pooled), ptr(g_tap), ptr(k_total), n, h, w, c, ptr(out),
-          stream_ptr(dev))
-    return out
-
-
-def conv1_1_backward_scaled_half(g: torch.Tensor, relu1_1_split16: torch.Tensor | None, w0: torch.Tensor, k: torch.Tensor,
-                                 k_total: torch.Tensor) -> torch.Tensor:
-    """conv1_1_backward_scaled with a half g (n,H,W,64) -> float NCHW (n,3,H,W)."""
-    dev = _need_cuda(g, w0, k, k_total)
-    w0 = _f32c(w0)
-    assert g.dtype == torch.float16 and g.is_contiguous()
-    n, h, w, c = g.shape
-    assert c == 64 and tuple(w0.shape) == (64, 3, 3, 3)
-    assert relu1_1_split16 is None or (relu1_1_split16.shape == g.shape and relu1_1_split16.dtype == torch.float32
-                                       and relu1_1_split16.is_contiguous() and relu1_1_split16.device == dev)
-    for t in (k, k_total):
-        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n
-    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
-    _call(dev, lib().nqa_conv1_1_backward_scaled_half, ptr(g), None if relu1_1_split16 is None else ptr(relu1_1_split16),
-          ptr(w0), ptr(k), ptr(k_total), n, h, w, ptr(out), stream_ptr(dev))
     return out
 
 

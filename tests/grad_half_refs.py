@@ -1,4 +1,4 @@
-"""A CPU emulation of the half gradient chain (grad_precision="f16": nerf_qa_amd/autograd.py, _pyramid_backward_half), the
+"""A CPU emulation of the half gradient chain (grad_precision="f16": nerf_qa_amd/autograd.py, pyramid_backward_device), the
 yardstick of its tests.
 
 It is tests/grad_replay.py's walk -- the same masks, the same transposed convolutions, the same pool Jacobian -- with

@@ -165,7 +165,7 @@ def test_l2pool_backward_scaled_half_equals_the_float_form(h, w, c):
     g_tap = (torch.randn((n, h, w, c), generator=gen) * 1e-6).to(DEV)
     gp = (torch.randn((n, (h + 1) // 2, (w + 1) // 2, c), generator=gen) * 9.0).to(torch.float16).to(DEV)
     K = torch.tensor([17, 21], dtype=torch.int32, device=DEV)
-    got = ops.l2pool_backward_scaled_half(tap, gp, g_tap, K)
+    got = ops.l2pool_backward_scaled(tap, gp, g_tap, K)
     want = ops.l2pool_backward_scaled(tap, gp.float(), g_tap, K)
     torch.cuda.synchronize()
     assert torch.isfinite(want).all() and want.abs().max().item() > 0
@@ -183,7 +183,7 @@ def test_conv1_1_backward_scaled_half_equals_the_float_form(h, w, masked):
     w0 = (torch.randn((64, 3, 3, 3), generator=gen) * 0.1).to(DEV)
     k = torch.tensor([4, -2], dtype=torch.int32, device=DEV)
     K = torch.tensor([30, 11], dtype=torch.int32, device=DEV)
-    got = ops.conv1_1_backward_scaled_half(g, act0, w0, k, K)
+    got = ops.conv1_1_backward_scaled(g, act0, w0, k, K)
     want = ops.conv1_1_backward_scaled(g.float(), act0, w0, k, K)
     torch.cuda.synchronize()
     assert got.shape == (n, 3, h, w) and torch.isfinite(want).all() and want.abs().max().item() > 0

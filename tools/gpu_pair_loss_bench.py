@@ -150,10 +150,10 @@ def one_shape(shape, baseline_only, say, grad_precision=None):
         return (autograd.dists_target_backward(dm, td, ds, g1, g2)
                 + autograd.adists_y_backward(am, ta.x, list(ta.taps), y0, st, u))
 
-    state = autograd.pair_target_forward(am, td, y0)[3]
+    _, _, _, state = autograd.pair_target_forward(am, td, y0)
 
     def pair_halves():
-        st = autograd.pair_target_forward(am, td, y0)[3]
+        _, _, _, st = autograd.pair_target_forward(am, td, y0)
         return autograd.pair_target_backward(am, td, y0, st, g1, g2, u)
 
     def pair_backward():
@@ -161,16 +161,12 @@ def one_shape(shape, baseline_only, say, grad_precision=None):
 
     def pair_backward_torch_add():
         """pair_target_backward with the DISTS tap gradients in maps of their own, added by torch."""
-        kept, astate = state
-        acts, ty, pooled = astate[3:]
-        g0, g_taps = autograd._adists_y_tap_grads(am, td.x, list(td.taps), y0, astate, u)
-        parts, fx0, fy0, scratch = kept
-        off = 3
-        for k, (fx, fy, part) in enumerate(zip(td.taps, ty, parts)):
-            g_taps[k].add_(ops.dists_stats_nhwc_backward_from(fx, fy, part, g1, g2, off, need_x=False)[1])
-            off += fx.shape[-1]
-        gy0 = autograd._image_stats_grad_from(fx0, fy0, scratch, g1, g2, (False, True))[1]
-        return autograd.pyramid_backward_device(dm, acts, ty, pooled, g_taps, masked=True) + g0 + gy0
+        pyramid = state.adists.pyramid
+        g0, g_taps = autograd._adists_y_tap_grads(am, td.x, list(td.taps), y0, state.adists, u)
+        gy0, d_taps = autograd._dists_y_tap_grads(td, pyramid.taps, state.stats, g1, g2)
+        for g, d in zip(g_taps, d_taps):
+            g.add_(d)
+        return autograd.pyramid_backward_device(dm, pyramid.acts, pyramid.taps, pyramid.pooled, g_taps, masked=True) + g0 + gy0
 
     say("  per step, halves called on one thread (timing ring: per-class device time; the event time beside it):")
     for name, fn in (("(a) separate", separate_halves), ("(b) pair", pair_halves)):
