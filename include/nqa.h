@@ -199,6 +199,19 @@ size_t nqa_dists_group_stats_bytes(int R, int K, int HW, int C, int prec, int nc
 int nqa_dists_group_stats(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
                           size_t scratch_bytes, float *s1, float *s2, void *stream);
 
+/* The group statistics' five sums and their launch plan, for tests and tools: nqa_dists_group_stats' launch, unchanged
+ * (the same arguments, the same scratch, the same refusals under the name dists_group_sums, plus a null sums), and one
+ * fold of its per-block fp64 partials in place of the finalisation.
+ *   sums     dev double (R * K, C, 5) = {sum x, sum y, sum x^2, sum y^2, sum xy} over the HW stored values of pair
+ *            p = r * K + k, per channel; x is reference r, y its render k.
+ * nqa_dists_group_stats_grid: out[0..3] = pixels per block, blocks per map, pixels a block takes side by side (256 for
+ * planes), the largest number of strip items a thread holds (at most 16), from the launcher's own planning functions.
+ * Host-only, touches no device; refuses (NQA_E_ARG / NQA_E_SHAPE) what nqa_dists_group_stats_bytes answers with 0, and a
+ * null out. */
+int nqa_dists_group_sums(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
+                         size_t scratch_bytes, double *sums, void *stream);
+int nqa_dists_group_stats_grid(int R, int K, int HW, int C, int prec, int nchw, int out[4]);
+
 /* The PAIR path's two statistics passes on their own, for tests and tools: the launch functions nqa_dists_forward and
  * nqa_adists_forward enqueue for a tapped map, unchanged, and one fold of their per-block fp64 partials.
  *   nqa_pool_stats   L2pooling.forward (DISTS_pt.py:22-25) and the five sums behind DISTS_pt.py:131-139 of ONE tap in one

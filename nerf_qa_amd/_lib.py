@@ -50,6 +50,8 @@ _SIGNATURES = {
     "nqa_dists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
     "nqa_dists_group_stats_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "nqa_dists_group_stats": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_dists_group_sums": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "nqa_dists_group_stats_grid": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "nqa_pool_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "nqa_stats_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nqa_pool_stats_grid": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),

@@ -560,45 +560,53 @@ size_t nqa_dists_group_stats_bytes(int R, int K, int HW, int C, int prec, int nc
   return align_up(group_stats_plan(R, K, &C, &HW, &planes, &prec, 1).doubles * 8, 256);
 }
 
+// The checks and the launch shared by nqa_dists_group_stats and nqa_dists_group_sums (`who` names the caller in the
+// messages; the null-pointer check is the caller's): the partials land in `scratch` in the layout of *plan.
+static int group_stats_launch(const char *who, const void *feat, int R, int K, int HW, int C, int prec, int nchw,
+                              void *scratch, size_t scratch_bytes, StatsPlan *plan, hipStream_t st) {
+  if (bad_group(who, R, K)) return NQA_E_ARG;
+  if (HW <= 0 || C <= 0) {
+    set_error("%s: non-positive size HW=%d C=%d", who, HW, C);
+    return NQA_E_ARG;
+  }
+  if (!prec_valid(prec)) {
+    set_error(is_mixed(prec) ? "%s: takes no mixed mode (prec %d): pass the kernel precision of the map's own stage"
+                             : "%s: unknown prec %d", who, prec);
+    return NQA_E_ARG;
+  }
+  const long eb = nchw ? 4 : (long)prec_elem_bytes(prec);  // (planes are float whatever prec is)
+  if ((long)HW * C * eb >= (1L << 31)) {
+    set_error("%s: map too large (HW*%d channels*%d bytes >= 2^31)", who, C, (int)eb);
+    return NQA_E_ARG;
+  }
+  if (!nchw && !group_stats_nhwc_ok(C, prec)) {
+    set_error("%s: no NHWC kernel for C=%d in prec %d (whole 16-byte groups, a power-of-two number of them)", who, C, prec);
+    return NQA_E_SHAPE;
+  }
+  const bool planes = nchw != 0;
+  *plan = group_stats_plan(R, K, &C, &HW, &planes, &prec, 1);
+  if (scratch_bytes < plan->doubles * 8) {
+    set_error("%s: scratch %zu < %zu bytes", who, scratch_bytes, plan->doubles * 8);
+    return NQA_E_WORKSPACE;
+  }
+  double *part = static_cast<double *>(scratch);
+  const size_t map_bytes = (size_t)HW * C * eb;
+  const char *ren = static_cast<const char *>(feat) + (size_t)R * map_bytes;
+  return nchw ? group_stats_nchw(static_cast<const float *>(feat), reinterpret_cast<const float *>(ren), R, K, C, HW, part, st)
+              : group_stats_nhwc(feat, ren, R, K, HW, C, prec, part, st);
+}
+
 int nqa_dists_group_stats(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
                           size_t scratch_bytes, float *s1, float *s2, void *stream) {
   if (!feat || !scratch || !s1 || !s2) {
     set_error("dists_group_stats: null pointer");
     return NQA_E_ARG;
   }
-  if (bad_group("dists_group_stats", R, K)) return NQA_E_ARG;
-  if (HW <= 0 || C <= 0) {
-    set_error("dists_group_stats: non-positive size HW=%d C=%d", HW, C);
-    return NQA_E_ARG;
-  }
-  if (!prec_valid(prec)) {
-    set_error(is_mixed(prec) ? "dists_group_stats: takes no mixed mode (prec %d): pass the kernel precision of the map's own stage"
-                             : "dists_group_stats: unknown prec %d", prec);
-    return NQA_E_ARG;
-  }
-  const long eb = nchw ? 4 : (long)prec_elem_bytes(prec);  // (planes are float whatever prec is)
-  if ((long)HW * C * eb >= (1L << 31)) {
-    set_error("dists_group_stats: map too large (HW*%d channels*%d bytes >= 2^31)", C, (int)eb);
-    return NQA_E_ARG;
-  }
-  if (!nchw && !group_stats_nhwc_ok(C, prec)) {
-    set_error("dists_group_stats: no NHWC kernel for C=%d in prec %d (whole 16-byte groups, a power-of-two number of them)", C, prec);
-    return NQA_E_SHAPE;
-  }
-  const bool planes = nchw != 0;
-  const StatsPlan p = group_stats_plan(R, K, &C, &HW, &planes, &prec, 1);
-  if (scratch_bytes < p.doubles * 8) {
-    set_error("dists_group_stats: scratch %zu < %zu bytes", scratch_bytes, p.doubles * 8);
-    return NQA_E_WORKSPACE;
-  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  double *part = static_cast<double *>(scratch);
-  const size_t map_bytes = (size_t)HW * C * eb;
-  const char *ren = static_cast<const char *>(feat) + (size_t)R * map_bytes;
-  const int rc = nchw ? group_stats_nchw(static_cast<const float *>(feat), reinterpret_cast<const float *>(ren), R, K, C, HW, part, st)
-                      : group_stats_nhwc(feat, ren, R, K, HW, C, prec, part, st);
+  StatsPlan p;
+  const int rc = group_stats_launch("dists_group_stats", feat, R, K, HW, C, prec, nchw, scratch, scratch_bytes, &p, st);
   if (rc) return rc;
-  return finalize(part, p.d, R * K, s1, s2, st);
+  return finalize(static_cast<const double *>(scratch), p.d, R * K, s1, s2, st);
 }
 
 size_t nqa_stats_scratch_bytes(int B, const int C[NQA_NUM_TAPS], const int Hk[NQA_NUM_TAPS],
@@ -897,6 +905,44 @@ int nqa_stats_nhwc(const void *feat, int B, int HW, int C, int prec, double *sum
   double *part = static_cast<double *>(ws);
   if ((rc = stats_nhwc(feat, B, HW, C, prec, part, st))) return rc;
   return fold_partials(part, B, nblk, C, sums, st);
+}
+
+// ---- the group statistics' five sums and plan (tests, tools): nqa_dists_group_stats' launch, folded instead of finalised ----
+int nqa_dists_group_sums(const void *feat, int R, int K, int HW, int C, int prec, int nchw, void *scratch,
+                         size_t scratch_bytes, double *sums, void *stream) {
+  if (!feat || !scratch || !sums) {
+    set_error("dists_group_sums: null pointer");
+    return NQA_E_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  StatsPlan p;
+  const int rc = group_stats_launch("dists_group_sums", feat, R, K, HW, C, prec, nchw, scratch, scratch_bytes, &p, st);
+  if (rc) return rc;
+  return fold_partials(static_cast<const double *>(scratch), R * K, p.d.nblk[0], C, sums, st);
+}
+int nqa_dists_group_stats_grid(int R, int K, int HW, int C, int prec, int nchw, int out[4]) {
+  if (!out) {
+    set_error("dists_group_stats_grid: null pointer");
+    return NQA_E_ARG;
+  }
+  if (bad_group("dists_group_stats_grid", R, K)) return NQA_E_ARG;
+  if (HW <= 0 || C <= 0) {
+    set_error("dists_group_stats_grid: non-positive size HW=%d C=%d", HW, C);
+    return NQA_E_ARG;
+  }
+  if (!prec_valid(prec)) {
+    set_error("dists_group_stats_grid: prec %d is not one of the kernel-level modes", prec);
+    return NQA_E_ARG;
+  }
+  if (!nchw && !group_stats_nhwc_ok(C, prec)) {
+    set_error("dists_group_stats_grid: no NHWC kernel for C=%d in prec %d", C, prec);
+    return NQA_E_SHAPE;
+  }
+  out[0] = nchw ? stats_nchw_ppb(HW) : group_stats_units_per_block(HW, C, prec, R);
+  out[1] = cdiv(HW, out[0]);
+  out[2] = nchw ? 256 : 256 / (C / (int)(16 / prec_elem_bytes(prec)));
+  out[3] = cdiv(out[0] < HW ? out[0] : HW, out[2]);
+  return NQA_OK;
 }
 
 int nqa_dists_score(const float *s1, const float *s2, const float *alpha, const float *beta, int B, float *out,

@@ -396,28 +396,62 @@ def dists_forward_group(ref: torch.Tensor, renders: torch.Tensor, packed: torch.
     return s1, s2
 
 
-def dists_group_stats(feat: torch.Tensor, r: int, k: int, prec, nchw: bool = False):
-    """(S1, S2), each float32 (r*k, C), of ONE map's group statistics as dists_forward_group launches them (include/nqa.h,
-    nqa_dists_group_stats).  feat holds n = r + r*k maps, the r references first, render (i, j) at map r + i*k + j:
-    nchw=True float32 planes (n, C, HW); else NHWC (n, HW, C) in prec's storage type."""
-    p = prec_id(prec)
-    dev = _need_cuda(feat)
-    r, k = int(r), int(k)
+def _group_maps(who: str, feat: torch.Tensor, r: int, k: int, p: int, nchw: bool):
+    """(C, HW) of the n = r + r*k maps of a group statistics call; ValueError where feat does not fit."""
     if p not in PREC_DTYPE:
-        raise ValueError(f"dists_group_stats: prec {p} is not one of the kernel-level modes")
+        raise ValueError(f"{who}: prec {p} is not one of the kernel-level modes")
     want = torch.float32 if nchw else PREC_DTYPE[p]
     if feat.dim() != 3 or r <= 0 or k <= 0 or feat.shape[0] != r + r * k or feat.numel() == 0 or feat.dtype != want \
             or not feat.is_contiguous():
-        raise ValueError(f"dists_group_stats: expected contiguous {want} ({r + r * k}, "
+        raise ValueError(f"{who}: expected contiguous {want} ({r + r * k}, "
                          f"{'C, HW' if nchw else 'HW, C'}), got {feat.dtype} {tuple(feat.shape)}")
-    c, hw = (int(feat.shape[1]), int(feat.shape[2])) if nchw else (int(feat.shape[2]), int(feat.shape[1]))
-    s1 = torch.empty((r * k, c), dtype=torch.float32, device=dev)
-    s2 = torch.empty((r * k, c), dtype=torch.float32, device=dev)
+    return (int(feat.shape[1]), int(feat.shape[2])) if nchw else (int(feat.shape[2]), int(feat.shape[1]))
+
+
+def dists_group_stats(feat: torch.Tensor, r: int, k: int, prec, nchw: bool = False, s1: torch.Tensor | None = None,
+                      s2: torch.Tensor | None = None, scratch: torch.Tensor | None = None):
+    """(S1, S2), each float32 (r*k, C), of ONE map's group statistics as dists_forward_group launches them (include/nqa.h,
+    nqa_dists_group_stats).  feat holds n = r + r*k maps, the r references first, render (i, j) at map r + i*k + j:
+    nchw=True float32 planes (n, C, HW); else NHWC (n, HW, C) in prec's storage type.  s1, s2: as conv_pool_stats'
+    outputs; scratch: a uint8 tensor of at least nqa_dists_group_stats_bytes to use instead of a new one."""
+    p = prec_id(prec)
+    dev = _need_cuda(feat)
+    r, k = int(r), int(k)
+    c, hw = _group_maps("dists_group_stats", feat, r, k, p, nchw)
+    s1 = _out_or_empty(s1, (r * k, c), torch.float32, dev)
+    s2 = _out_or_empty(s2, (r * k, c), torch.float32, dev)
     nbytes = lib().nqa_dists_group_stats_bytes(r, k, hw, c, p, int(nchw))
-    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-    _call(dev, lib().nqa_dists_group_stats, ptr(feat), r, k, hw, c, p, int(nchw), ptr(scratch), nbytes, ptr(s1), ptr(s2),
-          stream_ptr(dev))
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    else:
+        _need_cuda(scratch)
+        assert scratch.device == dev and scratch.dtype == torch.uint8 and scratch.numel() >= nbytes and scratch.is_contiguous()
+    _call(dev, lib().nqa_dists_group_stats, ptr(feat), r, k, hw, c, p, int(nchw), ptr(scratch), scratch.numel(), ptr(s1),
+          ptr(s2), stream_ptr(dev))
     return s1, s2
+
+
+def dists_group_sums(feat: torch.Tensor, r: int, k: int, prec, nchw: bool = False, sums: torch.Tensor | None = None):
+    """The five sums behind dists_group_stats, float64 (r*k, C, 5) = sum x, sum y, sum x^2, sum y^2, sum xy with x the
+    pair's reference (include/nqa.h, nqa_dists_group_sums): the same launch, its partials folded.  feat, nchw: as
+    dists_group_stats'; sums: as conv_pool_stats'."""
+    p = prec_id(prec)
+    dev = _need_cuda(feat)
+    r, k = int(r), int(k)
+    c, hw = _group_maps("dists_group_sums", feat, r, k, p, nchw)
+    sums = _out_or_empty(sums, (r * k, c, 5), torch.float64, dev)
+    nbytes = lib().nqa_dists_group_stats_bytes(r, k, hw, c, p, int(nchw))
+    ws = torch.full((max(nbytes, 256),), 0xFF, dtype=torch.uint8, device=dev)  # (a block that never ran leaves NaN sums)
+    _call(dev, lib().nqa_dists_group_sums, ptr(feat), r, k, hw, c, p, int(nchw), ptr(ws), nbytes, ptr(sums), stream_ptr(dev))
+    return sums
+
+
+def dists_group_stats_grid(r: int, k: int, hw: int, c: int, prec, nchw: bool = False) -> tuple:
+    """(pixels per block, blocks per map, pixels a block takes side by side, the largest item count of a thread) of the
+    group statistics launch for these arguments, from the launcher's own planning functions (no device is touched)."""
+    g = (C.c_int * 4)()
+    check(lib().nqa_dists_group_stats_grid(int(r), int(k), int(hw), int(c), prec_id(prec), int(nchw), g))
+    return tuple(g)
 
 
 def _feats_args(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor]):
@@ -439,17 +473,23 @@ def _feats_args(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor]):
     return dev, f0, f1, b, cs, hs, wsz, p0, p1
 
 
-def dists_stats_nchw(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor], keep_scratch: bool = False):
+def dists_stats_nchw(feats0: Sequence[torch.Tensor], feats1: Sequence[torch.Tensor], keep_scratch: bool = False,
+                     s1: torch.Tensor | None = None, s2: torch.Tensor | None = None, scratch: torch.Tensor | None = None):
     """(S1, S2) from two lists of six float32 NCHW feature maps (forward_from_feats).
 
     keep_scratch=True returns (S1, S2, scratch): the forward's per-block fp64 sums, which dists_stats_nchw_backward
-    reads (pass it unchanged, with the same maps)."""
+    reads (pass it unchanged, with the same maps).  s1, s2: as conv_pool_stats' outputs; scratch: a uint8 tensor of at
+    least nqa_stats_scratch_bytes to use instead of a new one."""
     dev, f0, f1, b, cs, hs, wsz, p0, p1 = _feats_args(feats0, feats1)
     ctot = sum(f.shape[1] for f in f0)
-    s1 = torch.empty((b, ctot), dtype=torch.float32, device=dev)
-    s2 = torch.empty((b, ctot), dtype=torch.float32, device=dev)
+    s1 = _out_or_empty(s1, (b, ctot), torch.float32, dev)
+    s2 = _out_or_empty(s2, (b, ctot), torch.float32, dev)
     nbytes = lib().nqa_stats_scratch_bytes(b, cs, hs, wsz)
-    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    else:
+        _need_cuda(scratch)
+        assert scratch.device == dev and scratch.dtype == torch.uint8 and scratch.numel() >= nbytes and scratch.is_contiguous()
     _call(dev, lib().nqa_dists_stats_nchw, p0, p1, b, cs, hs, wsz, ptr(scratch), scratch.numel(), ptr(s1), ptr(s2),
                                      stream_ptr(dev))
     if keep_scratch:

@@ -1,5 +1,5 @@
-"""CPU-side checks of the group entry points (include/nqa.h: nqa_dists_forward_group, nqa_dists_group_stats and their
-two size queries): declared in the header, exported by the library, bound by _lib.py; every refusal happens on the host
+"""CPU-side checks of the group entry points (include/nqa.h: nqa_dists_forward_group, nqa_dists_group_stats, their two
+size queries, and the tests' and tools' nqa_dists_group_sums / nqa_dists_group_stats_grid): declared in the header, exported by the library, bound by _lib.py; every refusal happens on the host
 -- an error code and a message naming the function, never a launch (the pointers below are fakes that nothing may
 dereference, and no device is touched); the workspace covers R + R * K images and the partial sums of R * K pairs."""
 import os
@@ -8,7 +8,8 @@ import re
 import pytest
 import torch
 
-NEW = ("nqa_dists_group_workspace_bytes", "nqa_dists_forward_group", "nqa_dists_group_stats_bytes", "nqa_dists_group_stats")
+NEW = ("nqa_dists_group_workspace_bytes", "nqa_dists_forward_group", "nqa_dists_group_stats_bytes", "nqa_dists_group_stats",
+       "nqa_dists_group_sums", "nqa_dists_group_stats_grid")
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "nqa.h")
 PREC = {"f32": 0, "bf16": 1, "f16": 2, "f32s": 3, "f32m": 4, "f32m2": 5, "f32m4": 6, "f16w": 7}
 FAKE = 0x10000  # fake device pointers start here
@@ -36,6 +37,9 @@ def test_exports_are_declared_bound_and_present(lib):
     for k in ("group_stats_nhwc_kernel", "group_stats_nchw_kernel"):
         assert k in build.NO_SCRATCH
     assert callable(ops.dists_forward_group) and callable(ops.dists_group_stats)
+    assert callable(ops.dists_group_sums) and callable(ops.dists_group_stats_grid)
+    doc = text.split("int nqa_dists_group_sums(")[0][-1500:]
+    assert "for tests and tools" in doc and "sum x, sum y, sum x^2, sum y^2, sum xy" in doc
     assert callable(DISTS.forward_group) and callable(video.score_videos)
 
 
@@ -105,6 +109,70 @@ def _stats(lib, R=2, K=3, HW=35, C=64, prec=0, nchw=0, feat=FAKE, scratch=2 * FA
     return lib.nqa_dists_group_stats(feat, R, K, HW, C, prec, nchw, scratch, nbytes, s1, s2, None)
 
 
+def _sums(lib, R=2, K=3, HW=35, C=64, prec=0, nchw=0, feat=FAKE, scratch=2 * FAKE, nbytes=None, sums=3 * FAKE):
+    if nbytes is None:
+        nbytes = 1 << 30
+    return lib.nqa_dists_group_sums(feat, R, K, HW, C, prec, nchw, scratch, nbytes, sums, None)
+
+
+def test_group_sums_refuses_what_group_stats_refuses(lib):
+    """Every refusal of nqa_dists_group_stats under the name dists_group_sums, and a null sums."""
+    for kw in ({"feat": None}, {"scratch": None}, {"sums": None}):
+        assert _sums(lib, **kw) == E_ARG, kw
+        assert b"dists_group_sums: null pointer" in lib.nqa_last_error()
+    for kw in ({"R": 0}, {"K": 0}, {"R": -2}, {"K": -1}, {"HW": 0}, {"HW": -7}, {"C": 0}, {"C": -64}):
+        assert _sums(lib, **kw) == E_ARG, kw
+        assert b"dists_group_sums: non-positive size" in lib.nqa_last_error()
+    assert _sums(lib, R=65536, K=1) == E_ARG and b"dists_group_sums: R*K = 65536 pairs" in lib.nqa_last_error()
+    for prec in (4, 5, 6, 7):
+        assert _sums(lib, prec=prec) == E_ARG and b"dists_group_sums: takes no mixed mode" in lib.nqa_last_error()
+    for prec in (8, -1):
+        assert _sums(lib, prec=prec) == E_ARG and b"dists_group_sums: unknown prec" in lib.nqa_last_error()
+    for C, prec, nchw, hw in ((64, 0, 0, 1 << 23), (512, 3, 0, 1 << 20), (512, 2, 0, 1 << 21), (3, 2, 1, (1 << 29) // 3 + 1)):
+        assert _sums(lib, HW=hw, C=C, prec=prec, nchw=nchw, nbytes=1) == E_ARG, (C, prec, nchw)
+        assert b"dists_group_sums: map too large" in lib.nqa_last_error()
+        assert _sums(lib, HW=hw - 1, C=C, prec=prec, nchw=nchw, nbytes=1) == E_WORKSPACE, (C, prec, nchw)
+    for C, prec in ((3, 0), (6, 0), (12, 0), (4, 2), (24, 2), (96, 0), (2048, 0)):
+        assert _sums(lib, C=C, prec=prec) == E_SHAPE, (C, prec)
+        assert b"dists_group_sums: no NHWC kernel for C=%d" % C in lib.nqa_last_error()
+    for C, prec, nchw in ((64, 0, 0), (512, 2, 0), (128, 1, 0), (256, 3, 0), (3, 0, 1), (5, 2, 1)):
+        need = lib.nqa_dists_group_stats_bytes(2, 3, 35, C, prec, nchw)  # (the same scratch as nqa_dists_group_stats)
+        for short in (0, 1, 6 * C * 5 * 8 - 1):
+            assert _sums(lib, C=C, prec=prec, nchw=nchw, nbytes=short) == E_WORKSPACE, (C, prec, nchw, short)
+            assert b"dists_group_sums: scratch" in lib.nqa_last_error()
+        assert need >= 6 * C * 5 * 8
+
+
+def test_group_stats_grid_reports_the_plan_and_refuses_on_the_host(lib):
+    import ctypes
+    g = (ctypes.c_int * 4)()
+    assert lib.nqa_dists_group_stats_grid(2, 3, 35, 64, 0, 0, None) == E_ARG
+    assert b"dists_group_stats_grid: null pointer" in lib.nqa_last_error()
+    for args, code in (((0, 1, 35, 64, 0, 0), E_ARG), ((1, 0, 35, 64, 0, 0), E_ARG), ((65536, 1, 35, 64, 0, 0), E_ARG),
+                       ((1, 1, 0, 64, 0, 0), E_ARG), ((1, 1, 35, 0, 0, 1), E_ARG), ((1, 1, 35, 64, 4, 0), E_ARG),
+                       ((1, 1, 35, 64, 8, 0), E_ARG), ((1, 1, 35, 96, 0, 0), E_SHAPE), ((1, 1, 35, 4, 2, 0), E_SHAPE)):
+        assert lib.nqa_dists_group_stats_grid(*args, g) == code, args
+        assert b"dists_group_stats_grid: " in lib.nqa_last_error()
+        assert lib.nqa_dists_group_stats_bytes(*args) == 0, args
+    # the scratch holds exactly the plan's partials; a thread never holds more than 16 items, and the blocks cover the map
+    for prec in (0, 1, 2, 3):
+        for nchw in (0, 1):
+            for C in ((3, 64) if nchw else (64, 128, 256, 512)):
+                for R, K, HW in ((1, 1, 1), (2, 3, 35), (3, 2, 1551), (1, 2, 24589), (1, 1, 262144), (4, 1, 1 << 18), (1, 1, 1 << 20)):
+                    key = (prec, nchw, C, R, K, HW)
+                    assert lib.nqa_dists_group_stats_grid(R, K, HW, C, prec, nchw, g) == 0, key
+                    ppb, nblk, pl, items = tuple(g)
+                    assert pl == (256 if nchw else 256 // (C // (4 if prec in (0, 3) else 8))), key
+                    assert ppb % pl == 0 or (nchw and ppb == HW), key
+                    assert 1 <= items <= 16 and items == -(-min(ppb, HW) // pl), key
+                    assert (nblk - 1) * ppb < HW <= nblk * ppb, key
+                    need = lib.nqa_dists_group_stats_bytes(R, K, HW, C, prec, nchw)
+                    assert need == -(-(R * K * nblk * C * 5 * 8) // 256) * 256, key
+    from nerf_qa_amd import ops
+    assert ops.dists_group_stats_grid(2, 3, 35, 64, "f32") == (64, 1, 16, 3)
+    assert ops.dists_group_stats_grid(2, 3, 4097, 3, "f16", nchw=True) == (4096, 2, 256, 16)
+
+
 def test_group_stats_refuses_bad_arguments(lib):
     for kw in ({"feat": None}, {"scratch": None}, {"s1": None}, {"s2": None}):
         assert _stats(lib, **kw) == E_ARG, kw
@@ -148,6 +216,10 @@ def test_ops_and_module_refuse_on_the_host():
         ops.dists_forward_group(ref, ren, blob, "f32")
     with pytest.raises(_lib.NqaError):
         ops.dists_group_stats(torch.rand(8, 35, 64), 2, 3, "f32")
+    with pytest.raises(_lib.NqaError):
+        ops.dists_group_sums(torch.rand(8, 35, 64), 2, 3, "f32")
+    with pytest.raises(_lib.NqaError):
+        ops.dists_group_stats_grid(2, 3, 35, 96, "f32")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         model = DISTS(precision="f32s")
