@@ -406,6 +406,51 @@ size_t nqa_adists_chain_bytes(int B, int H, int W);
 int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
                      void *workspace, size_t workspace_bytes, float *const *ps_prod, float *d, float *map, void *stream);
 
+/* ---- A-DISTS with a window size other than 21 (ADISTS(window_size=n), ADISTS.py:36,66-69) ----
+ * Every A-DISTS entry point above whose result depends on the window has a form with an explicit `int window` behind
+ * `W`; there is no hidden state.  The old names are the window-21 calls of these.  window: 3 .. 63, odd or even; the
+ * taps are those of the reference's gaussian(window, window / 3) -- float32 of exp, a float32-rounded sum, float32
+ * quotients, centre window / 2, so an even window is not symmetric -- built on the host and handed to the kernels as a
+ * table.  A stage whose tap is at least window x window gives (h-window+1) x (w-window+1) maps of valid windows, a
+ * smaller one the global branch's 1 x 1, unchanged.
+ * Dispatch of the window pass: window == 21 runs the three specialised kernels exactly as the old names do; every other
+ * window runs the generic kernels (nqa_window_n.h: ring of horizontal sums in LDS, one wave per block), NHWC taps with C
+ * a multiple of 64 in float / f16 / bf16 storage, planes for C == 3, pair and group forms.  nqa_set_conv_variant + 2048
+ * makes window 21 run the generic kernels too (tests and tools compare the two with it).
+ *   strip   of the generic kernels: 0 the launcher's own height, 1 <= strip <= H-window+1 that many output rows per
+ *           block (more than 64 are flushed in groups of 64), for planes as well.
+ * The upper end is the ring's: 1280 * window bytes of LDS per wave, two waves per 160-KiB CU.
+ * Refusals are those of the old names, plus NQA_E_ARG "window <n> outside [3, 63]"; the functions that return a size
+ * return 0 and set the same message.  The front part (nqa_adists_front) does not depend on the window. */
+size_t nqa_adists_workspace_bytes_n(int B, int H, int W, int window, int prec);
+int nqa_adists_forward_n(const float *x_nchw, const float *y_nchw, int B, int H, int W, int window, const void *packed_w,
+                         int prec, void *workspace, size_t workspace_bytes, float *d, void *stream);
+int nqa_adists_forward_map_n(const float *x_nchw, const float *y_nchw, int B, int H, int W, int window,
+                             const void *packed_w, int prec, void *workspace, size_t workspace_bytes, float *d,
+                             float *map, void *stream);
+int nqa_adists_dists_forward_n(const float *x_nchw, const float *y_nchw, int B, int H, int W, int window,
+                               const void *packed_w, int prec, void *workspace, size_t workspace_bytes, float *d,
+                               float *s1, float *s2, float *map, void *stream);
+size_t nqa_adists_group_workspace_bytes_n(int R, int K, int H, int W, int window, int prec);
+int nqa_adists_forward_group_n(const float *ref, const float *renders, int R, int K, int H, int W, int window,
+                               const void *packed_w, int prec, void *workspace, size_t workspace_bytes, float *d,
+                               float *s1, float *s2, void *stream);
+int nqa_adists_window_stage_n(const void *fx, const void *fy, int B, int H, int W, int window, int C, int prec,
+                              const float *q, const float *wgt, int strip, float *gamma, float *tw, float *sw,
+                              void *stream);
+int nqa_adists_window_stage_group_n(const void *fx, const void *fy, int R, int K, int H, int W, int window, int C,
+                                    int prec, const float *q, const float *wgt, int strip, float *gamma, float *tw,
+                                    float *sw, void *stream);
+int nqa_adists_chain_dims_n(int H, int W, int window, int *mh, int *mw);
+size_t nqa_adists_chain_bytes_n(int B, int H, int W, int window);
+int nqa_adists_chain_n(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
+                       int window, void *workspace, size_t workspace_bytes, float *const *ps_prod, float *d, float *map,
+                       void *stream);
+size_t nqa_adists_chain_group_bytes_n(int R, int K, int H, int W, int window);
+int nqa_adists_chain_group_n(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K,
+                             int H, int W, int window, void *workspace, size_t workspace_bytes, float *const *ps_prod,
+                             float *d, void *stream);
+
 /* The FRONT part of nqa_adists_forward on its own, for tests and tools: from the two images and the five tapped maps to
  * the per-channel scalars q and the channel weights wgt that the window pass and the global branch read.  It runs what
  * nqa_adists_forward runs for them, through the same launch functions, on the same grids, in the same order: the
@@ -497,7 +542,8 @@ int nqa_conv_pool_stats(const void *in, int B, int H, int W, int layer, const vo
  * pool + statistics pass over the tap it wrote) instead of conv + L2-pool + statistics in one kernel (nqa_conv_pool.hip);
  * adding 128 does the same for stage 1 (conv1_regw_kernel + pool_stats_kernel instead of nqa_conv1_pool.hip's kernel);
  * adding 8 selects the first form of the A-DISTS window pass (every wave loads its own taps instead of sharing them
- * through LDS).  Bits 8-9 choose the implicit GEMM's grid on maps whose last 32-wide tile column is at most half full
+ * through LDS); adding 2048 runs a 21-tap A-DISTS window on the generic window kernels (nqa_window_n.h) instead of the
+ * specialised ones.  Bits 8-9 choose the implicit GEMM's grid on maps whose last 32-wide tile column is at most half full
  * (1 <= W % 32 <= 16): by default such a layer takes ONE launch of 32-wide tiles plus 16-wide tiles down the right edge
  * (conv3x3_igemm_mixed_kernel) wherever that needs fewer rounds of blocks over the chip than the plain grid of 32-wide
  * tiles; adding 256 keeps the plain grid everywhere (A/B runs), adding 512 takes the mixed grid on every such map

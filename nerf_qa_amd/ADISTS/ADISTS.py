@@ -76,9 +76,8 @@ class ADISTS(torch.nn.Module):
         # forward, the head and the head's backward do not depend on it
         self.grad_precision = resolve_grad_precision(grad_precision)
         self.loss_head = _check_loss_head(loss_head or os.environ.get("NQA_ADISTS_LOSS_HEAD", DEFAULT_LOSS_HEAD))
-        if window_size != 21:
-            raise NotImplementedError("the HIP windowed-statistics kernel is built for the 21x21 window "
-                                      "the reference always uses")
+        # 21 (the reference's default) runs the specialised window kernels, every other size in 3..63 the generic ones
+        window_size = ops.check_window(window_size, "window_size")
         convs, self.vgg_source = load_vgg16_convs(vgg16_path)
         self.stage1, self.stage2, self.stage3, self.stage4, self.stage5 = _build_stages(convs)
         for param in self.parameters():
@@ -148,9 +147,14 @@ class ADISTS(torch.nn.Module):
         d.pop("_packed_key", None)
         d["_packed"], d["_ws"], d["_side"] = {}, ops.Workspace(), {}
 
+    def _window(self) -> int:
+        """window_size as the kernels take it (also of a module unpickled with another size); ValueError outside 3..63."""
+        return ops.check_window(self.window_size, "window_size")
+
     def _score(self, x, y, prec):
         """D (B,) of a batch (see _batched)."""
-        return self._batched(x, y, prec, lambda a, b, packed: ops.adists_forward(a, b, packed, prec, self._ws))
+        n = self._window()
+        return self._batched(x, y, prec, lambda a, b, packed: ops.adists_forward(a, b, packed, prec, self._ws, window=n))
 
     def _batched(self, x, y, prec, call):
         """call(x, y, packed) -> a tensor or a tuple of tensors with one row per pair (_score: D; pair.score_pair: D, S1,
@@ -191,7 +195,8 @@ class ADISTS(torch.nn.Module):
         autograd.adists_backward_y, HIP from end to end, without a device -> host read."""
         from .. import autograd
         from . import head
-        if self.loss_head != "torch" and y.requires_grad and not x.requires_grad:
+        # (the one-sided HIP backward is built on 21-tap kernels: any other window takes the torch head on every side)
+        if self.loss_head != "torch" and y.requires_grad and not x.requires_grad and self._window() == ops.WINDOW:
             return autograd.AdistsLossY.apply(x, y, self)
         tx = autograd.PyramidTaps.apply(x, self) if x.requires_grad else self._taps_nograd(x)
         ty = autograd.PyramidTaps.apply(y, self) if y.requires_grad else self._taps_nograd(y)
@@ -219,7 +224,8 @@ class ADISTS(torch.nn.Module):
         if as_map:
             # (:163,188-189,193) the reference's (B,H,W) + (B,1,H,W) addition broadcasts to (B,B,H,W)
             # with out[i, j] = map[i]; reproduced as is (callers use B = 1, nerf_nr_qa_prep_4.py:70)
-            _, m = ops.adists_forward(x, y, self._packed_weights(x.device, prec), prec, self._ws, with_map=True)
+            _, m = ops.adists_forward(x, y, self._packed_weights(x.device, prec), prec, self._ws, with_map=True,
+                                      window=self._window())
             b = m.shape[0]
             return m.unsqueeze(1).expand(b, b, *m.shape[1:]).contiguous()
         d = self._score(x, y, prec)
@@ -244,10 +250,13 @@ class ADISTS(torch.nn.Module):
         (the value is the staged head's, not the fused kernel's); the conv chain behind them in the module's
         grad_precision ("f32s", or "f16": half gradient maps, the same value).  The target is used whole: NqaError if its batch does not
         fit NQA_MAX_WORKSPACE_GB (pass target[i:j] slices), and for tensors off the GPU; ValueError for a target of
-        another module, one prepared before the VGG weights changed, and a shape that does not fit."""
+        another module, one prepared before the VGG weights changed, and a shape that does not fit.  With a window_size
+        other than 21 the value works as described, but a gradient does not (the head's HIP backward is 21-tap):
+        ValueError where y requires grad -- use adists(x, y), whose torch head differentiates any window."""
         from .. import autograd, target as tgt
         tgt.check(self, target, y, "ADISTS")
         if torch.is_grad_enabled() and y.requires_grad:
+            autograd.check_target_window(self)
             return autograd.AdistsTargetLoss.apply(y, target, self, bool(as_loss))
         d, _ = autograd.adists_target_d(self, target, y, keep=False)
         return 1 - d.mean() if as_loss else 1 - d
@@ -279,7 +288,8 @@ class ADISTS(torch.nn.Module):
         r, k, h, w = self._group_checks(ref, renders)
         prec = self.precision_for(h, w)
         with torch.no_grad():
-            d = ops.adists_forward_group(ref, renders, self._packed_weights(ref.device, prec), prec, self._ws)
+            d = ops.adists_forward_group(ref, renders, self._packed_weights(ref.device, prec), prec, self._ws,
+                                         window=self._window())
         return 1 - d.mean() if as_loss else (1 - d).reshape(r, k)
 
 

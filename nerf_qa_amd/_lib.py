@@ -87,6 +87,22 @@ _SIGNATURES = {
     "nqa_adists_chain_bytes": (_sz, [_i, _i, _i]),
     "nqa_adists_chain": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _vp, _sz, C.POINTER(_vp), _vp,
                               _vp, _vp]),
+    # the same entry points with an explicit window size behind W (3..63; the old names are their window-21 calls)
+    "nqa_adists_workspace_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_adists_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp]),
+    "nqa_adists_forward_map_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_adists_dists_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "nqa_adists_group_workspace_bytes_n": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "nqa_adists_forward_group_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "nqa_adists_window_stage_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "nqa_adists_window_stage_group_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "nqa_adists_chain_dims_n": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "nqa_adists_chain_bytes_n": (_sz, [_i, _i, _i, _i]),
+    "nqa_adists_chain_n": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp),
+                                _vp, _vp, _vp]),
+    "nqa_adists_chain_group_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_adists_chain_group_n": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _sz,
+                                      C.POINTER(_vp), _vp, _vp]),
     "nqa_adists_front_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), _i]),
     "nqa_adists_front_grid": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i)]),
     "nqa_adists_front": (_i, [_vp, _vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _sz, _vp, _vp, _vp]),

@@ -360,23 +360,24 @@ def adists_y_forward(module, x, tx, y, keep=True, kept=None):
     DISTS); no pyramid launch runs here then, and `keep` is not looked at."""
     b, _, h, w = x.shape
     prec, dev, ws = "f32s", x.device, module._ws
+    n = module._window()  # (a value for any window; adists_y_backward follows only a 21-tap forward)
     pyramid = _pyramid_forward(module, y, keep) if kept is None else KeptPyramid(*kept)
     ty = pyramid.taps
     # ---- what the head takes from x alone, and the per-channel scalars of both: the forward's own kernels ----
     q = torch.empty((8, b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
     wgt = torch.empty((b, ops.TOTAL_CHNS), dtype=torch.float32, device=dev)
     ops.adists_front_into(x, y, [torch.cat([a, c]) for a, c in zip(tx, ty)], prec, q, wgt, ws)
-    dims, _ = ops.adists_chain_dims(h, w)
+    dims, _ = ops.adists_chain_dims(h, w, n)
     maps = [torch.empty((4, b) + d, dtype=torch.float32, device=dev) for d in dims]  # gamma, tw, sw, ps_prod per stage
     off = 0
     for k, c in enumerate(ops.CHNS):
         fx, fy = (x, y) if k == 0 else (tx[k - 1], ty[k - 1])
         ops.adists_window_stage_into(fx, fy, q[:, :, off:off + c].contiguous(), wgt[:, off:off + c].contiguous(), prec, 0,
-                                     maps[k][0], maps[k][1], maps[k][2])
+                                     maps[k][0], maps[k][1], maps[k][2], n)
         off += c
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     ops.adists_chain_into([m[0] for m in maps], [m[1] for m in maps], [m[2] for m in maps], h, w, [m[3] for m in maps], d,
-                          None, ws)
+                          None, ws, n)
     return d, AdistsState(q, wgt, maps, pyramid)
 
 
@@ -457,6 +458,16 @@ class AdistsLossY(torch.autograd.Function):
         if not ctx.needs_input_grad[1]:
             return None, None, None
         return None, adists_backward_y(ctx.module, x, y, _loss_u(grad, x.shape[0], True)).to(y.dtype), None
+
+
+def check_target_window(module) -> None:
+    """ValueError for a gradient through forward_target with a window other than 21: the head's backward
+    (nqa_window_moments, nqa_adists_ts_backward) is built on 21-tap kernels."""
+    n = module._window()
+    if n != ops.WINDOW:
+        raise ValueError(f"forward_target differentiates through 21-tap HIP kernels only, and this module has "
+                         f"window_size={n}: for a gradient call adists(x, y) (as_loss=True), whose torch head "
+                         "differentiates any window; forward_target without a gradient works for every window")
 
 
 def adists_target_fits(target) -> None:

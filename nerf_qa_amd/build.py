@@ -33,7 +33,9 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_igemm_mixed_kernel", "conv3x3_reg
               "group_stats_nhwc_kernel", "group_stats_nchw_kernel",
               "adists_window_lds_group_kernel", "adists_window_planar_group_kernel",
               "adists_ts_coef_kernel", "adists_ts_dot_kernel", "adists_ts_fold_kernel", "adists_ts_apply_kernel",
-              "adists_ts_apply_nhwc_kernel", "adists_ts_global_kernel")
+              "adists_ts_apply_nhwc_kernel", "adists_ts_global_kernel",
+              "adists_window_n_lanes_kernel", "adists_window_n_lanes_group_kernel", "adists_window_n_planar_kernel",
+              "adists_window_n_planar_group_kernel")
 
 
 def parse_resource_remarks(text: str) -> dict:

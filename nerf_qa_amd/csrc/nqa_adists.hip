@@ -21,11 +21,13 @@
 
 namespace nqa {
 
-static constexpr int kWin = 21;
+static constexpr int kWin = 21;                  // the window of the three specialised kernels, and of the old entry points
+static constexpr int kWinMin = 3, kWinMax = 63;  // what the generic kernels take (nqa_window_n.h derives the upper end)
 static constexpr int kChainBlocks = 1024;  // most blocks per image of the chain's reduction kernels
 
 // tuning hook (nqa_set_conv_variant bit 3): the per-wave-loads form of the window pass, kept for A/B timing
 static bool adists_window_legacy() { return tuning().window_legacy; }
+static bool adists_window_generic() { return tuning().window_generic; }
 
 struct Gauss {
   float g[kWin];
@@ -714,6 +716,9 @@ __global__ __launch_bounds__(256) void adists_global_group_kernel(const float *_
   global_body<true>(q, B, ctot, coff, creal, wgt, gamma, tw, sw, K);
 }
 
+// The same pass for a run-time window size (3..63): ring in LDS, taps from a table.  Every window but 21 runs on these.
+#include "nqa_window_n.h"
+
 // ---------------------------------------------------------------------------------
 // Probability chain on the small maps (compute_prob, ADISTS.py:77-99) and the stage's D.
 struct ChainAcc {       // one per (stage, image); zeroed before the chain
@@ -1027,6 +1032,39 @@ static Gauss make_gauss() {
   return g;
 }
 
+// gaussian(n, n / 3) for every n the generic kernels take, by make_gauss's arithmetic: the centre is n / 2 (integer),
+// so an even window is not symmetric (ADISTS.py:102-104); sigma = n / 3 and 2 sigma^2 are Python's doubles.
+static const GaussN &gauss_n(int n) {
+  struct Table {
+    GaussN t[kWinMax + 1];
+    Table() {
+      memset(t, 0, sizeof(t));
+      for (int n = kWinMin; n <= kWinMax; ++n) {
+        const double sigma = (double)n / 3.0;
+        float v[kWinMax];
+        double sd = 0.0;
+        for (int i = 0; i < n; ++i) {
+          v[i] = (float)exp(-(double)((i - n / 2) * (i - n / 2)) / (2.0 * (sigma * sigma)));
+          sd += (double)v[i];
+        }
+        const float s = (float)sd;
+        for (int i = 0; i < n; ++i) t[n].g[i] = v[i] / s;
+      }
+    }
+  };
+  static const Table table;
+  return table.t[n];
+}
+
+// NQA_OK for a window the library takes, else the argument error naming the range under the caller's name.
+static int window_check(const char *who, int window) {
+  if (window < kWinMin || window > kWinMax) {
+    set_error("%s: window %d outside [%d, %d]", who, window, kWinMin, kWinMax);
+    return NQA_E_ARG;
+  }
+  return NQA_OK;
+}
+
 // Every host function below describes a call by three integers: X x-side images, B pairs, and K -- 0 for B independent
 // pairs (X = B, pair b reads x image b), > 0 for groups of K renders per reference (B = X * K, pair b reads x image
 // b / K).  What A-DISTS takes from x alone (entropy weights, gamma, the probability chain) is sized and launched by X,
@@ -1044,10 +1082,11 @@ struct APlan {
   int mh[NQA_NUM_TAPS], mw[NQA_NUM_TAPS];                  // map dims (1x1 for the global branch)
   bool windowed[NQA_NUM_TAPS];
   int ent_ppb[NQA_NUM_TAPS];
+  int win;  // the window size the maps are sized for
 };
 
 // Feature dims of the six taps of an H x W frame (k = 0 the image, k = 1 relu1_2 at full size, then halved, rounding up),
-// and the dims of a stage's gamma / TW / SW / ps_prod maps: valid 21 x 21 windows, or 1 x 1 from the global branch.
+// and the dims of a stage's gamma / TW / SW / ps_prod maps: valid win x win windows, or 1 x 1 from the global branch.
 static void tap_dims(int H, int W, int h[NQA_NUM_TAPS], int w[NQA_NUM_TAPS]) {
   h[0] = h[1] = H;
   w[0] = w[1] = W;
@@ -1056,12 +1095,12 @@ static void tap_dims(int H, int W, int h[NQA_NUM_TAPS], int w[NQA_NUM_TAPS]) {
     w[k] = (w[k - 1] + 1) / 2;
   }
 }
-static void map_dims(const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], int mh[NQA_NUM_TAPS], int mw[NQA_NUM_TAPS],
-                     bool windowed[NQA_NUM_TAPS]) {
+static void map_dims(const int h[NQA_NUM_TAPS], const int w[NQA_NUM_TAPS], int win, int mh[NQA_NUM_TAPS],
+                     int mw[NQA_NUM_TAPS], bool windowed[NQA_NUM_TAPS]) {
   for (int k = 0; k < NQA_NUM_TAPS; ++k) {
-    windowed[k] = h[k] >= kWin && w[k] >= kWin;
-    mh[k] = windowed[k] ? h[k] - (kWin - 1) : 1;
-    mw[k] = windowed[k] ? w[k] - (kWin - 1) : 1;
+    windowed[k] = h[k] >= win && w[k] >= win;
+    mh[k] = windowed[k] ? h[k] - (win - 1) : 1;
+    mw[k] = windowed[k] ? w[k] - (win - 1) : 1;
   }
 }
 
@@ -1118,7 +1157,7 @@ static size_t chain_part_bytes(int X, int B) {
 }
 
 // One NHWC batch of n = X + B images (the x images first), all five taps kept.
-static APlan make_plan(int X, int B, int K, int H, int W, int prec) {
+static APlan make_plan(int X, int B, int K, int H, int W, int prec, int win) {
   APlan p;
   memset(&p, 0, sizeof(p));
   const size_t esz = prec_elem_bytes(prec);
@@ -1144,7 +1183,8 @@ static APlan make_plan(int X, int B, int K, int H, int W, int prec) {
   p.ent = take((size_t)eoff * 8);
   p.hsum = K > 0 ? take((size_t)X * coff * 4) : p.q + (size_t)2 * B * coff * 4;
   p.wgt = take((size_t)X * coff * 4);
-  map_dims(p.h, p.w, p.mh, p.mw, p.windowed);
+  p.win = win;
+  map_dims(p.h, p.w, win, p.mh, p.mw, p.windowed);
   for (int k = 0; k < 6; ++k)
     for (int j = 0; j < 4; ++j)  // gamma and ps_prod per x image, tw and sw per pair
       p.maps[k][j] = take((size_t)(j == 0 || j == 3 ? X : B) * p.mh[k] * p.mw[k] * 4);
@@ -1279,13 +1319,97 @@ static const Gauss *checked_gauss(const char *who) {
   return &gauss;
 }
 
+// Strip height of the generic kernels: a strip pays n - 1 rows of vertical run-in, so it grows with the window (64 rows
+// per 16 taps, up to 256) while the grid still holds ~4096 blocks (a block is one wave: 16 per CU), else 64 rows.
+// strip_req in [1, Ho] replaces that choice (tests reach the multi-group strips at small shapes with it).
+static int window_n_strip(int n, int Ho, int nbx, int B, int strip_req) {
+  if (strip_req > 0) return strip_req;
+  int strip = 64 * cdiv(n, 16);
+  while (strip > 64 && (long)nbx * cdiv(Ho, strip) * B < 4096) strip -= 64;
+  return min(strip, Ho);
+}
+
+// The generic window pass (nqa_window_n.h) of one stage with a window of n, H and W at least n.  K as above.
+// The dynamic-LDS limit of a kernel is raised once per device, so to what the largest window needs (78.75 KiB).
+static constexpr int kWindowNMaxLds = kWinMax * 5 * 64 * (int)sizeof(float);
+template <typename P>
+static int launch_window_n_lanes(const void *fx, const void *fy, int B, int H, int W, int C, const float *q, int ctot,
+                                 int coff, const float *wgt, int n, float *gamma, float *tw, float *sw, hipStream_t st,
+                                 int strip_req, int K) {
+  const int Ho = H - (n - 1), Wo = W - (n - 1);
+  const typename P::T *px = reinterpret_cast<const typename P::T *>(fx), *py = reinterpret_cast<const typename P::T *>(fy);
+  if (C <= 0 || C % 64) {
+    set_error("adists_window_n: unsupported channel count %d", C);
+    return NQA_E_SHAPE;
+  }
+  const int strip = window_n_strip(n, Ho, Wo, B, strip_req);
+  const int lds = n * 5 * 64 * (int)sizeof(float);
+  dim3 grid(Wo, cdiv(Ho, strip), B);
+  if (grid.y > 65535u) {
+    set_error("adists_window_n: grid too large");
+    return NQA_E_SHAPE;
+  }
+  int rc;
+  if (K > 0) {
+    if ((rc = lds_limit<adists_window_n_lanes_group_kernel<P>>(kWindowNMaxLds, "adists_window_n_lanes_group"))) return rc;
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_window_n_lanes_group_kernel<P><<<grid, 64, lds, st>>>(px, py, H, W, C, q, B, ctot, coff, wgt, gauss_n(n), n,
+                                                                 strip, gamma, tw, sw, K);
+    return check_launch("adists_window_n_lanes_group");
+  }
+  if ((rc = lds_limit<adists_window_n_lanes_kernel<P>>(kWindowNMaxLds, "adists_window_n_lanes"))) return rc;
+  TimedLaunch t(NQA_K_ADISTS, st);
+  adists_window_n_lanes_kernel<P><<<grid, 64, lds, st>>>(px, py, H, W, C, q, B, ctot, coff, wgt, gauss_n(n), n, strip,
+                                                         gamma, tw, sw);
+  return check_launch("adists_window_n_lanes");
+}
+
+static int launch_window_n_planar(const float *x, const float *y, int B, int H, int W, const float *q, int ctot,
+                                  int coff, const float *wgt, int n, float *gamma, float *tw, float *sw, hipStream_t st,
+                                  int strip_req, int K) {
+  const int Ho = H - (n - 1), Wo = W - (n - 1);
+  const int nbx = cdiv(Wo, 64);
+  const int strip = window_n_strip(n, Ho, nbx, B, strip_req);
+  const int lds = n * 5 * 64 * (int)sizeof(float);
+  dim3 grid(nbx, cdiv(Ho, strip), B);
+  if (grid.y > 65535u) {
+    set_error("adists_window_n: grid too large");
+    return NQA_E_SHAPE;
+  }
+  int rc;
+  if (K > 0) {
+    if ((rc = lds_limit<adists_window_n_planar_group_kernel>(kWindowNMaxLds, "adists_window_n_planar_group"))) return rc;
+    TimedLaunch t(NQA_K_ADISTS, st);
+    adists_window_n_planar_group_kernel<<<grid, 64, lds, st>>>(x, y, H, W, q, B, ctot, coff, wgt, gauss_n(n), n, strip,
+                                                               gamma, tw, sw, K);
+    return check_launch("adists_window_n_planar_group");
+  }
+  if ((rc = lds_limit<adists_window_n_planar_kernel>(kWindowNMaxLds, "adists_window_n_planar"))) return rc;
+  TimedLaunch t(NQA_K_ADISTS, st);
+  adists_window_n_planar_kernel<<<grid, 64, lds, st>>>(x, y, H, W, q, B, ctot, coff, wgt, gauss_n(n), n, strip, gamma, tw,
+                                                       sw);
+  return check_launch("adists_window_n_planar");
+}
+
 // One stage of the heavy pass: the global branch for maps smaller than the window, the planar kernel for the image,
 // else the lanes pass in the taps' storage type.  fx holds the x-side maps, fy the B pairs' y maps.  The forward's
-// stage loop and the two single-stage entry points all dispatch here (`who` names the caller in a refusal).
-static int launch_window_stage(const char *who, const void *fx, const void *fy, int B, int K, int H, int W, int C,
-                               int prec, const float *q, int ctot, int coff, const float *wgt, float *gamma, float *tw,
-                               float *sw, hipStream_t st, int strip = 0) {
-  if (H < kWin || W < kWin) return launch_global(q, B, ctot, coff, C, wgt, gamma, tw, sw, st, K);
+// stage loop and the single-stage entry points all dispatch here (`who` names the caller in a refusal).  A window of
+// 21 runs the three specialised kernels unless the calling thread's tuning asks for the generic ones; every other
+// window (kWinMin..kWinMax, checked by the caller) runs the generic ones.
+static int launch_window_stage(const char *who, const void *fx, const void *fy, int B, int K, int H, int W, int win,
+                               int C, int prec, const float *q, int ctot, int coff, const float *wgt, float *gamma,
+                               float *tw, float *sw, hipStream_t st, int strip = 0) {
+  if (H < win || W < win) return launch_global(q, B, ctot, coff, C, wgt, gamma, tw, sw, st, K);
+  if (win != kWin || adists_window_generic()) {
+    if (C == 3)
+      return launch_window_n_planar(static_cast<const float *>(fx), static_cast<const float *>(fy), B, H, W, q, ctot,
+                                    coff, wgt, win, gamma, tw, sw, st, strip, K);
+    switch (storage_prec(prec)) {
+      case NQA_PREC_F32: return launch_window_n_lanes<PrecF32>(fx, fy, B, H, W, C, q, ctot, coff, wgt, win, gamma, tw, sw, st, strip, K);
+      case NQA_PREC_BF16: return launch_window_n_lanes<PrecBF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, win, gamma, tw, sw, st, strip, K);
+      default: return launch_window_n_lanes<PrecF16>(fx, fy, B, H, W, C, q, ctot, coff, wgt, win, gamma, tw, sw, st, strip, K);
+    }
+  }
   const Gauss *gp = checked_gauss(who);
   if (!gp) return NQA_E_LAUNCH;
   if (C == 3)
@@ -1304,9 +1428,14 @@ using namespace nqa;
 
 extern "C" {
 
-size_t nqa_adists_workspace_bytes(int B, int H, int W, int prec) {
+size_t nqa_adists_workspace_bytes_n(int B, int H, int W, int window, int prec) {
+  if (window_check("adists_workspace_bytes_n", window)) return 0;
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return make_plan(B, B, 0, H, W, prec).total;
+  return make_plan(B, B, 0, H, W, prec, window).total;
+}
+
+size_t nqa_adists_workspace_bytes(int B, int H, int W, int prec) {
+  return nqa_adists_workspace_bytes_n(B, H, W, kWin, prec);
 }
 
 }  // extern "C"
@@ -1471,8 +1600,8 @@ static int adists_tail(const char *who, const float *x, const float *y, int X, i
     const void *fx = k == 0 ? static_cast<const void *>(x) : taps[k - 1];
     const void *fy = k == 0 ? static_cast<const void *>(y)
                             : static_cast<const char *>(taps[k - 1]) + (size_t)X * p.h[k] * p.w[k] * p.c[k] * esz;
-    if ((rc = launch_window_stage(who, fx, fy, B, K, p.h[k], p.w[k], p.c[k], prec, q, ctot, p.sd.coff[k], wgt, gamma, tw,
-                                  sw, st)))
+    if ((rc = launch_window_stage(who, fx, fy, B, K, p.h[k], p.w[k], p.win, p.c[k], prec, q, ctot, p.sd.coff[k], wgt,
+                                  gamma, tw, sw, st)))
       return rc;
   }
   return launch_chain(cm, X, B, K, H, W, reinterpret_cast<ChainAcc *>(base + p.acc_x),
@@ -1480,13 +1609,14 @@ static int adists_tail(const char *who, const float *x, const float *y, int X, i
                       reinterpret_cast<float *>(base + p.ones), d_out, map_out, st);
 }
 
-static int adists_run(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
-                      size_t ws_bytes, float *d_out, float *map_out, void *stream, float *s1_out = nullptr,
+static int adists_run(const float *x, const float *y, int B, int H, int W, int win, const void *packed, int prec,
+                      void *ws, size_t ws_bytes, float *d_out, float *map_out, void *stream, float *s1_out = nullptr,
                       float *s2_out = nullptr) {
   if (!x || !y || !packed || !ws || !d_out) {
     set_error("adists_forward: null pointer");
     return NQA_E_ARG;
   }
+  if (int rc = window_check("adists_forward", win)) return rc;
   if (B <= 0 || H <= 0 || W <= 0 || !prec_valid(prec)) {
     set_error("adists_forward: bad size or prec (B=%d H=%d W=%d prec=%d)", B, H, W, prec);
     return NQA_E_ARG;
@@ -1495,7 +1625,7 @@ static int adists_run(const float *x, const float *y, int B, int H, int W, const
     set_error("adists_forward: image too large for 32-bit in-image byte offsets");
     return NQA_E_ARG;
   }
-  const APlan p = make_plan(B, B, 0, H, W, prec);
+  const APlan p = make_plan(B, B, 0, H, W, prec, win);
   if (ws_bytes < p.total) {
     set_error("adists_forward: workspace %zu < %zu bytes", ws_bytes, p.total);
     return NQA_E_WORKSPACE;
@@ -1558,7 +1688,7 @@ static int chain_frame_check(const char *who, int B, int H, int W) {
 // nqa_adists_chain (group false: X pairs, K ignored) and nqa_adists_chain_group (X references of K renders) behind
 // their argument lists: the refusals under the caller's name, then launch_chain on the caller's maps.
 static int chain_entry(const char *who, bool group, const float *const *gamma, const float *const *tw,
-                       const float *const *sw, int X, int K, int H, int W, void *ws, size_t ws_bytes,
+                       const float *const *sw, int X, int K, int H, int W, int win, void *ws, size_t ws_bytes,
                        float *const *ps_prod, float *d, float *map, void *stream) {
   if (!gamma || !tw || !sw || !ws || !ps_prod || !d) {
     set_error("%s: null pointer", who);
@@ -1574,6 +1704,7 @@ static int chain_entry(const char *who, bool group, const float *const *gamma, c
     return NQA_E_ARG;
   }
   if (int rc = chain_frame_check(who, X, H, W)) return rc;
+  if (int rc = window_check(who, win)) return rc;
   if (!group) K = 0;
   const int B = group ? X * K : X;
   const ChainPlan c = chain_plan(X, B, K);
@@ -1584,7 +1715,7 @@ static int chain_entry(const char *who, bool group, const float *const *gamma, c
   ChainMaps cm;
   int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
   tap_dims(H, W, h, w);
-  map_dims(h, w, cm.mh, cm.mw, cm.windowed);
+  map_dims(h, w, win, cm.mh, cm.mw, cm.windowed);
   for (int k = 0; k < NQA_NUM_TAPS; ++k) {
     cm.gamma[k] = gamma[k];
     cm.tw[k] = tw[k];
@@ -1599,29 +1730,41 @@ static int chain_entry(const char *who, bool group, const float *const *gamma, c
 
 extern "C" {
 
-int nqa_adists_chain_dims(int H, int W, int *mh, int *mw) {
+int nqa_adists_chain_dims_n(int H, int W, int window, int *mh, int *mw) {
   if (!mh || !mw) {
     set_error("adists_chain_dims: null pointer");
     return NQA_E_ARG;
   }
   if (int rc = chain_frame_check("adists_chain_dims", 1, H, W)) return rc;
+  if (int rc = window_check("adists_chain_dims", window)) return rc;
   int h[NQA_NUM_TAPS], w[NQA_NUM_TAPS];
   bool windowed[NQA_NUM_TAPS];
   tap_dims(H, W, h, w);
-  map_dims(h, w, mh, mw, windowed);
+  map_dims(h, w, window, mh, mw, windowed);
   int nwin = 0;
   for (int k = 0; k < NQA_NUM_TAPS; ++k) nwin += windowed[k] ? 1 : 0;
   return nwin;
 }
 
-size_t nqa_adists_chain_bytes(int B, int H, int W) {
+int nqa_adists_chain_dims(int H, int W, int *mh, int *mw) { return nqa_adists_chain_dims_n(H, W, kWin, mh, mw); }
+
+size_t nqa_adists_chain_bytes_n(int B, int H, int W, int window) {
+  if (window_check("adists_chain_bytes_n", window)) return 0;
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   return chain_plan(B, B, 0).total;
 }
 
+size_t nqa_adists_chain_bytes(int B, int H, int W) { return nqa_adists_chain_bytes_n(B, H, W, kWin); }
+
+int nqa_adists_chain_n(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
+                       int window, void *ws, size_t ws_bytes, float *const *ps_prod, float *d, float *map,
+                       void *stream) {
+  return chain_entry("adists_chain", false, gamma, tw, sw, B, 0, H, W, window, ws, ws_bytes, ps_prod, d, map, stream);
+}
+
 int nqa_adists_chain(const float *const *gamma, const float *const *tw, const float *const *sw, int B, int H, int W,
                      void *ws, size_t ws_bytes, float *const *ps_prod, float *d, float *map, void *stream) {
-  return chain_entry("adists_chain", false, gamma, tw, sw, B, 0, H, W, ws, ws_bytes, ps_prod, d, map, stream);
+  return nqa_adists_chain_n(gamma, tw, sw, B, H, W, kWin, ws, ws_bytes, ps_prod, d, map, stream);
 }
 
 }  // extern "C"
@@ -1749,14 +1892,15 @@ int nqa_adists_front(const float *x, const float *y, const void *const *taps, in
 }  // extern "C"
 
 // One stage of the heavy pass on its own, dispatched as the loop above dispatches it (ctot = C, coff = 0).
-static int window_stage_check(const char *who, int B, int H, int W, int C, int prec, int strip) {
+static int window_stage_check(const char *who, int B, int H, int W, int win, int C, int prec, int strip) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || !prec_valid(prec)) {
     set_error("%s: bad size or prec (B=%d H=%d W=%d C=%d prec=%d)", who, B, H, W, C, prec);
     return NQA_E_ARG;
   }
-  const bool windowed = H >= kWin && W >= kWin;
-  if (strip < 0 || (windowed && strip > H - (kWin - 1))) {
-    set_error("%s: strip %d outside [0, %d]", who, strip, windowed ? H - (kWin - 1) : 0);
+  if (int rc = window_check(who, win)) return rc;
+  const bool windowed = H >= win && W >= win;
+  if (strip < 0 || (windowed && strip > H - (win - 1))) {
+    set_error("%s: strip %d outside [0, %d]", who, strip, windowed ? H - (win - 1) : 0);
     return NQA_E_ARG;
   }
   if (C != 3 && C != 64 && C != 128 && C != 256 && C != 512) {
@@ -1777,46 +1921,68 @@ int nqa_adists_window_grid(int B, int H, int W, int C, int prec, int strip, int 
     set_error("adists_window_grid: null pointer");
     return NQA_E_ARG;
   }
-  if (int rc = window_stage_check("adists_window_grid", B, H, W, C, prec, strip)) return rc;
+  if (int rc = window_stage_check("adists_window_grid", B, H, W, kWin, C, prec, strip)) return rc;
   grid[0] = grid[1] = grid[2] = 0;
-  if (H >= kWin && W >= kWin && C != 3 && window_uses_lds(prec_elem_bytes(prec)))
+  if (H >= kWin && W >= kWin && C != 3 && !adists_window_generic() && window_uses_lds(prec_elem_bytes(prec)))
     window_lds_grid(H - (kWin - 1), W - (kWin - 1), B, strip, grid[0], grid[1], grid[2]);
   return NQA_OK;
 }
 
-int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W, int C, int prec, const float *q,
-                            const float *wgt, int strip, float *gamma, float *tw, float *sw, void *stream) {
+int nqa_adists_window_stage_n(const void *fx, const void *fy, int B, int H, int W, int window, int C, int prec,
+                              const float *q, const float *wgt, int strip, float *gamma, float *tw, float *sw,
+                              void *stream) {
   if (!fx || !fy || !q || !wgt || !gamma || !tw || !sw) {
     set_error("adists_window_stage: null pointer");
     return NQA_E_ARG;
   }
-  if (int rc = window_stage_check("adists_window_stage", B, H, W, C, prec, strip)) return rc;
-  return launch_window_stage("adists_window_stage", fx, fy, B, 0, H, W, C, prec, q, C, 0, wgt, gamma, tw, sw,
+  if (int rc = window_stage_check("adists_window_stage", B, H, W, window, C, prec, strip)) return rc;
+  return launch_window_stage("adists_window_stage", fx, fy, B, 0, H, W, window, C, prec, q, C, 0, wgt, gamma, tw, sw,
                              static_cast<hipStream_t>(stream), strip);
+}
+
+int nqa_adists_window_stage(const void *fx, const void *fy, int B, int H, int W, int C, int prec, const float *q,
+                            const float *wgt, int strip, float *gamma, float *tw, float *sw, void *stream) {
+  return nqa_adists_window_stage_n(fx, fy, B, H, W, kWin, C, prec, q, wgt, strip, gamma, tw, sw, stream);
+}
+
+int nqa_adists_forward_n(const float *x, const float *y, int B, int H, int W, int window, const void *packed, int prec,
+                         void *ws, size_t ws_bytes, float *d_out, void *stream) {
+  return adists_run(x, y, B, H, W, window, packed, prec, ws, ws_bytes, d_out, nullptr, stream);
 }
 
 int nqa_adists_forward(const float *x, const float *y, int B, int H, int W, const void *packed, int prec, void *ws,
                        size_t ws_bytes, float *d_out, void *stream) {
-  return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, nullptr, stream);
+  return nqa_adists_forward_n(x, y, B, H, W, kWin, packed, prec, ws, ws_bytes, d_out, stream);
 }
 
-int nqa_adists_forward_map(const float *x, const float *y, int B, int H, int W, const void *packed, int prec,
-                           void *ws, size_t ws_bytes, float *d_out, float *map_out, void *stream) {
+int nqa_adists_forward_map_n(const float *x, const float *y, int B, int H, int W, int window, const void *packed,
+                             int prec, void *ws, size_t ws_bytes, float *d_out, float *map_out, void *stream) {
   if (!map_out) {
     set_error("adists_forward_map: null map pointer");
     return NQA_E_ARG;
   }
-  return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, map_out, stream);
+  return adists_run(x, y, B, H, W, window, packed, prec, ws, ws_bytes, d_out, map_out, stream);
+}
+
+int nqa_adists_forward_map(const float *x, const float *y, int B, int H, int W, const void *packed, int prec,
+                           void *ws, size_t ws_bytes, float *d_out, float *map_out, void *stream) {
+  return nqa_adists_forward_map_n(x, y, B, H, W, kWin, packed, prec, ws, ws_bytes, d_out, map_out, stream);
+}
+
+int nqa_adists_dists_forward_n(const float *x, const float *y, int B, int H, int W, int window, const void *packed,
+                               int prec, void *ws, size_t ws_bytes, float *d_out, float *s1, float *s2, float *map_out,
+                               void *stream) {
+  if (!s1 || !s2) {
+    set_error("adists_dists_forward: null similarity pointer");
+    return NQA_E_ARG;
+  }
+  return adists_run(x, y, B, H, W, window, packed, prec, ws, ws_bytes, d_out, map_out, stream, s1, s2);
 }
 
 int nqa_adists_dists_forward(const float *x, const float *y, int B, int H, int W, const void *packed, int prec,
                              void *ws, size_t ws_bytes, float *d_out, float *s1, float *s2, float *map_out,
                              void *stream) {
-  if (!s1 || !s2) {
-    set_error("adists_dists_forward: null similarity pointer");
-    return NQA_E_ARG;
-  }
-  return adists_run(x, y, B, H, W, packed, prec, ws, ws_bytes, d_out, map_out, stream, s1, s2);
+  return nqa_adists_dists_forward_n(x, y, B, H, W, kWin, packed, prec, ws, ws_bytes, d_out, s1, s2, map_out, stream);
 }
 
 }  // extern "C"
@@ -1851,14 +2017,25 @@ static int group_args_check(const char *who, int R, int K, int H, int W, int pre
 
 extern "C" {
 
-size_t nqa_adists_group_workspace_bytes(int R, int K, int H, int W, int prec) {
+size_t nqa_adists_group_workspace_bytes_n(int R, int K, int H, int W, int window, int prec) {
+  if (window_check("adists_group_workspace_bytes_n", window)) return 0;
   if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs || !prec_valid(prec)) return 0;
   if ((long)H * W * 64 * (long)prec_elem_bytes(prec) >= (1L << 31)) return 0;
-  return make_plan(R, R * K, K, H, W, prec).total;
+  return make_plan(R, R * K, K, H, W, prec, window).total;
+}
+
+size_t nqa_adists_group_workspace_bytes(int R, int K, int H, int W, int prec) {
+  return nqa_adists_group_workspace_bytes_n(R, K, H, W, kWin, prec);
 }
 
 int nqa_adists_forward_group(const float *ref, const float *renders, int R, int K, int H, int W, const void *packed,
                              int prec, void *ws, size_t ws_bytes, float *d_out, float *s1, float *s2, void *stream) {
+  return nqa_adists_forward_group_n(ref, renders, R, K, H, W, kWin, packed, prec, ws, ws_bytes, d_out, s1, s2, stream);
+}
+
+int nqa_adists_forward_group_n(const float *ref, const float *renders, int R, int K, int H, int W, int window,
+                               const void *packed, int prec, void *ws, size_t ws_bytes, float *d_out, float *s1,
+                               float *s2, void *stream) {
   if (!ref || !renders || !packed || !ws || !d_out) {
     set_error("adists_forward_group: null pointer");
     return NQA_E_ARG;
@@ -1868,8 +2045,9 @@ int nqa_adists_forward_group(const float *ref, const float *renders, int R, int 
     return NQA_E_ARG;
   }
   if (int rc = group_args_check("adists_forward_group", R, K, H, W, prec)) return rc;
+  if (int rc = window_check("adists_forward_group", window)) return rc;
   const int B = R * K, n = R + B;
-  const APlan p = make_plan(R, B, K, H, W, prec);
+  const APlan p = make_plan(R, B, K, H, W, prec, window);
   if (ws_bytes < p.total) {
     set_error("adists_forward_group: workspace %zu < %zu bytes", ws_bytes, p.total);
     return NQA_E_WORKSPACE;
@@ -1901,6 +2079,12 @@ int nqa_adists_forward_group(const float *ref, const float *renders, int R, int 
 int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, int H, int W, int C, int prec,
                                   const float *q, const float *wgt, int strip, float *gamma, float *tw, float *sw,
                                   void *stream) {
+  return nqa_adists_window_stage_group_n(fx, fy, R, K, H, W, kWin, C, prec, q, wgt, strip, gamma, tw, sw, stream);
+}
+
+int nqa_adists_window_stage_group_n(const void *fx, const void *fy, int R, int K, int H, int W, int window, int C,
+                                    int prec, const float *q, const float *wgt, int strip, float *gamma, float *tw,
+                                    float *sw, void *stream) {
   if (!fx || !fy || !q || !wgt || !gamma || !tw || !sw) {
     set_error("adists_window_stage_group: null pointer");
     return NQA_E_ARG;
@@ -1909,19 +2093,31 @@ int nqa_adists_window_stage_group(const void *fx, const void *fy, int R, int K, 
     set_error("adists_window_stage_group: bad group (R=%d K=%d; at most %ld pairs)", R, K, kAdistsGroupMaxPairs);
     return NQA_E_ARG;
   }
-  if (int rc = window_stage_check("adists_window_stage_group", R * K, H, W, C, prec, strip)) return rc;
-  return launch_window_stage("adists_window_stage_group", fx, fy, R * K, K, H, W, C, prec, q, C, 0, wgt, gamma, tw, sw,
+  if (int rc = window_stage_check("adists_window_stage_group", R * K, H, W, window, C, prec, strip)) return rc;
+  return launch_window_stage("adists_window_stage_group", fx, fy, R * K, K, H, W, window, C, prec, q, C, 0, wgt, gamma, tw, sw,
                              static_cast<hipStream_t>(stream), strip);
 }
 
-size_t nqa_adists_chain_group_bytes(int R, int K, int H, int W) {
+size_t nqa_adists_chain_group_bytes_n(int R, int K, int H, int W, int window) {
+  if (window_check("adists_chain_group_bytes_n", window)) return 0;
   if (R <= 0 || K <= 0 || H <= 0 || W <= 0 || (long)R * K > kAdistsGroupMaxPairs) return 0;
   return chain_plan(R, R * K, K).total;
 }
 
+size_t nqa_adists_chain_group_bytes(int R, int K, int H, int W) {
+  return nqa_adists_chain_group_bytes_n(R, K, H, W, kWin);
+}
+
+int nqa_adists_chain_group_n(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K,
+                             int H, int W, int window, void *ws, size_t ws_bytes, float *const *ps_prod, float *d,
+                             void *stream) {
+  return chain_entry("adists_chain_group", true, gamma, tw, sw, R, K, H, W, window, ws, ws_bytes, ps_prod, d, nullptr,
+                     stream);
+}
+
 int nqa_adists_chain_group(const float *const *gamma, const float *const *tw, const float *const *sw, int R, int K, int H,
                            int W, void *ws, size_t ws_bytes, float *const *ps_prod, float *d, void *stream) {
-  return chain_entry("adists_chain_group", true, gamma, tw, sw, R, K, H, W, ws, ws_bytes, ps_prod, d, nullptr, stream);
+  return nqa_adists_chain_group_n(gamma, tw, sw, R, K, H, W, kWin, ws, ws_bytes, ps_prod, d, stream);
 }
 
 }  // extern "C"

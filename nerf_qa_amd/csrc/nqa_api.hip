@@ -225,8 +225,11 @@ int nqa_set_conv_variant(int variant) {
     t.mixed_launches = 0;
     return c;
   }
+  const bool window_generic = variant > 0 && (variant & 2048) != 0;  // bit 11 rides above the query value 1024
+  const int asked = variant;
+  if (window_generic) variant -= 2048;
   if (variant < 0 || variant > 1023 || (variant & 3) == 3 || (variant & 768) == 768) {
-    set_error("set_conv_variant: unknown variant %d", variant);
+    set_error("set_conv_variant: unknown variant %d", asked);
     return NQA_E_ARG;
   }
   t.conv_variant = variant & 3;
@@ -237,6 +240,7 @@ int nqa_set_conv_variant(int variant) {
   t.fuse_taps = !(variant & 64);
   t.fuse_stage1 = !(variant & 128);
   t.edge_grid = (variant >> 8) & 3;
+  t.window_generic = window_generic;
   return NQA_OK;
 }
 

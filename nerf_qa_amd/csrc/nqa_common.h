@@ -298,6 +298,7 @@ struct Tuning {
   // bits 8-9, the grid of the implicit GEMM on maps with 1 <= W % 32 <= 16: 0 = mixed (16-wide tiles on the right
   // edge) where it saves a round of blocks, 1 = plain grids only, 2 = mixed on every such map (tests, at small sizes)
   int edge_grid = 0;
+  bool window_generic = false;  // bit 11: a window of 21 runs the generic window kernels (nqa_window_n.h) as well
   int mixed_launches = 0;  // mixed grids this thread has launched since it last asked (variant 1024)
 };
 Tuning &tuning();

@@ -7,6 +7,7 @@ tensors and raise otherwise -- there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 from typing import List, Sequence
 
@@ -568,77 +569,94 @@ def timing_collect():
     return {name: (n[i], ms[i]) for i, name in enumerate(_lib.K_NAMES)}
 
 
+CONV_WINDOW_GENERIC = 2048  # set_conv_variant bit: a 21-tap A-DISTS window runs on the generic window kernels too
+WINDOW_MIN, WINDOW_MAX = 3, 63  # the A-DISTS window sizes the library takes (include/nqa.h)
+
+
+def check_window(window, who: str = "window") -> int:
+    """The A-DISTS window size as an int; ValueError naming the range for anything but an integer in 3..63."""
+    try:
+        n = None if isinstance(window, (bool, str)) else operator.index(window)
+    except TypeError:
+        n = None
+    if n is None or not WINDOW_MIN <= n <= WINDOW_MAX:
+        raise ValueError(f"{who} must be an integer in {WINDOW_MIN}..{WINDOW_MAX} (the HIP window kernels' range), "
+                         f"got {window!r}")
+    return n
+
+
 def adists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, ws: Workspace | None = None,
-                   with_map: bool = False):
+                   with_map: bool = False, window: int = 21):
     """D (B,) float32 of ADISTS.forward (ADISTS.py:147-191); the caller returns 1-D or 1-mean(D).
 
-    with_map=True also returns the as_map=True distortion map (ADISTS.py:188-189,193) as (B,H,W)."""
-    p = prec_id(prec)
+    with_map=True also returns the as_map=True distortion map (ADISTS.py:188-189,193) as (B,H,W).
+    window: the module's window_size (3..63; 21 runs the specialised kernels)."""
+    p, n = prec_id(prec), check_window(window)
     dev = _need_cuda(x, y, packed)
     x, y = _f32c(x), _f32c(y)
     if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"expected two (B,3,H,W) tensors of equal shape, got {tuple(x.shape)} / {tuple(y.shape)}")
     b, _, h, w = x.shape
-    mb = _max_pairs(lambda n: lib().nqa_adists_workspace_bytes(n, h, w, p), b)
+    mb = _max_pairs(lambda k: lib().nqa_adists_workspace_bytes_n(k, h, w, n, p), b)
     if mb < b:
-        parts = [adists_forward(x[i:i + mb], y[i:i + mb], packed, prec, ws, with_map) for i in range(0, b, mb)]
+        parts = [adists_forward(x[i:i + mb], y[i:i + mb], packed, prec, ws, with_map, n) for i in range(0, b, mb)]
         if with_map:
             return torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts])
         return torch.cat(parts)
     d = torch.empty((b,), dtype=torch.float32, device=dev)
-    nbytes = lib().nqa_adists_workspace_bytes(b, h, w, p)
+    nbytes = lib().nqa_adists_workspace_bytes_n(b, h, w, n, p)
     buf = (ws or Workspace()).get(nbytes, dev)
     if with_map:
         m = torch.empty((b, h, w), dtype=torch.float32, device=dev)
-        _call(dev, lib().nqa_adists_forward_map, ptr(x), ptr(y), b, h, w, ptr(packed), p, ptr(buf), buf.numel(), ptr(d),
-                                           ptr(m), stream_ptr(dev))
+        _call(dev, lib().nqa_adists_forward_map_n, ptr(x), ptr(y), b, h, w, n, ptr(packed), p, ptr(buf), buf.numel(),
+              ptr(d), ptr(m), stream_ptr(dev))
         return d, m
-    _call(dev, lib().nqa_adists_forward, ptr(x), ptr(y), b, h, w, ptr(packed), p, ptr(buf), buf.numel(), ptr(d),
-                                   stream_ptr(dev))
+    _call(dev, lib().nqa_adists_forward_n, ptr(x), ptr(y), b, h, w, n, ptr(packed), p, ptr(buf), buf.numel(), ptr(d),
+          stream_ptr(dev))
     return d
 
 
 def adists_dists_forward(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, prec, ws: Workspace | None = None,
-                         with_map: bool = False):
+                         with_map: bool = False, window: int = 21):
     """(D (B,), S1 (B,1475), S2 (B,1475)[, map (B,H,W)]) from ONE pyramid: adists_forward's D (and map), bit for bit, plus
     the similarities dists_forward computes for the same pairs in `prec`, folded from the sums A-DISTS forms anyway
-    (include/nqa.h, nqa_adists_dists_forward)."""
-    p = prec_id(prec)
+    (include/nqa.h, nqa_adists_dists_forward).  window: as adists_forward's."""
+    p, n = prec_id(prec), check_window(window)
     dev = _need_cuda(x, y, packed)
     x, y = _f32c(x), _f32c(y)
     if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"expected two (B,3,H,W) tensors of equal shape, got {tuple(x.shape)} / {tuple(y.shape)}")
     b, _, h, w = x.shape
-    mb = _max_pairs(lambda n: lib().nqa_adists_workspace_bytes(n, h, w, p), b)
+    mb = _max_pairs(lambda k: lib().nqa_adists_workspace_bytes_n(k, h, w, n, p), b)
     if mb < b:
-        parts = [adists_dists_forward(x[i:i + mb], y[i:i + mb], packed, prec, ws, with_map) for i in range(0, b, mb)]
+        parts = [adists_dists_forward(x[i:i + mb], y[i:i + mb], packed, prec, ws, with_map, n) for i in range(0, b, mb)]
         return tuple(torch.cat([q[j] for q in parts]) for j in range(4 if with_map else 3))
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     s1 = torch.empty((b, TOTAL_CHNS), dtype=torch.float32, device=dev)
     s2 = torch.empty((b, TOTAL_CHNS), dtype=torch.float32, device=dev)
     m = torch.empty((b, h, w), dtype=torch.float32, device=dev) if with_map else None
-    nbytes = lib().nqa_adists_workspace_bytes(b, h, w, p)
+    nbytes = lib().nqa_adists_workspace_bytes_n(b, h, w, n, p)
     buf = (ws or Workspace()).get(nbytes, dev)
-    _call(dev, lib().nqa_adists_dists_forward, ptr(x), ptr(y), b, h, w, ptr(packed), p, ptr(buf), buf.numel(), ptr(d),
-          ptr(s1), ptr(s2), ptr(m) if with_map else None, stream_ptr(dev))
+    _call(dev, lib().nqa_adists_dists_forward_n, ptr(x), ptr(y), b, h, w, n, ptr(packed), p, ptr(buf), buf.numel(),
+          ptr(d), ptr(s1), ptr(s2), ptr(m) if with_map else None, stream_ptr(dev))
     return (d, s1, s2, m) if with_map else (d, s1, s2)
 
 
 def adists_forward_group(ref: torch.Tensor, renders: torch.Tensor, packed: torch.Tensor, prec,
-                         ws: Workspace | None = None, with_dists: bool = False):
+                         ws: Workspace | None = None, with_dists: bool = False, window: int = 21):
     """D (R*K,) float32 of K renders against ONE reference for R such groups: ref (R,3,H,W), renders (R,K,3,H,W), pair
     r * K + k = (ref[r], renders[r, k]) with x = the reference.  Everything A-DISTS takes from x alone runs once per
     reference (include/nqa.h, nqa_adists_forward_group).  with_dists=True returns (D, S1, S2), S1 / S2 (R*K,1475) the
     DISTS similarities of the same pairs from the same sums.  Groups are independent: a batch of more than 65 535 pairs,
-    or one whose workspace would exceed NQA_MAX_WORKSPACE_GB, runs in equal slices over R."""
-    p = prec_id(prec)
+    or one whose workspace would exceed NQA_MAX_WORKSPACE_GB, runs in equal slices over R.  window: as adists_forward's."""
+    p, n = prec_id(prec), check_window(window)
     dev = _need_cuda(ref, renders, packed)
     r, k, h, w = _group_dims(ref, renders)
     ref, renders = _f32c(ref), _f32c(renders)
-    mr = _max_pairs(lambda n: lib().nqa_adists_group_workspace_bytes(n, k, h, w, p), r)
+    mr = _max_pairs(lambda j: lib().nqa_adists_group_workspace_bytes_n(j, k, h, w, n, p), r)
     mr = max(1, min(mr, 65535 // k))  # (pairs of one call: the library's limit)
     if mr < r:
-        parts = [adists_forward_group(ref[i:i + mr], renders[i:i + mr], packed, prec, ws, with_dists)
+        parts = [adists_forward_group(ref[i:i + mr], renders[i:i + mr], packed, prec, ws, with_dists, n)
                  for i in range(0, r, mr)]
         if with_dists:
             return tuple(torch.cat([q[j] for q in parts]) for j in range(3))
@@ -646,51 +664,60 @@ def adists_forward_group(ref: torch.Tensor, renders: torch.Tensor, packed: torch
     d = torch.empty((r * k,), dtype=torch.float32, device=dev)
     s1 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev) if with_dists else None
     s2 = torch.empty((r * k, TOTAL_CHNS), dtype=torch.float32, device=dev) if with_dists else None
-    nbytes = lib().nqa_adists_group_workspace_bytes(r, k, h, w, p)
+    nbytes = lib().nqa_adists_group_workspace_bytes_n(r, k, h, w, n, p)
     buf = (ws or Workspace()).get(nbytes, dev)
-    _call(dev, lib().nqa_adists_forward_group, ptr(ref), ptr(renders), r, k, h, w, ptr(packed), p, ptr(buf), buf.numel(),
-          ptr(d), ptr(s1) if with_dists else None, ptr(s2) if with_dists else None, stream_ptr(dev))
+    _call(dev, lib().nqa_adists_forward_group_n, ptr(ref), ptr(renders), r, k, h, w, n, ptr(packed), p, ptr(buf),
+          buf.numel(), ptr(d), ptr(s1) if with_dists else None, ptr(s2) if with_dists else None, stream_ptr(dev))
     return (d, s1, s2) if with_dists else d
 
 
 def adists_window_stage_group(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, prec,
-                              strip: int = 0):
+                              strip: int = 0, window: int = 21, out=None):
     """One stage of the group window pass as adists_forward_group launches it (include/nqa.h,
     nqa_adists_window_stage_group): fx the R references' maps, fy the R*K renders' (pair r * K + k), q (8,R*K,C), wgt
-    (R,C); maps as adists_window_stage takes them.  Returns gamma (R, mh, mw) and tw, sw (R*K, mh, mw)."""
-    p, strip = prec_id(prec), int(strip)
+    (R,C); maps as adists_window_stage takes them.  Returns gamma (R, mh, mw) and tw, sw (R*K, mh, mw); out = (gamma,
+    tw, sw): caller-owned contiguous float32 maps of those shapes to write instead (tests place them between guards)."""
+    p, strip, n = prec_id(prec), int(strip), check_window(window)
     dev = _need_cuda(fx, fy, q, wgt)
     r = int(wgt.shape[0]) if wgt.dim() == 2 else 0
-    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip, "adists_window_stage_group", r)
-    gamma = torch.empty((r,) + shape[1:], dtype=torch.float32, device=dev)
-    tw = torch.empty(shape, dtype=torch.float32, device=dev)
-    sw = torch.empty(shape, dtype=torch.float32, device=dev)
-    _call(dev, lib().nqa_adists_window_stage_group, ptr(fx), ptr(fy), r, b // r, h, w, c, p, ptr(q), ptr(wgt), strip,
+    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip, "adists_window_stage_group", r, n)
+    if out is None:
+        gamma = torch.empty((r,) + shape[1:], dtype=torch.float32, device=dev)
+        tw = torch.empty(shape, dtype=torch.float32, device=dev)
+        sw = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        gamma, tw, sw = out
+        _need_cuda(gamma, tw, sw)
+        for t, sh in ((gamma, (r,) + shape[1:]), (tw, shape), (sw, shape)):
+            if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"adists_window_stage_group: outputs must be contiguous float32 {sh}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+    _call(dev, lib().nqa_adists_window_stage_group_n, ptr(fx), ptr(fy), r, b // r, h, w, n, c, p, ptr(q), ptr(wgt), strip,
           ptr(gamma), ptr(tw), ptr(sw), stream_ptr(dev))
     return gamma, tw, sw
 
 
 def adists_chain_group(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor], sw: Sequence[torch.Tensor], h: int,
-                       w: int, ws: Workspace | None = None):
+                       w: int, ws: Workspace | None = None, window: int = 21):
     """The back part of adists_forward_group as it launches it (include/nqa.h, nqa_adists_chain_group): gamma six
     (R, mh, mw) maps, tw / sw six (R*K, mh, mw) maps for an h x w frame -> (ps_prod: six (R, mh, mw) maps, D (R*K,))."""
     _chain_lists(gamma=gamma, tw=tw, sw=sw)
     dev = _need_cuda(*gamma, *tw, *sw)
-    h, w = int(h), int(w)
+    h, w, n = int(h), int(w), check_window(window)
     r = int(gamma[0].shape[0]) if gamma[0].dim() == 3 else 0
-    b, dims = _chain_dims(gamma, tw, sw, h, w, "adists_chain_group", r)
+    b, dims = _chain_dims(gamma, tw, sw, h, w, "adists_chain_group", r, n)
     ps = [torch.empty((r,) + dm, dtype=torch.float32, device=dev) for dm in dims]
     d = torch.empty((b,), dtype=torch.float32, device=dev)
-    nbytes = lib().nqa_adists_chain_group_bytes(r, b // r, h, w)
+    nbytes = lib().nqa_adists_chain_group_bytes_n(r, b // r, h, w, n)
     buf = (ws or Workspace()).get(nbytes, dev)
     arr = lambda ts: (C.c_void_p * 6)(*[ptr(t) for t in ts])
-    _call(dev, lib().nqa_adists_chain_group, arr(gamma), arr(tw), arr(sw), r, b // r, h, w, ptr(buf), buf.numel(), arr(ps),
+    _call(dev, lib().nqa_adists_chain_group_n, arr(gamma), arr(tw), arr(sw), r, b // r, h, w, n, ptr(buf), buf.numel(), arr(ps),
           ptr(d), stream_ptr(dev))
     return ps, d
 
 
 def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, p: int, strip: int,
-                       who: str = "adists_window_stage", r: int | None = None):
+                       who: str = "adists_window_stage", r: int | None = None, window: int = 21):
     """Every check of adists_window_stage (or, with the group count r, adists_window_stage_group) on its inputs;
     (B, H, W, C, shape of a per-pair output map).  C is q's: 3 means float32 NCHW planes, anything else NHWC taps in
     prec's storage type.  The x-side tensors (fx, wgt) have r rows, or B without r; the pair-side ones (fy, q) B."""
@@ -716,36 +743,39 @@ def _window_stage_dims(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt:
         if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be contiguous {dt} {sh}, got {t.dtype} {tuple(t.shape)}"
                              f"{'' if t.is_contiguous() else ' (not contiguous)'}")
-    windowed = h >= WINDOW and w >= WINDOW
-    out = (b, h - WINDOW + 1, w - WINDOW + 1) if windowed else (b, 1, 1)
+    windowed = h >= window and w >= window
+    out = (b, h - window + 1, w - window + 1) if windowed else (b, 1, 1)
     if strip < 0 or (windowed and strip > out[1]):
         raise ValueError(f"{who}: strip {strip} outside [0, {out[1] if windowed else 0}]")
     return b, h, w, c, out
 
 
-def adists_window_stage(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, prec, strip: int = 0):
+def adists_window_stage(fx: torch.Tensor, fy: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, prec, strip: int = 0,
+                        window: int = 21):
     """One stage of the A-DISTS heavy pass as adists_forward launches it (include/nqa.h, nqa_adists_window_stage):
     (gamma, tw, sw), each (B, H-20, W-20) float32, or (B, 1, 1) from the global branch when H or W is under 21.
     q (8,B,C) and wgt (B,C) float32; fx, fy (B,3,H,W) float32 planes for C == 3, else (B,H,W,C) NHWC taps in prec's
-    storage type.  strip: see the header (0 = the launcher's choice)."""
+    storage type.  strip: see the header (0 = the launcher's choice).  window: 3..63 in place of 21 (the generic
+    kernels; nqa_adists_window_stage_n)."""
+    n = check_window(window)
     _need_cuda(fx, fy, q, wgt)
-    out_shape = _window_stage_dims(fx, fy, q, wgt, prec_id(prec), int(strip))[4]
+    out_shape = _window_stage_dims(fx, fy, q, wgt, prec_id(prec), int(strip), window=n)[4]
     out = torch.empty((3,) + out_shape, dtype=torch.float32, device=fx.device)
-    adists_window_stage_into(fx, fy, q, wgt, prec, strip, out[0], out[1], out[2])
+    adists_window_stage_into(fx, fy, q, wgt, prec, strip, out[0], out[1], out[2], n)
     return out[0], out[1], out[2]
 
 
-def adists_window_stage_into(fx, fy, q, wgt, prec, strip, gamma, tw, sw) -> None:
+def adists_window_stage_into(fx, fy, q, wgt, prec, strip, gamma, tw, sw, window: int = 21) -> None:
     """adists_window_stage into caller-owned contiguous float32 maps of the shape it would return (tests place them
     between guard regions).  Every check of adists_window_stage applies."""
-    p, strip = prec_id(prec), int(strip)
+    p, strip, n = prec_id(prec), int(strip), check_window(window)
     dev = _need_cuda(fx, fy, q, wgt, gamma, tw, sw)
-    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip)
+    b, h, w, c, shape = _window_stage_dims(fx, fy, q, wgt, p, strip, window=n)
     for t in (gamma, tw, sw):
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"adists_window_stage: outputs must be contiguous float32 {shape}, got {t.dtype} "
                              f"{tuple(t.shape)}")
-    _call(dev, lib().nqa_adists_window_stage, ptr(fx), ptr(fy), b, h, w, c, p, ptr(q), ptr(wgt), strip, ptr(gamma),
+    _call(dev, lib().nqa_adists_window_stage_n, ptr(fx), ptr(fy), b, h, w, n, c, p, ptr(q), ptr(wgt), strip, ptr(gamma),
           ptr(tw), ptr(sw), stream_ptr(dev))
 
 
@@ -757,11 +787,11 @@ def adists_window_grid(b: int, h: int, w: int, c: int, prec, strip: int = 0) -> 
     return tuple(g)
 
 
-def adists_chain_dims(h: int, w: int):
+def adists_chain_dims(h: int, w: int, window: int = 21):
     """([(mh, mw)] of the six stages' maps for an h x w frame, the number of windowed stages), from the library's own plan
-    (include/nqa.h, nqa_adists_chain_dims)."""
+    (include/nqa.h, nqa_adists_chain_dims_n)."""
     mh, mw = (C.c_int * 6)(), (C.c_int * 6)()
-    n = lib().nqa_adists_chain_dims(int(h), int(w), mh, mw)
+    n = lib().nqa_adists_chain_dims_n(int(h), int(w), check_window(window), mh, mw)
     if n < 0:
         check(n)
     return list(zip(mh, mw)), n
@@ -773,7 +803,7 @@ def _chain_lists(**lists) -> None:
             raise ValueError(f"adists_chain: {name} must be a list of six tensors, one per stage")
 
 
-def _chain_dims(gamma, tw, sw, h: int, w: int, who: str = "adists_chain", r: int | None = None):
+def _chain_dims(gamma, tw, sw, h: int, w: int, who: str = "adists_chain", r: int | None = None, window: int = 21):
     """Every check of adists_chain (or, with the group count r, adists_chain_group) on its inputs but their device;
     (B, [(mh, mw)] per stage).  The x-side maps (gamma) have r rows, or B without r; the pair-side ones (tw, sw) B."""
     _chain_lists(gamma=gamma, tw=tw, sw=sw)
@@ -785,7 +815,7 @@ def _chain_dims(gamma, tw, sw, h: int, w: int, who: str = "adists_chain", r: int
     nx = b if r is None else r
     if nx <= 0 or b % nx:
         raise ValueError(f"{who}: {b} pairs do not divide into {nx} groups")
-    dims, _ = adists_chain_dims(h, w)
+    dims, _ = adists_chain_dims(h, w, window)
     for name, ts, n in (("gamma", gamma, nx), ("tw", tw, b), ("sw", sw, b)):
         for k, t in enumerate(ts):
             sh = (n,) + dims[k]
@@ -796,21 +826,22 @@ def _chain_dims(gamma, tw, sw, h: int, w: int, who: str = "adists_chain", r: int
 
 
 def adists_chain(gamma: Sequence[torch.Tensor], tw: Sequence[torch.Tensor], sw: Sequence[torch.Tensor], h: int, w: int,
-                 with_map: bool = True, ws: Workspace | None = None):
+                 with_map: bool = True, ws: Workspace | None = None, window: int = 21):
     """The back part of adists_forward as it launches it (include/nqa.h, nqa_adists_chain): from the six stages' gamma /
     tw / sw maps, each (B, mh, mw) float32 for an h x w frame (adists_chain_dims), to (ps_prod: six (B, mh, mw) maps,
     D (B,), map (B,h,w) or None)."""
     _chain_lists(gamma=gamma, tw=tw, sw=sw)
     dev = _need_cuda(*gamma, *tw, *sw)
-    b, dims = _chain_dims(gamma, tw, sw, h, w)
+    b, dims = _chain_dims(gamma, tw, sw, h, w, window=check_window(window))
     ps = [torch.empty((b,) + d, dtype=torch.float32, device=dev) for d in dims]
     d = torch.empty((b,), dtype=torch.float32, device=dev)
     m = torch.empty((b, int(h), int(w)), dtype=torch.float32, device=dev) if with_map else None
-    adists_chain_into(gamma, tw, sw, h, w, ps, d, m, ws)
+    adists_chain_into(gamma, tw, sw, h, w, ps, d, m, ws, window)
     return ps, d, m
 
 
-def adists_chain_into(gamma, tw, sw, h: int, w: int, ps_prod, d, map_out=None, ws: Workspace | None = None) -> None:
+def adists_chain_into(gamma, tw, sw, h: int, w: int, ps_prod, d, map_out=None, ws: Workspace | None = None,
+                      window: int = 21) -> None:
     """adists_chain into caller-owned contiguous float32 outputs of the shapes it would return (tests place them between
     guard regions); map_out None: no map.  Every check of adists_chain applies."""
     _chain_lists(gamma=gamma, tw=tw, sw=sw, ps_prod=ps_prod)
@@ -818,16 +849,17 @@ def adists_chain_into(gamma, tw, sw, h: int, w: int, ps_prod, d, map_out=None, w
     if not all(torch.is_tensor(t) for t in outs):
         raise ValueError("adists_chain: d (and map_out, if given) must be tensors")
     dev = _need_cuda(*gamma, *tw, *sw, *outs)
-    b, dims = _chain_dims(gamma, tw, sw, h, w)
+    n = check_window(window)
+    b, dims = _chain_dims(gamma, tw, sw, h, w, window=n)
     h, w = int(h), int(w)
     want = [(b,) + dm for dm in dims] + [(b,)] + ([] if map_out is None else [(b, h, w)])
     for t, sh in zip(outs, want):
         if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"adists_chain: outputs must be contiguous float32, here {sh}, got {t.dtype} {tuple(t.shape)}")
-    nbytes = lib().nqa_adists_chain_bytes(b, h, w)
+    nbytes = lib().nqa_adists_chain_bytes_n(b, h, w, n)
     buf = (ws or Workspace()).get(nbytes, dev)
     arr = lambda ts: (C.c_void_p * 6)(*[ptr(t) for t in ts])
-    _call(dev, lib().nqa_adists_chain, arr(gamma), arr(tw), arr(sw), b, h, w, ptr(buf), buf.numel(), arr(ps_prod), ptr(d),
+    _call(dev, lib().nqa_adists_chain_n, arr(gamma), arr(tw), arr(sw), b, h, w, n, ptr(buf), buf.numel(), arr(ps_prod), ptr(d),
           None if map_out is None else ptr(map_out), stream_ptr(dev))
 
 

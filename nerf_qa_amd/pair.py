@@ -82,15 +82,16 @@ def score_pair(dists_model, adists_model, x, y, batch_average=False, as_loss=Fal
                        "there is no CPU fallback)" % (x.device, y.device))
     dev = x.device
     _check_same_weights(dists_model, adists_model, dev)
-    ws = adists_model._ws
+    ws, n = adists_model._ws, adists_model._window()
     with torch.no_grad():
         if as_map:
-            d, s1, s2, m = ops.adists_dists_forward(x, y, adists_model._packed_weights(dev, prec), prec, ws, with_map=True)
+            d, s1, s2, m = ops.adists_dists_forward(x, y, adists_model._packed_weights(dev, prec), prec, ws, with_map=True,
+                                                    window=n)
             b = m.shape[0]
             a_out = m.unsqueeze(1).expand(b, b, *m.shape[1:]).contiguous()  # (ADISTS.forward: the reference's broadcast)
         else:
             d, s1, s2 = adists_model._batched(
-                x, y, prec, lambda a, b, packed: ops.adists_dists_forward(a, b, packed, prec, ws))
+                x, y, prec, lambda a, b, packed: ops.adists_dists_forward(a, b, packed, prec, ws, window=n))
             a_out = 1 - d.mean() if as_loss else 1 - d
     return dists_model._weighted(s1, s2, batch_average), a_out
 
@@ -108,7 +109,7 @@ def score_group(dists_model, adists_model, ref, renders):
     _check_same_weights(dists_model, adists_model, dev)
     with torch.no_grad():
         d, s1, s2 = ops.adists_forward_group(ref, renders, adists_model._packed_weights(dev, prec), prec, adists_model._ws,
-                                             with_dists=True)
+                                             with_dists=True, window=adists_model._window())
     return dists_model._weighted(s1, s2, False).reshape(r, k), (1 - d).reshape(r, k)
 
 
@@ -128,7 +129,8 @@ def forward_target(dists_model, adists_model, target, y, batch_average=False, as
     The gradient chain runs in the two modules' grad_precision, which must be the same ("f32s" | "f16").
     ValueError for modules that name different ones, a target of a third module, one prepared before its owner's VGG
     weights changed, and a shape that does not fit; NqaError for modules with different VGG weights, tensors off the GPU, and a batch whose A-DISTS
-    scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices)."""
+    scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices); ValueError too where y requires grad and the A-DISTS
+    module's window_size is not 21 (ADISTS.forward_target)."""
     from . import autograd, target as tgt
     gp = [getattr(m, "grad_precision", "f32s") for m in (dists_model, adists_model)]
     if gp[0] != gp[1]:  # (one chain carries both metrics' gradients: the same kind of rule as pair_precision)
@@ -138,6 +140,7 @@ def forward_target(dists_model, adists_model, target, y, batch_average=False, as
     _check_same_weights(dists_model, adists_model, y.device, "forward_target")
     autograd.adists_target_fits(target)
     if torch.is_grad_enabled() and y.requires_grad:
+        autograd.check_target_window(adists_model)
         s1, s2, a = autograd.PairTargetLoss.apply(y, target, adists_model, bool(as_loss))
     else:
         s1, s2, d = autograd.pair_target_values(adists_model, target, y)
