@@ -543,7 +543,9 @@ int nqa_conv_pool_stats(const void *in, int B, int H, int W, int layer, const vo
  * adding 128 does the same for stage 1 (conv1_regw_kernel + pool_stats_kernel instead of nqa_conv1_pool.hip's kernel);
  * adding 8 selects the first form of the A-DISTS window pass (every wave loads its own taps instead of sharing them
  * through LDS); adding 2048 runs a 21-tap A-DISTS window on the generic window kernels (nqa_window_n.h) instead of the
- * specialised ones.  Bits 8-9 choose the implicit GEMM's grid on maps whose last 32-wide tile column is at most half full
+ * specialised ones; adding 4096 does the same for a window of 21 on the _n window-moments and stage-backward entry points
+ * (nqa_window_moments_forward_n ...; nqa_window_moments_n.hip; the bit counts on top of a non-zero variant, e.g. 1 + 4096:
+ * 4096 on its own is refused as it always was).  Bits 8-9 choose the implicit GEMM's grid on maps whose last 32-wide tile column is at most half full
  * (1 <= W % 32 <= 16): by default such a layer takes ONE launch of 32-wide tiles plus 16-wide tiles down the right edge
  * (conv3x3_igemm_mixed_kernel) wherever that needs fewer rounds of blocks over the chip than the plain grid of 32-wide
  * tiles; adding 256 keeps the plain grid everywhere (A/B runs), adding 512 takes the mixed grid on every such map
@@ -771,6 +773,31 @@ size_t nqa_adists_ts_backward_bytes(int B, int C, int H, int W);
 int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
                            int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *workspace,
                            size_t workspace_bytes, float *gy, void *stream);
+
+/* ---- the same four entry points for a window of `window` taps, 3 <= window <= 63, odd or even
+ * (nqa_window_moments_n.hip): the normalised Gaussian of sigma window / 3 centred at window / 2 (integer division, so an
+ * even window is not symmetric), the taps of nqa_adists_forward_n.  Everything above holds with 21 replaced by `window`:
+ * h = H - window + 1, w = W - window + 1; a stage of nqa_adists_ts_backward_n is windowed iff H >= window && W >= window,
+ * ps is (B, h, w) there and (B, 1, 1) on the global branch, which a map under the window in either direction takes.
+ * Sums run in ascending tap order forwards and in ascending window order in the transposed pass, which walks the taps
+ * mirrored.  Rows move as 16-byte accesses where W % 4 == 0 (the window-mean maps only where also (window - 1) % 4 == 0),
+ * and the alignment rule is the one above: every pointer 16-byte aligned where W % 4 == 0 (ps of
+ * nqa_adists_ts_backward_n only where mh * mw is a multiple of 4 as well: nothing else reads it in 16-byte pieces, and a
+ * stage's ps inside a larger buffer need not start on a 16-byte boundary then).
+ * window == 21 runs the 21-tap kernels of the entry points above, bit for bit, unless nqa_set_conv_variant carries 4096,
+ * which sends it to the generic kernels too (tests, A/B runs); the entry points above never change.
+ * Refusals are those above, on the host and before any launch, and in addition NQA_E_ARG for a window outside [3, 63]
+ * (the message names the range); NQA_E_SHAPE for H or W below `window` on the two moments entry points.
+ * nqa_adists_ts_backward_bytes_n is 0 for a window outside the range as for every other refused size. */
+int nqa_window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int window, float *out,
+                                 void *stream);
+int nqa_window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int window, const float *g0,
+                                  const float *g1, const float *g2, const float *g3, const float *g4, float *gx, float *gy,
+                                  void *stream);
+size_t nqa_adists_ts_backward_bytes_n(int B, int C, int H, int W, int window);
+int nqa_adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
+                             const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask,
+                             int out_nhwc, void *workspace, size_t workspace_bytes, float *gy, void *stream);
 
 #ifdef __cplusplus
 }

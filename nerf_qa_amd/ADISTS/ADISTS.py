@@ -23,7 +23,9 @@ layers in f32s, as for DISTS(require_grad=True)) and the head -- texture probabi
 evaluated in torch operations on the GPU (ADISTS/head.py) so that autograd differentiates it; the value returned is still the
 fused kernel's.  With the gradient on y alone (x the fixed frame: the training-loss use) and loss_head="auto" the head's
 backward is HIP as well (autograd.AdistsLossY, csrc/nqa_adists_backward.hip): no torch head, no graph over maps, no host
-read.  Otherwise the value 1-mean(D) comes from the fused kernel alone (there is no graph to lose).  No script of
+read; loss_head="hip" (opt-in) does the same for every window_size in 3..63 -- the one-sided backward, prepared targets and
+the pair step on the generic window-moments kernels (csrc/nqa_window_moments_n.hip) -- where "auto" keeps them to 21.
+Otherwise the value 1-mean(D) comes from the fused kernel alone (there is no graph to lose).  No script of
 the reference calls it with a gradient (prep.py:186, test2_prep.py:151 pass as_loss=False).  as_map=True returns the
 reference's [B,B,H,W] distortion map (:163,188-193) from one extra kernel.
 """
@@ -53,9 +55,12 @@ DEFAULT_PRECISION = "auto"
 AUTO_EXACT_PIXELS = 128 * 128
 # The head of the loss path (as_loss=True under autograd).  "auto": the one-sided HIP backward (autograd.AdistsLossY)
 # where only y requires grad -- a render optimised against a fixed frame x -- and the torch head (ADISTS/head.py)
-# wherever x requires grad; "torch": the torch head for every case.  NQA_ADISTS_LOSS_HEAD sets the default.
+# wherever x requires grad -- both only with window_size 21, every other window on the torch head with shifted slices;
+# "torch": the torch head for every case; "hip": "auto" at 21 launch for launch, and for every other window in 3..63 the
+# one-sided HIP backward and forward_target's gradients on the generic window-moments kernels, the torch head with HIP
+# window moments (head window_impl="hip") wherever x requires grad.  NQA_ADISTS_LOSS_HEAD sets the default.
 DEFAULT_LOSS_HEAD = "auto"
-LOSS_HEADS = ("auto", "torch")
+LOSS_HEADS = ("auto", "torch", "hip")
 
 
 def _check_loss_head(v):
@@ -192,15 +197,19 @@ class ADISTS(torch.nn.Module):
 
         With the gradient on y alone (x the fixed ground-truth frame, prep.py:186) and loss_head "auto" there is no
         torch head and no autograd graph over maps: autograd.AdistsLossY returns the same value and its backward is
-        autograd.adists_backward_y, HIP from end to end, without a device -> host read."""
+        autograd.adists_backward_y, HIP from end to end, without a device -> host read.  "auto" does so with
+        window_size 21 only; loss_head "hip" for every window, and its torch head (x requires grad) takes the HIP window
+        moments for every window as well."""
         from .. import autograd
         from . import head
-        # (the one-sided HIP backward is built on 21-tap kernels: any other window takes the torch head on every side)
-        if self.loss_head != "torch" and y.requires_grad and not x.requires_grad and self._window() == ops.WINDOW:
+        # (under "auto" the one-sided HIP backward stays on the 21-tap kernels and any other window takes the torch head on
+        # every side; "hip" runs it on the generic kernels for every window)
+        hip = self.loss_head == "hip"
+        if self.loss_head != "torch" and y.requires_grad and not x.requires_grad and (hip or self._window() == ops.WINDOW):
             return autograd.AdistsLossY.apply(x, y, self)
         tx = autograd.PyramidTaps.apply(x, self) if x.requires_grad else self._taps_nograd(x)
         ty = autograd.PyramidTaps.apply(y, self) if y.requires_grad else self._taps_nograd(y)
-        d = head.adists_d([x.float()] + list(tx), [y.float()] + list(ty), self.window_size)
+        d = head.adists_d([x.float()] + list(tx), [y.float()] + list(ty), self.window_size, "hip" if hip else "auto")
         loss = 1 - d.mean()
         with torch.no_grad():
             value = 1 - self._score(x.detach(), y.detach(), self.precision_for(x.shape[-2], x.shape[-1])).mean()
@@ -251,8 +260,10 @@ class ADISTS(torch.nn.Module):
         grad_precision ("f32s", or "f16": half gradient maps, the same value).  The target is used whole: NqaError if its batch does not
         fit NQA_MAX_WORKSPACE_GB (pass target[i:j] slices), and for tensors off the GPU; ValueError for a target of
         another module, one prepared before the VGG weights changed, and a shape that does not fit.  With a window_size
-        other than 21 the value works as described, but a gradient does not (the head's HIP backward is 21-tap):
-        ValueError where y requires grad -- use adists(x, y), whose torch head differentiates any window."""
+        other than 21 the value works as described; a gradient does with loss_head="hip" (the head's HIP backward on
+        the generic window-moments kernels, every window in 3..63; y.grad is then that of forward(x, y) under "hip" bit
+        for bit), and under "auto" / "torch" it is a ValueError where y requires grad -- use adists(x, y), whose torch
+        head differentiates any window, or build the module with loss_head="hip"."""
         from .. import autograd, target as tgt
         tgt.check(self, target, y, "ADISTS")
         if torch.is_grad_enabled() and y.requires_grad:

@@ -9,7 +9,8 @@ head below is torch on the GPU, so autograd differentiates it.  It is written fo
 global moments where a map is smaller than the window (the reference's try / except) decided from the shape -- and is
 checked against float64 autograd over the CPU oracle (tests/test_gpu_backward.py).  The 21 x 21 Gaussian window means,
 the only part that touches every value of every map 42 times, are `autograd.WindowMoments` on float32 CUDA maps (one
-HIP launch forward, one backward: csrc/nqa_window_moments.hip) and two 1-D passes of shifted slices everywhere else."""
+HIP launch forward, one backward: csrc/nqa_window_moments.hip) and two 1-D passes of shifted slices everywhere else;
+window_impl="hip" takes the HIP moments for every window size in 3..63 (csrc/nqa_window_moments_n.hip)."""
 from __future__ import annotations
 
 import math
@@ -51,14 +52,17 @@ def _window_mean(t: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
 def _moments(x: torch.Tensor, y, window_size: int, window_impl: str):
     """Window means (E[x], E[x^2]) of x alone or (E[x], E[y], E[x^2], E[y^2], E[xy]) of a pair.  "auto": the HIP kernels
     where they apply (float32 CUDA maps, the library's 21-tap window), the slices of _window_mean otherwise (CPU tensors,
-    float64, other window sizes); "slices": always those."""
-    if window_impl not in ("auto", "slices"):
-        raise ValueError(f"window_impl must be 'auto' or 'slices', got {window_impl!r}")
-    hip = (window_impl == "auto" and window_size == 21 and x.is_cuda and x.dtype == torch.float32
+    float64, other window sizes); "slices": always those; "hip": the HIP kernels for every window size in 3..63 on float32
+    CUDA maps (the generic kernels of csrc/nqa_window_moments_n.hip beside the 21-tap ones), slices elsewhere."""
+    if window_impl not in ("auto", "slices", "hip"):
+        raise ValueError(f"window_impl must be 'auto', 'slices' or 'hip', got {window_impl!r}")
+    from ..ops import WINDOW_MAX, WINDOW_MIN
+    sized = window_size == 21 if window_impl == "auto" else WINDOW_MIN <= window_size <= WINDOW_MAX
+    hip = (window_impl != "slices" and sized and x.is_cuda and x.dtype == torch.float32
            and (y is None or (y.is_cuda and y.dtype == torch.float32)))
     if hip:
         from ..autograd import WindowMoments
-        return WindowMoments.apply(x, y)
+        return WindowMoments.apply(x, y) if window_size == 21 else WindowMoments.apply(x, y, window_size)
     g = gauss_1d(window_size, x)
     if y is None:
         return _window_mean(x, g), _window_mean(x * x, g)
@@ -117,7 +121,8 @@ def channel_weights(feats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
 def adists_d(feats_x: Sequence[torch.Tensor], feats_y: Sequence[torch.Tensor], window_size: int = 21,
              window_impl: str = "auto") -> torch.Tensor:
     """D (B,) of ADISTS.py:147-191 from the two pyramids (lists of six NCHW maps); the module returns 1 - D or 1 - mean(D).
-    window_impl="slices" forces the shifted-slice window means on every device (see _moments)."""
+    window_impl="slices" forces the shifted-slice window means on every device, "hip" takes the HIP window means for
+    every window size (see _moments)."""
     ps_x = texture_probabilities(feats_x, window_size, window_impl)
     wl = channel_weights(feats_x)
     d = 0

@@ -141,6 +141,11 @@ _SIGNATURES = {
     "nqa_window_moments_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nqa_adists_ts_backward_bytes": (_sz, [_i, _i, _i, _i]),
     "nqa_adists_ts_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    "nqa_window_moments_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "nqa_window_moments_backward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nqa_adists_ts_backward_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
+    "nqa_adists_ts_backward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp,
+                                      _vp]),
     "nqa_set_conv_variant": (_i, [_i]),
     "nqa_timing_enable": (_i, [_i]),
     "nqa_timing_collect": (_i, [C.POINTER(_i), C.POINTER(C.c_double)]),

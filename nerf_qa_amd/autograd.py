@@ -18,6 +18,9 @@ reference the tests pin, A-DISTS' head, and the baseline of tools/gpu_loss_step_
 
 A-DISTS as a loss with the gradient on y alone (x the fixed frame) has the same kind of path: AdistsLossY /
 adists_backward_y, the head's backward in csrc/nqa_adists_backward.hip on top of the scoring path's staged entry points.
+Under loss_head="auto" that path (and a gradient through a prepared target) is taken with window_size 21 only; under
+loss_head="hip" every window in 3..63 takes it, on the generic window-moments kernels of csrc/nqa_window_moments_n.hip
+(_backward_window names the window the stage backward runs with).
 
 Against a PREPARED TARGET (nerf_qa_amd/target.py: the fixed frame's taps computed once for the whole optimisation) both
 losses run one kept pyramid of y per step and nothing of x: DistsTargetSimilarities keeps the statistics' fp64 partials
@@ -325,10 +328,16 @@ def dists_backward(module, x, y, g1, g2, need=(True, True), host_scaled=False):
     return (gimg + gx0, None) if need[0] else (None, gimg + gy0)
 
 
-def _adists_y_bytes(b, h, w):
+def _adists_y_bytes(b, h, w, window=ops.WINDOW):
     """Device bytes adists_backward_y holds beside the pyramid for b pairs of h x w frames at its largest stage (relu1_2:
-    the two planar copies of the taps, the NHWC gradient and the stage's workspace)."""
-    return 3 * b * 64 * h * w * 4 + int(ops.lib().nqa_adists_ts_backward_bytes(b, 64, h, w))
+    the two planar copies of the taps, the NHWC gradient and the stage's workspace for a window of `window` taps)."""
+    return 3 * b * 64 * h * w * 4 + int(ops.lib().nqa_adists_ts_backward_bytes_n(b, 64, h, w, window))
+
+
+def _backward_window(module) -> int:
+    """The window the head's HIP backward runs with: the module's own under loss_head="hip"; 21 otherwise, where a
+    backward runs only with window_size 21 (ADISTS._loss_with_grad, check_target_window)."""
+    return module._window() if getattr(module, "loss_head", None) == "hip" else ops.WINDOW
 
 
 @torch.no_grad()
@@ -343,7 +352,8 @@ def adists_backward_y(module, x, y, u):
     the batch.  Batches whose scratch would pass NQA_MAX_WORKSPACE_GB run in slices of pairs."""
     x, y, u = x.float().contiguous(), y.float().contiguous(), ops._f32c(u)
     b, _, h, w = x.shape
-    n = ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b)
+    win = _backward_window(module)
+    n = ops._max_pairs(lambda k: _adists_y_bytes(k, h, w, win), b)
     if n < b:
         return torch.cat([adists_backward_y(module, x[i:i + n], y[i:i + n], u[i:i + n]) for i in range(0, b, n)])
     tx = pyramid_taps(module, x)
@@ -360,7 +370,7 @@ def adists_y_forward(module, x, tx, y, keep=True, kept=None):
     DISTS); no pyramid launch runs here then, and `keep` is not looked at."""
     b, _, h, w = x.shape
     prec, dev, ws = "f32s", x.device, module._ws
-    n = module._window()  # (a value for any window; adists_y_backward follows only a 21-tap forward)
+    n = module._window()  # (a value for any window; adists_y_backward follows it at 21, and at every n under "hip")
     pyramid = _pyramid_forward(module, y, keep) if kept is None else KeptPyramid(*kept)
     ty = pyramid.taps
     # ---- what the head takes from x alone, and the per-channel scalars of both: the forward's own kernels ----
@@ -385,12 +395,13 @@ def _adists_y_tap_grads(module, x, tx, y, state, u):
     """(g0, g_taps) of A-DISTS towards y for dL/dD = u (B,): the image term (B,3,H,W) and the five masked NHWC tap
     gradients, each a buffer of its own that the caller may add to."""
     q, wgt, maps, ty = state.q, state.wgt, state.maps, state.pyramid.taps
-    prec, ws = "f32s", module._ws
-    g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws)
+    prec, ws, win = "f32s", module._ws, _backward_window(module)
+    g0 = ops.adists_ts_backward(x, y, q, wgt, maps[0][3], u, mask=False, coff=0, ws=ws, window=win)
     off, g_taps = 3, []
     for k in range(1, 6):
         px, py = ops.nhwc_to_nchw_f32(tx[k - 1], prec), ops.nhwc_to_nchw_f32(ty[k - 1], prec)
-        g_taps.append(ops.adists_ts_backward(px, py, q, wgt, maps[k][3], u, mask=True, coff=off, nhwc=True, ws=ws))
+        g_taps.append(ops.adists_ts_backward(px, py, q, wgt, maps[k][3], u, mask=True, coff=off, nhwc=True, ws=ws,
+                                                window=win))
         off += ops.CHNS[k]
     return g0, g_taps
 
@@ -461,21 +472,23 @@ class AdistsLossY(torch.autograd.Function):
 
 
 def check_target_window(module) -> None:
-    """ValueError for a gradient through forward_target with a window other than 21: the head's backward
-    (nqa_window_moments, nqa_adists_ts_backward) is built on 21-tap kernels."""
+    """ValueError for a gradient through forward_target with a window other than 21 unless the module was built with
+    loss_head="hip": under "auto" and "torch" the head's backward stays on the 21-tap kernels (nqa_window_moments,
+    nqa_adists_ts_backward); "hip" runs their generic forms (the _n entry points) for every window in 3..63."""
     n = module._window()
-    if n != ops.WINDOW:
+    if n != ops.WINDOW and getattr(module, "loss_head", None) != "hip":
         raise ValueError(f"forward_target differentiates through 21-tap HIP kernels only, and this module has "
                          f"window_size={n}: for a gradient call adists(x, y) (as_loss=True), whose torch head "
-                         "differentiates any window; forward_target without a gradient works for every window")
+                         "differentiates any window, or build the module with loss_head=\"hip\", whose HIP backward takes "
+                         "every window in 3..63; forward_target without a gradient works for every window")
 
 
-def adists_target_fits(target) -> None:
+def adists_target_fits(target, window=ops.WINDOW) -> None:
     """NqaError for a target whose batch's A-DISTS scratch (_adists_y_bytes) would pass NQA_MAX_WORKSPACE_GB."""
     b, _, h, w = target.shape
-    if ops._max_pairs(lambda k: _adists_y_bytes(k, h, w), b) < b:
+    if ops._max_pairs(lambda k: _adists_y_bytes(k, h, w, window), b) < b:
         from ._lib import NqaError
-        raise NqaError(f"forward_target: {b} pairs of {h} x {w} need {_adists_y_bytes(b, h, w)} bytes of scratch beside the "
+        raise NqaError(f"forward_target: {b} pairs of {h} x {w} need {_adists_y_bytes(b, h, w, window)} bytes of scratch beside the "
                        "pyramid, more than NQA_MAX_WORKSPACE_GB allows: pass the target in slices (target[i:j])")
 
 
@@ -484,7 +497,7 @@ def adists_target_d(module, target, y, keep, kept=None):
     WHOLE: there is no slicing by NQA_MAX_WORKSPACE_GB here, and a batch whose scratch (_adists_y_bytes) would pass that
     budget is refused with NqaError -- prepare or slice the target in smaller batches.  kept: y's pyramid where the
     caller already holds it (adists_y_forward)."""
-    adists_target_fits(target)
+    adists_target_fits(target, _backward_window(module))
     return adists_y_forward(module, target.x, list(target.taps), y.detach().float().contiguous(), keep=keep, kept=kept)
 
 
@@ -713,24 +726,27 @@ class FeatsSimilarities(torch.autograd.Function):
 
 
 class WindowMoments(torch.autograd.Function):
-    """(x, y | None) -> the 21 x 21 Gaussian window means of NCHW maps (ops.window_moments: two maps of x alone, five of a
-    pair), differentiable in both: what the A-DISTS head is built from (ADISTS.py:79-86, :165-175).  Saves x and y only;
-    the backward is one launch of csrc/nqa_window_moments.hip for the sides that need a gradient, in which no window's
-    term can reach a pixel outside that window.  Gradients come back in the inputs' dtype and shape."""
+    """(x, y | None, window = 21) -> the window x window Gaussian window means of NCHW maps (ops.window_moments: two maps of
+    x alone, five of a pair), differentiable in both: what the A-DISTS head is built from (ADISTS.py:79-86, :165-175).
+    Saves x and y only; the backward is one launch of csrc/nqa_window_moments.hip (21) or csrc/nqa_window_moments_n.hip
+    (every other window in 3..63) for the sides that need a gradient, in which no window's term can reach a pixel
+    outside that window.  Gradients come back in the inputs' dtype and shape."""
 
     @staticmethod
-    def forward(ctx, x, y=None):
+    def forward(ctx, x, y=None, window=ops.WINDOW):
         fx, fy = ops._f32c(x), None if y is None else ops._f32c(y)
         ctx.save_for_backward(fx, fy)
         ctx.set_materialize_grads(False)  # an unused map's gradient stays None: its pass of the backward is skipped
         ctx.dtypes = (x.dtype, None if y is None else y.dtype)
-        return ops.window_moments(fx, fy)
+        ctx.window = ops.check_window(window)
+        return ops.window_moments(fx, fy, ctx.window)
 
     @staticmethod
     def backward(ctx, *grads):
         fx, fy = ctx.saved_tensors
         need = (ctx.needs_input_grad[0], fy is not None and ctx.needs_input_grad[1])
         if not any(need):
-            return None, None
-        gx, gy = ops.window_moments_backward(fx, fy, grads, need)
-        return (None if gx is None else gx.to(ctx.dtypes[0])), (None if gy is None else gy.to(ctx.dtypes[1]))
+            return None, None, None
+        extra = {} if ctx.window == ops.WINDOW else {"window": ctx.window}  # (the default window: the call as it always was)
+        gx, gy = ops.window_moments_backward(fx, fy, grads, need, **extra)
+        return (None if gx is None else gx.to(ctx.dtypes[0])), (None if gy is None else gy.to(ctx.dtypes[1])), None

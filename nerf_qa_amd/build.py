@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
 SOURCES = ["nqa_api.hip", "nqa_weights.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_group_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
            "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_window_moments.hip",
-           "nqa_adists_backward.hip"]
+           "nqa_window_moments_n.hip", "nqa_adists_backward.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]  # the remarks are parsed below: no hand-scheduled kernel may spill
@@ -35,7 +35,8 @@ NO_SCRATCH = ("conv3x3_igemm_kernel", "conv3x3_igemm_mixed_kernel", "conv3x3_reg
               "adists_ts_coef_kernel", "adists_ts_dot_kernel", "adists_ts_fold_kernel", "adists_ts_apply_kernel",
               "adists_ts_apply_nhwc_kernel", "adists_ts_global_kernel",
               "adists_window_n_lanes_kernel", "adists_window_n_lanes_group_kernel", "adists_window_n_planar_kernel",
-              "adists_window_n_planar_group_kernel")
+              "adists_window_n_planar_group_kernel",
+              "window_moments_n_fwd_kernel", "window_moments_n_bwd_kernel")
 
 
 def parse_resource_remarks(text: str) -> dict:
@@ -83,10 +84,12 @@ def check_no_scratch(res: dict) -> list:
 # (v_fmac_f32 with a 32-bit immediate); the SLP vectorizer would pair them into v_pk_*_f32, which issue at half
 # rate on gfx950 and need a {w, w} register pair built per tap
 # nqa_window_moments.hip: the same tap arithmetic (literal weights, one scalar FMA per tap), for the same reason
+# nqa_window_moments_n.hip: one scalar FMA per tap with the weight in a scalar register, for the same reason
 # nqa_conv_pool.hip: the fused epilogue is written as slices of a few scalar float instructions per k-step; SLP would
 # pair instructions of DIFFERENT slices (packed f32 ops, packed conversions) and drag them out of the MFMAs' shadow
 FILE_FLAGS = {"nqa_adists.hip": ["-fno-slp-vectorize"], "nqa_conv_pool.hip": ["-fno-slp-vectorize"],
-              "nqa_conv1_pool.hip": ["-fno-slp-vectorize"], "nqa_window_moments.hip": ["-fno-slp-vectorize"]}
+              "nqa_conv1_pool.hip": ["-fno-slp-vectorize"], "nqa_window_moments.hip": ["-fno-slp-vectorize"],
+              "nqa_window_moments_n.hip": ["-fno-slp-vectorize"]}
 
 
 def source_hash() -> str:

@@ -1065,6 +1065,10 @@ static int window_check(const char *who, int window) {
   return NQA_OK;
 }
 
+// the same table and the same check for the generic window-moments kernels (nqa_window_moments_n.hip)
+const float *window_taps_n(int n) { return gauss_n(n).g; }
+int window_check_n(const char *who, int window) { return window_check(who, window); }
+
 // Every host function below describes a call by three integers: X x-side images, B pairs, and K -- 0 for B independent
 // pairs (X = B, pair b reads x image b), > 0 for groups of K renders per reference (B = X * K, pair b reads x image
 // b / K).  What A-DISTS takes from x alone (entropy weights, gamma, the probability chain) is sized and launched by X,

@@ -5,7 +5,7 @@
 // With x fixed, the texture probabilities p and the channel weights w are constants; only the windowed T / S terms
 // (ADISTS.py:165-183) and F.normalize of y (:167) are differentiated (the contract is in include/nqa.h).
 //
-//   windowed stage (H, W >= 21)
+//   windowed stage (H, W >= the window: 21, or the n of the _n entry point on nqa_window_moments_n.hip's kernels)
 //     window_moments_forward          the five raw window means (nqa_window_moments.hip)
 //     adists_ts_coef_kernel           pointwise over map positions: the upstreams g1, g3, g4 of E[y], E[y^2], E[xy], written
 //                                     over those three maps
@@ -276,16 +276,16 @@ struct TsPlan {
   size_t off_sdot, off_pm, off_mom, bytes;  // byte offsets into the workspace
 };
 
-static TsPlan ts_plan(int B, int C, int H, int W) {
+static TsPlan ts_plan(int B, int C, int H, int W, int win = kWinB) {
   TsPlan t = {};
-  t.windowed = H >= kWinB && W >= kWinB;
+  t.windowed = H >= win && W >= win;
   t.P = (size_t)B * C;
   t.HW = (size_t)H * W;
   if (!t.windowed) {
     t.bytes = 16;  // (nothing is kept; 0 is the refusal)
     return t;
   }
-  t.hw = (size_t)(H - kWinB + 1) * (W - kWinB + 1);
+  t.hw = (size_t)(H - win + 1) * (W - win + 1);
   t.nblk_coef = (int)((t.hw + kCoefPerBlock - 1) / kCoefPerBlock);
   t.nblk_dot = (int)((t.HW + kDotPerBlock - 1) / kDotPerBlock);
   t.nblk_apply = (int)((t.HW + kCoefPerBlock - 1) / kCoefPerBlock);
@@ -297,20 +297,25 @@ static TsPlan ts_plan(int B, int C, int H, int W) {
 }
 
 // whether every flat grid of the stage fits a launch (P * blocks per plane under 2^31)
-bool adists_ts_backward_fits(int B, int C, int H, int W) {
-  const TsPlan t = ts_plan(B, C, H, W);
+bool adists_ts_backward_fits_n(int B, int C, int H, int W, int window) {
+  const TsPlan t = ts_plan(B, C, H, W, window);
   const size_t lim = (size_t)1 << 31;
   if (t.P >= lim) return false;
   if (!t.windowed) return true;
   return t.P * (size_t)t.nblk_apply < lim && t.P * (size_t)t.nblk_coef < lim;
 }
 
-size_t adists_ts_backward_bytes(int B, int C, int H, int W) { return ts_plan(B, C, H, W).bytes; }
+bool adists_ts_backward_fits(int B, int C, int H, int W) { return adists_ts_backward_fits_n(B, C, H, W, kWinB); }
 
-int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
-                       int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *ws, float *gy,
-                       hipStream_t st) {
-  const TsPlan t = ts_plan(B, C, H, W);
+size_t adists_ts_backward_bytes(int B, int C, int H, int W) { return ts_plan(B, C, H, W).bytes; }
+size_t adists_ts_backward_bytes_n(int B, int C, int H, int W, int window) { return ts_plan(B, C, H, W, window).bytes; }
+
+// win > 0: the stage with a window of win taps on the _n window moments (which decide the kernels of win == 21);
+// win == 0: the 21-tap kernels directly, whatever the tuning state says
+static int ts_backward(const float *x, const float *y, int B, int C, int H, int W, int win, const float *q,
+                       const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc,
+                       void *ws, float *gy, hipStream_t st) {
+  const TsPlan t = ts_plan(B, C, H, W, win ? win : kWinB);
   const int P = (int)t.P, HW = (int)t.HW;
   if (!t.windowed) {
     TimedLaunch tl(NQA_K_ADISTS, st);
@@ -321,16 +326,22 @@ int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int 
   double *part = reinterpret_cast<double *>(base), *sdot = reinterpret_cast<double *>(base + t.off_sdot);
   float *pm = reinterpret_cast<float *>(base + t.off_pm), *mom = reinterpret_cast<float *>(base + t.off_mom);
   const int hw = (int)t.hw, vec = (W & 3) == 0;
+  // the moment maps are planes of hw floats: 16-byte accesses there need hw % 4 == 0 as well, which W % 4 == 0 implies
+  // for a window of 21 (and of any n with (n - 1) % 4 == 0) and for no other
+  const int vec_m = vec && (t.hw & 3) == 0;
   int rc;
-  if ((rc = window_moments_forward(x, y, P, H, W, mom, st))) return rc;
+  if ((rc = win ? window_moments_forward_n(x, y, P, H, W, win, mom, st) : window_moments_forward(x, y, P, H, W, mom, st)))
+    return rc;
   {
     TimedLaunch tl(NQA_K_ADISTS, st);
     adists_ts_coef_kernel<<<(unsigned)(t.P * t.nblk_coef), 256, 0, st>>>(mom, B, C, hw, t.nblk_coef, q, wgt, ctot, coff, ps, u,
-                                                                         vec);
+                                                                         vec_m);
     if ((rc = check_launch("adists_ts_coef"))) return rc;
   }
   const float *const g[5] = {nullptr, mom + t.P * t.hw, nullptr, mom + 3 * t.P * t.hw, mom + 4 * t.P * t.hw};
-  if ((rc = window_moments_backward(x, y, P, H, W, g, nullptr, pm, st))) return rc;
+  if ((rc = win ? window_moments_backward_n(x, y, P, H, W, win, g, nullptr, pm, st)
+                : window_moments_backward(x, y, P, H, W, g, nullptr, pm, st)))
+    return rc;
   {
     TimedLaunch tl(NQA_K_ADISTS, st);
     adists_ts_dot_kernel<<<(unsigned)(t.P * t.nblk_dot), 256, 0, st>>>(pm, y, HW, t.nblk_dot, vec, part);
@@ -348,6 +359,18 @@ int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int 
   }
   adists_ts_apply_kernel<<<(unsigned)(t.P * t.nblk_apply), 256, 0, st>>>(pm, y, HW, t.nblk_apply, vec, sdot, mask, gy);
   return check_launch("adists_ts_apply");
+}
+
+int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
+                       int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *ws, float *gy,
+                       hipStream_t st) {
+  return ts_backward(x, y, B, C, H, W, 0, q, wgt, ctot, coff, ps, u, mask, out_nhwc, ws, gy, st);
+}
+
+int adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
+                         const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc,
+                         void *ws, float *gy, hipStream_t st) {
+  return ts_backward(x, y, B, C, H, W, window, q, wgt, ctot, coff, ps, u, mask, out_nhwc, ws, gy, st);
 }
 
 }  // namespace nqa

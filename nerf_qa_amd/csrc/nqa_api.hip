@@ -228,6 +228,10 @@ int nqa_set_conv_variant(int variant) {
   const bool window_generic = variant > 0 && (variant & 2048) != 0;  // bit 11 rides above the query value 1024
   const int asked = variant;
   if (window_generic) variant -= 2048;
+  // bit 12, for the _n window-moments entry points; counted only on top of a non-zero variant: a bare 4096 stays the
+  // unknown variant it was before the bit existed
+  const bool moments_generic = variant > 4096 && (variant & 4096) != 0;
+  if (moments_generic) variant -= 4096;
   if (variant < 0 || variant > 1023 || (variant & 3) == 3 || (variant & 768) == 768) {
     set_error("set_conv_variant: unknown variant %d", asked);
     return NQA_E_ARG;
@@ -241,6 +245,7 @@ int nqa_set_conv_variant(int variant) {
   t.fuse_stage1 = !(variant & 128);
   t.edge_grid = (variant >> 8) & 3;
   t.window_generic = window_generic;
+  t.moments_generic = moments_generic;
   return NQA_OK;
 }
 
@@ -1345,7 +1350,7 @@ int nqa_window_moments_backward(const float *x, const float *y, int P, int H, in
 
 // ---- one stage of the A-DISTS head's backward towards y (nqa_adists_backward.hip) ------------------------------------
 // The refusals that depend on sizes alone; quiet for the _bytes query.
-static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, int coff, int out_nhwc) {
+static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, int coff, int out_nhwc, int window = 21) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ctot <= 0 || coff < 0 || (long)coff + C > ctot || B > 65535) {
     if (who)
       set_error("%s: bad argument (B %d, C %d, H %d, W %d, ctot %d, coff %d: non-positive size, channels outside q, or "
@@ -1356,11 +1361,11 @@ static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, i
     if (who) set_error("%s: %d x %d: H > 2^20 or more than 2^30 pixels per plane", who, H, W);
     return NQA_E_SHAPE;
   }
-  if (!adists_ts_backward_fits(B, C, H, W)) {
+  if (!adists_ts_backward_fits_n(B, C, H, W, window)) {
     if (who) set_error("%s: %d planes of %d x %d need more than 2^31 blocks in one launch (slice the batch)", who, B * C, H, W);
     return NQA_E_SHAPE;
   }
-  if (out_nhwc && H >= 21 && W >= 21 && C % 32) {
+  if (out_nhwc && H >= window && W >= window && C % 32) {
     if (who) set_error("%s: an NHWC gradient of a windowed stage needs C %% 32 == 0, got C %d", who, C);
     return NQA_E_SHAPE;
   }
@@ -1394,6 +1399,84 @@ int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, 
   }
   return adists_ts_backward(x, y, B, C, H, W, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0, workspace, gy,
                             static_cast<hipStream_t>(stream));
+}
+
+// ---- the same four for a window of `window` taps, 3 .. 63 (nqa_window_moments_n.hip) ---------------------------------
+static int window_bad_shape_n(const char *who, int P, int H, int W, int window) {
+  if (P <= 0) {
+    set_error("%s: bad argument (P %d <= 0)", who, P);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_check_n(who, window)) return rc;
+  if (H < window || W < window) {
+    set_error("%s: %d x %d is smaller than the %d x %d window", who, H, W, window, window);
+    return NQA_E_SHAPE;
+  }
+  return 0;
+}
+
+int nqa_window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int window, float *out,
+                                 void *stream) {
+  if (!x || !out) {
+    set_error("window_moments_forward_n: bad argument (null pointer)");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_bad_shape_n("window_moments_forward_n", P, H, W, window)) return rc;
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15)) {
+    set_error("window_moments_forward_n: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_too_large("window_moments_forward_n", H, W)) return rc;
+  return window_moments_forward_n(x, y, P, H, W, window, out, static_cast<hipStream_t>(stream));
+}
+
+int nqa_window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int window, const float *g0,
+                                  const float *g1, const float *g2, const float *g3, const float *g4, float *gx, float *gy,
+                                  void *stream) {
+  if (!x || (!gx && !gy) || (!y && (g1 || g3 || g4 || gy))) {
+    set_error("window_moments_backward_n: bad argument (null pointer, no gradient to write, or y's terms given without y)");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_bad_shape_n("window_moments_backward_n", P, H, W, window)) return rc;
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)g3 |
+                      (uintptr_t)g4 | (uintptr_t)gx | (uintptr_t)gy) & 15)) {
+    set_error("window_moments_backward_n: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_too_large("window_moments_backward_n", H, W)) return rc;
+  const float *const g[5] = {g0, g1, g2, g3, g4};
+  return window_moments_backward_n(x, y, P, H, W, window, g, gx, gy, static_cast<hipStream_t>(stream));
+}
+
+size_t nqa_adists_ts_backward_bytes_n(int B, int C, int H, int W, int window) {
+  if (window < 3 || window > 63 || ts_bad_sizes(nullptr, B, C, H, W, C, 0, 0, window)) return 0;
+  return adists_ts_backward_bytes_n(B, C, H, W, window);
+}
+
+int nqa_adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
+                             const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask,
+                             int out_nhwc, void *workspace, size_t workspace_bytes, float *gy, void *stream) {
+  if (!x || !y || !q || !wgt || !ps || !u || !workspace || !gy) {
+    set_error("adists_ts_backward_n: bad argument (null pointer)");
+    return NQA_E_ARG;
+  }
+  if (int rc = window_check_n("adists_ts_backward_n", window)) return rc;
+  if (int rc = ts_bad_sizes("adists_ts_backward_n", B, C, H, W, ctot, coff, out_nhwc, window)) return rc;
+  // ps moves as 16-byte accesses only where its planes of mh x mw floats are whole 16-byte rows too (always at 21)
+  const bool rows16 = W % 4 == 0 && H >= window && W >= window;
+  const bool ps16 = rows16 && ((long)(H - window + 1) * (W - window + 1)) % 4 == 0;
+  if (((uintptr_t)workspace & 15) || (rows16 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gy) & 15)) ||
+      (ps16 && ((uintptr_t)ps & 15))) {
+    set_error("adists_ts_backward_n: the workspace, and with W %d a multiple of 4 the maps, must be 16-byte aligned", W);
+    return NQA_E_ARG;
+  }
+  const size_t need = adists_ts_backward_bytes_n(B, C, H, W, window);
+  if (workspace_bytes < need) {
+    set_error("adists_ts_backward_n: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return adists_ts_backward_n(x, y, B, C, H, W, window, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0, workspace, gy,
+                              static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -570,6 +570,9 @@ def timing_collect():
 
 
 CONV_WINDOW_GENERIC = 2048  # set_conv_variant bit: a 21-tap A-DISTS window runs on the generic window kernels too
+# set_conv_variant bit: window=21 on window_moments / window_moments_backward / adists_ts_backward runs the generic
+# window-moments kernels (csrc/nqa_window_moments_n.hip) too
+CONV_MOMENTS_GENERIC = 4096
 WINDOW_MIN, WINDOW_MAX = 3, 63  # the A-DISTS window sizes the library takes (include/nqa.h)
 
 
@@ -1305,28 +1308,33 @@ def _window_planes(x: torch.Tensor, y: torch.Tensor | None):
     return dev
 
 
-def window_moments(x: torch.Tensor, y: torch.Tensor | None = None):
-    """The 21 x 21 Gaussian window means of float32 NCHW maps (B,C,H,W), each (B,C,H-20,W-20): (E[x], E[x^2]) of x alone,
-    (E[x], E[y], E[x^2], E[y^2], E[xy]) of a pair.  One launch; the products are formed in registers."""
+def window_moments(x: torch.Tensor, y: torch.Tensor | None = None, window: int = WINDOW):
+    """The n x n Gaussian window means (n = window, 3..63; sigma n / 3, head.gauss_1d's taps) of float32 NCHW maps
+    (B,C,H,W), each (B,C,H-n+1,W-n+1): (E[x], E[x^2]) of x alone, (E[x], E[y], E[x^2], E[y^2], E[xy]) of a pair.  One
+    launch; the products are formed in registers.  21 runs the specialised kernels, every other size the generic ones."""
+    win = check_window(window)
     dev = _window_planes(x, y)
     b, c, h, w = x.shape
     n = 2 if y is None else 5
-    out = torch.empty((n, b, c, max(h - WINDOW + 1, 0), max(w - WINDOW + 1, 0)), dtype=torch.float32, device=dev)
-    _call(dev, lib().nqa_window_moments_forward, ptr(x), None if y is None else ptr(y), b * c, h, w, ptr(out), stream_ptr(dev))
+    out = torch.empty((n, b, c, max(h - win + 1, 0), max(w - win + 1, 0)), dtype=torch.float32, device=dev)
+    _call(dev, lib().nqa_window_moments_forward_n, ptr(x), None if y is None else ptr(y), b * c, h, w, win, ptr(out),
+          stream_ptr(dev))
     return out.unbind(0)
 
 
-def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequence, need=(True, True)):
-    """(gx, gy) of window_moments(x, y) for the upstream gradients `grads` of its maps (two without y, five with; None =
+def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequence, need=(True, True),
+                            window: int = WINDOW):
+    """(gx, gy) of window_moments(x, y, window) for the upstream gradients `grads` of its maps (two without y, five with; None =
     zero): gx = W^T g_x + 2 x W^T g_xx + y W^T g_xy and its mirror, every pixel summing over the windows that contain it.
     None where need[i] is False (nothing is computed for that side; the other is bit-identical) and for gy without y."""
+    win = check_window(window)
     dev = _window_planes(x, y)
     b, c, h, w = x.shape
     grads = list(grads)
     if len(grads) != (2 if y is None else 5):
         raise ValueError(f"window_moments_backward: expected {2 if y is None else 5} upstream maps, got {len(grads)}")
     g5 = [grads[0], None, grads[1], None, None] if y is None else grads
-    shape = (b, c, h - WINDOW + 1, w - WINDOW + 1)
+    shape = (b, c, h - win + 1, w - win + 1)
     for i, g in enumerate(g5):
         if g is None:
             continue
@@ -1339,7 +1347,7 @@ def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequ
         return None, None
     gx = torch.empty_like(x) if need_x else None
     gy = torch.empty_like(y) if need_y else None
-    _call(dev, lib().nqa_window_moments_backward, ptr(x), None if y is None else ptr(y), b * c, h, w,
+    _call(dev, lib().nqa_window_moments_backward_n, ptr(x), None if y is None else ptr(y), b * c, h, w, win,
           *[None if g is None else ptr(g) for g in g5], None if gx is None else ptr(gx), None if gy is None else ptr(gy),
           stream_ptr(dev))
     return gx, gy
@@ -1348,11 +1356,13 @@ def window_moments_backward(x: torch.Tensor, y: torch.Tensor | None, grads: Sequ
 # ---- one stage of the A-DISTS head's backward towards y (include/nqa.h, nqa_adists_backward.hip) ------------------
 def adists_ts_backward(x: torch.Tensor, y: torch.Tensor, q: torch.Tensor, wgt: torch.Tensor, ps: torch.Tensor,
                        u: torch.Tensor, mask: bool, coff: int = 0, nhwc: bool = False, ws: Workspace | None = None,
-                       out: torch.Tensor | None = None) -> torch.Tensor:
+                       out: torch.Tensor | None = None, window: int = WINDOW) -> torch.Tensor:
     """dL/dy of one A-DISTS stage with x fixed (include/nqa.h, nqa_adists_ts_backward): x, y float32 planar maps
     (B,C,H,W); q (8,B,ctot) and wgt (B,ctot) as adists_front leaves them, the stage's channels at columns coff .. coff+C;
     ps (B,mh,mw) the stage's ps_prod of adists_chain; u (B,) = dL/dD.  mask: times the ReLU mask (y > 0).  Returns the
-    gradient planar (B,C,H,W), or NHWC (B,H,W,C) with nhwc=True (what pyramid_backward_device takes)."""
+    gradient planar (B,C,H,W), or NHWC (B,H,W,C) with nhwc=True (what pyramid_backward_device takes).  window: the
+    stage's window size n (3..63): windowed where H, W >= n, with ps (B,H-n+1,W-n+1), else the global branch."""
+    win = check_window(window)
     dev = _need_cuda(x, y, q, wgt, ps, u)
     for t in (x, y):
         if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
@@ -1364,8 +1374,8 @@ def adists_ts_backward(x: torch.Tensor, y: torch.Tensor, q: torch.Tensor, wgt: t
     if q.dim() != 3 or q.shape[0] != 8 or q.shape[1] != b or coff < 0 or coff + c > q.shape[2]:
         raise ValueError(f"adists_ts_backward: q must be (8, {b}, ctot) with columns {coff} .. {coff + c} inside, got {tuple(q.shape)}")
     ctot = int(q.shape[2])
-    windowed = h >= WINDOW and w >= WINDOW
-    mshape = (b, h - WINDOW + 1, w - WINDOW + 1) if windowed else (b, 1, 1)
+    windowed = h >= win and w >= win
+    mshape = (b, h - win + 1, w - win + 1) if windowed else (b, 1, 1)
     for name, t, sh in (("q", q, (8, b, ctot)), ("wgt", wgt, (b, ctot)), ("ps", ps, mshape), ("u", u, (b,))):
         if tuple(t.shape) != sh or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"adists_ts_backward: {name} must be contiguous float32 {sh}, got {t.dtype} {tuple(t.shape)}")
@@ -1374,8 +1384,8 @@ def adists_ts_backward(x: torch.Tensor, y: torch.Tensor, q: torch.Tensor, wgt: t
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"adists_ts_backward: out must be contiguous float32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    nbytes = lib().nqa_adists_ts_backward_bytes(b, c, h, w)
+    nbytes = lib().nqa_adists_ts_backward_bytes_n(b, c, h, w, win)
     buf = (ws or Workspace()).get(max(nbytes, 16), dev)
-    _call(dev, lib().nqa_adists_ts_backward, ptr(x), ptr(y), b, c, h, w, ptr(q), ptr(wgt), ctot, coff, ptr(ps), ptr(u),
+    _call(dev, lib().nqa_adists_ts_backward_n, ptr(x), ptr(y), b, c, h, w, win, ptr(q), ptr(wgt), ctot, coff, ptr(ps), ptr(u),
           int(bool(mask)), int(bool(nhwc)), ptr(buf), buf.numel(), ptr(out), stream_ptr(dev))
     return out

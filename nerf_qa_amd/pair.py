@@ -129,8 +129,9 @@ def forward_target(dists_model, adists_model, target, y, batch_average=False, as
     The gradient chain runs in the two modules' grad_precision, which must be the same ("f32s" | "f16").
     ValueError for modules that name different ones, a target of a third module, one prepared before its owner's VGG
     weights changed, and a shape that does not fit; NqaError for modules with different VGG weights, tensors off the GPU, and a batch whose A-DISTS
-    scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices); ValueError too where y requires grad and the A-DISTS
-    module's window_size is not 21 (ADISTS.forward_target)."""
+    scratch would pass NQA_MAX_WORKSPACE_GB (pass target[i:j] slices); ValueError too where y requires grad, the A-DISTS
+    module's window_size is not 21 and its loss_head is not "hip" (ADISTS.forward_target): with loss_head="hip" the pair
+    step differentiates at every window in 3..63."""
     from . import autograd, target as tgt
     gp = [getattr(m, "grad_precision", "f32s") for m in (dists_model, adists_model)]
     if gp[0] != gp[1]:  # (one chain carries both metrics' gradients: the same kind of rule as pair_precision)
@@ -138,7 +139,7 @@ def forward_target(dists_model, adists_model, target, y, batch_average=False, as
                          f"grad_precision={gp[0]!r} and the A-DISTS module for {gp[1]!r}: give both the same")
     tgt.check_pair(dists_model, adists_model, target, y)
     _check_same_weights(dists_model, adists_model, y.device, "forward_target")
-    autograd.adists_target_fits(target)
+    autograd.adists_target_fits(target, autograd._backward_window(adists_model))
     if torch.is_grad_enabled() and y.requires_grad:
         autograd.check_target_window(adists_model)
         s1, s2, a = autograd.PairTargetLoss.apply(y, target, adists_model, bool(as_loss))
