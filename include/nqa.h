@@ -774,9 +774,9 @@ int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, 
                            int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *workspace,
                            size_t workspace_bytes, float *gy, void *stream);
 
-/* ---- the same four entry points for a window of `window` taps, 3 <= window <= 63, odd or even
- * (nqa_window_moments_n.hip): the normalised Gaussian of sigma window / 3 centred at window / 2 (integer division, so an
- * even window is not symmetric), the taps of nqa_adists_forward_n.  Everything above holds with 21 replaced by `window`:
+/* ---- the same four entry points for a window of `window` taps, 3 <= window <= 63, odd or even: the normalised
+ * Gaussian of sigma window / 3 centred at window / 2 (integer division, so an even window is not symmetric), the taps of
+ * nqa_adists_forward_n.  Everything above holds with 21 replaced by `window`:
  * h = H - window + 1, w = W - window + 1; a stage of nqa_adists_ts_backward_n is windowed iff H >= window && W >= window,
  * ps is (B, h, w) there and (B, 1, 1) on the global branch, which a map under the window in either direction takes.
  * Sums run in ascending tap order forwards and in ascending window order in the transposed pass, which walks the taps
@@ -784,8 +784,9 @@ int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, 
  * and the alignment rule is the one above: every pointer 16-byte aligned where W % 4 == 0 (ps of
  * nqa_adists_ts_backward_n only where mh * mw is a multiple of 4 as well: nothing else reads it in 16-byte pieces, and a
  * stage's ps inside a larger buffer need not start on a 16-byte boundary then).
- * window == 21 runs the 21-tap kernels of the entry points above, bit for bit, unless nqa_set_conv_variant carries 4096,
- * which sends it to the generic kernels too (tests, A/B runs); the entry points above never change.
+ * The entry points above ARE these four at window == 21, under their own names in the messages, with one difference:
+ * here window == 21 runs the 21-tap kernels, bit for bit, unless nqa_set_conv_variant carries 4096, which sends it to the
+ * generic kernels too (tests, A/B runs); the entry points above run the 21-tap kernels whatever the variant says.
  * Refusals are those above, on the host and before any launch, and in addition NQA_E_ARG for a window outside [3, 63]
  * (the message names the range); NQA_E_SHAPE for H or W below `window` on the two moments entry points.
  * nqa_adists_ts_backward_bytes_n is 0 for a window outside the range as for every other refused size. */

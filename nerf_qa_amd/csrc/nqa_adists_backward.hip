@@ -5,8 +5,8 @@
 // With x fixed, the texture probabilities p and the channel weights w are constants; only the windowed T / S terms
 // (ADISTS.py:165-183) and F.normalize of y (:167) are differentiated (the contract is in include/nqa.h).
 //
-//   windowed stage (H, W >= the window: 21, or the n of the _n entry point on nqa_window_moments_n.hip's kernels)
-//     window_moments_forward          the five raw window means (nqa_window_moments.hip)
+//   windowed stage (H, W >= the window n of the call, 3 .. 63; the entry point without a window passes 21)
+//     window_moments_forward          the five raw window means (nqa_window_moments_n.hip, which picks the kernels)
 //     adists_ts_coef_kernel           pointwise over map positions: the upstreams g1, g3, g4 of E[y], E[y^2], E[xy], written
 //                                     over those three maps
 //     window_moments_backward         P = W^T g1 + 2 Y W^T g3 + X W^T g4, the one-sided three-pass call
@@ -14,7 +14,7 @@
 //     adists_ts_fold_kernel           one wave per plane folds them in a fixed order: s = a_y^2 <P, Y>, 0 under the clamp
 //     adists_ts_apply_kernel          gy = P - Y s, times the ReLU mask (Y > 0); planar out, or
 //     adists_ts_apply_nhwc_kernel     the same through a 32 channel x 64 pixel LDS tile into an NHWC map
-//   global stage (a map under 21 in either direction)
+//   global stage (a map under the window in either direction)
 //     adists_ts_global_kernel         one block per plane does all of it from q's plain moments
 //
 // Everything here streams: 16-byte accesses where the rows allow them (W % 4 == 0), one writer per element, no atomics
@@ -26,7 +26,6 @@
 
 namespace nqa {
 
-static constexpr int kWinB = 21;
 static constexpr int kCoefPerBlock = 1024;  // map positions per block of the coefficient and planar apply kernels
 static constexpr int kDotPerBlock = 4096;   // plane elements per block of the dot-product partials
 static constexpr double kEps = 1e-6;        // ADISTS.py:182-183
@@ -276,7 +275,7 @@ struct TsPlan {
   size_t off_sdot, off_pm, off_mom, bytes;  // byte offsets into the workspace
 };
 
-static TsPlan ts_plan(int B, int C, int H, int W, int win = kWinB) {
+static TsPlan ts_plan(int B, int C, int H, int W, int win) {
   TsPlan t = {};
   t.windowed = H >= win && W >= win;
   t.P = (size_t)B * C;
@@ -297,7 +296,7 @@ static TsPlan ts_plan(int B, int C, int H, int W, int win = kWinB) {
 }
 
 // whether every flat grid of the stage fits a launch (P * blocks per plane under 2^31)
-bool adists_ts_backward_fits_n(int B, int C, int H, int W, int window) {
+bool adists_ts_backward_fits(int B, int C, int H, int W, int window) {
   const TsPlan t = ts_plan(B, C, H, W, window);
   const size_t lim = (size_t)1 << 31;
   if (t.P >= lim) return false;
@@ -305,17 +304,13 @@ bool adists_ts_backward_fits_n(int B, int C, int H, int W, int window) {
   return t.P * (size_t)t.nblk_apply < lim && t.P * (size_t)t.nblk_coef < lim;
 }
 
-bool adists_ts_backward_fits(int B, int C, int H, int W) { return adists_ts_backward_fits_n(B, C, H, W, kWinB); }
+size_t adists_ts_backward_bytes(int B, int C, int H, int W, int window) { return ts_plan(B, C, H, W, window).bytes; }
 
-size_t adists_ts_backward_bytes(int B, int C, int H, int W) { return ts_plan(B, C, H, W).bytes; }
-size_t adists_ts_backward_bytes_n(int B, int C, int H, int W, int window) { return ts_plan(B, C, H, W, window).bytes; }
-
-// win > 0: the stage with a window of win taps on the _n window moments (which decide the kernels of win == 21);
-// win == 0: the 21-tap kernels directly, whatever the tuning state says
-static int ts_backward(const float *x, const float *y, int B, int C, int H, int W, int win, const float *q,
-                       const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc,
-                       void *ws, float *gy, hipStream_t st) {
-  const TsPlan t = ts_plan(B, C, H, W, win ? win : kWinB);
+// `kernels` goes to the two window-moments calls, which decide what a window of 21 runs
+int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, int window, MomentsKernels kernels,
+                       const float *q, const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask,
+                       int out_nhwc, void *ws, float *gy, hipStream_t st) {
+  const TsPlan t = ts_plan(B, C, H, W, window);
   const int P = (int)t.P, HW = (int)t.HW;
   if (!t.windowed) {
     TimedLaunch tl(NQA_K_ADISTS, st);
@@ -330,8 +325,7 @@ static int ts_backward(const float *x, const float *y, int B, int C, int H, int 
   // for a window of 21 (and of any n with (n - 1) % 4 == 0) and for no other
   const int vec_m = vec && (t.hw & 3) == 0;
   int rc;
-  if ((rc = win ? window_moments_forward_n(x, y, P, H, W, win, mom, st) : window_moments_forward(x, y, P, H, W, mom, st)))
-    return rc;
+  if ((rc = window_moments_forward(x, y, P, H, W, window, kernels, mom, st))) return rc;
   {
     TimedLaunch tl(NQA_K_ADISTS, st);
     adists_ts_coef_kernel<<<(unsigned)(t.P * t.nblk_coef), 256, 0, st>>>(mom, B, C, hw, t.nblk_coef, q, wgt, ctot, coff, ps, u,
@@ -339,9 +333,7 @@ static int ts_backward(const float *x, const float *y, int B, int C, int H, int 
     if ((rc = check_launch("adists_ts_coef"))) return rc;
   }
   const float *const g[5] = {nullptr, mom + t.P * t.hw, nullptr, mom + 3 * t.P * t.hw, mom + 4 * t.P * t.hw};
-  if ((rc = win ? window_moments_backward_n(x, y, P, H, W, win, g, nullptr, pm, st)
-                : window_moments_backward(x, y, P, H, W, g, nullptr, pm, st)))
-    return rc;
+  if ((rc = window_moments_backward(x, y, P, H, W, window, kernels, g, nullptr, pm, st))) return rc;
   {
     TimedLaunch tl(NQA_K_ADISTS, st);
     adists_ts_dot_kernel<<<(unsigned)(t.P * t.nblk_dot), 256, 0, st>>>(pm, y, HW, t.nblk_dot, vec, part);
@@ -359,18 +351,6 @@ static int ts_backward(const float *x, const float *y, int B, int C, int H, int 
   }
   adists_ts_apply_kernel<<<(unsigned)(t.P * t.nblk_apply), 256, 0, st>>>(pm, y, HW, t.nblk_apply, vec, sdot, mask, gy);
   return check_launch("adists_ts_apply");
-}
-
-int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
-                       int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *ws, float *gy,
-                       hipStream_t st) {
-  return ts_backward(x, y, B, C, H, W, 0, q, wgt, ctot, coff, ps, u, mask, out_nhwc, ws, gy, st);
-}
-
-int adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
-                         const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc,
-                         void *ws, float *gy, hipStream_t st) {
-  return ts_backward(x, y, B, C, H, W, window, q, wgt, ctot, coff, ps, u, mask, out_nhwc, ws, gy, st);
 }
 
 }  // namespace nqa

@@ -1296,14 +1296,17 @@ int nqa_conv1_1_backward_scaled_half(const void *g_f16_nhwc, const void *relu1_1
                                       static_cast<hipStream_t>(stream));
 }
 
-// ---- windowed moments of the A-DISTS head (nqa_window_moments.hip) ---------------------------------------------------
-static int window_bad_shape(const char *who, int P, int H, int W) {
+// ---- windowed moments of the A-DISTS head (nqa_window_moments_n.hip, nqa_window_moments.hip) ------------------------
+// One checked implementation per operation.  Each old name is its _n form at a window of 21 under its own name `who`,
+// with MomentsKernels::Taps21 where the _n name passes Tuned; 21 cannot trip the window-range refusal.
+static int window_bad_shape(const char *who, int P, int H, int W, int window) {
   if (P <= 0) {
     set_error("%s: bad argument (P %d <= 0)", who, P);
     return NQA_E_ARG;
   }
-  if (H < 21 || W < 21) {
-    set_error("%s: %d x %d is smaller than the 21 x 21 window", who, H, W);
+  if (int rc = window_check_n(who, window)) return rc;
+  if (H < window || W < window) {
+    set_error("%s: %d x %d is smaller than the %d x %d window", who, H, W, window, window);
     return NQA_E_SHAPE;
   }
   return 0;
@@ -1317,40 +1320,62 @@ static int window_too_large(const char *who, int H, int W) {
   return 0;
 }
 
-int nqa_window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, void *stream) {
+static int moments_forward(const char *who, int window, MomentsKernels kernels, const float *x, const float *y, int P,
+                           int H, int W, float *out, void *stream) {
   if (!x || !out) {
-    set_error("window_moments_forward: bad argument (null pointer)");
+    set_error("%s: bad argument (null pointer)", who);
     return NQA_E_ARG;
   }
-  if (int rc = window_bad_shape("window_moments_forward", P, H, W)) return rc;
+  if (int rc = window_bad_shape(who, P, H, W, window)) return rc;
   if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15)) {  // (rows move as 16-byte accesses then)
-    set_error("window_moments_forward: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
+    set_error("%s: with W %d a multiple of 4 the maps must be 16-byte aligned", who, W);
     return NQA_E_ARG;
   }
-  if (int rc = window_too_large("window_moments_forward", H, W)) return rc;
-  return window_moments_forward(x, y, P, H, W, out, static_cast<hipStream_t>(stream));
+  if (int rc = window_too_large(who, H, W)) return rc;
+  return window_moments_forward(x, y, P, H, W, window, kernels, out, static_cast<hipStream_t>(stream));
+}
+
+static int moments_backward(const char *who, int window, MomentsKernels kernels, const float *x, const float *y, int P,
+                            int H, int W, const float *const (&g)[5], float *gx, float *gy, void *stream) {
+  if (!x || (!gx && !gy) || (!y && (g[1] || g[3] || g[4] || gy))) {
+    set_error("%s: bad argument (null pointer, no gradient to write, or y's terms given without y)", who);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_bad_shape(who, P, H, W, window)) return rc;
+  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g[0] | (uintptr_t)g[1] | (uintptr_t)g[2] |
+                      (uintptr_t)g[3] | (uintptr_t)g[4] | (uintptr_t)gx | (uintptr_t)gy) & 15)) {
+    set_error("%s: with W %d a multiple of 4 the maps must be 16-byte aligned", who, W);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_too_large(who, H, W)) return rc;
+  return window_moments_backward(x, y, P, H, W, window, kernels, g, gx, gy, static_cast<hipStream_t>(stream));
+}
+
+int nqa_window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, void *stream) {
+  return moments_forward("window_moments_forward", 21, MomentsKernels::Taps21, x, y, P, H, W, out, stream);
+}
+
+int nqa_window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int window, float *out,
+                                 void *stream) {
+  return moments_forward("window_moments_forward_n", window, MomentsKernels::Tuned, x, y, P, H, W, out, stream);
 }
 
 int nqa_window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *g0, const float *g1,
                                 const float *g2, const float *g3, const float *g4, float *gx, float *gy, void *stream) {
-  if (!x || (!gx && !gy) || (!y && (g1 || g3 || g4 || gy))) {
-    set_error("window_moments_backward: bad argument (null pointer, no gradient to write, or y's terms given without y)");
-    return NQA_E_ARG;
-  }
-  if (int rc = window_bad_shape("window_moments_backward", P, H, W)) return rc;
-  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)g3 |
-                      (uintptr_t)g4 | (uintptr_t)gx | (uintptr_t)gy) & 15)) {
-    set_error("window_moments_backward: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
-    return NQA_E_ARG;
-  }
-  if (int rc = window_too_large("window_moments_backward", H, W)) return rc;
-  const float *const g[5] = {g0, g1, g2, g3, g4};
-  return window_moments_backward(x, y, P, H, W, g, gx, gy, static_cast<hipStream_t>(stream));
+  return moments_backward("window_moments_backward", 21, MomentsKernels::Taps21, x, y, P, H, W, {g0, g1, g2, g3, g4}, gx,
+                          gy, stream);
+}
+
+int nqa_window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int window, const float *g0,
+                                  const float *g1, const float *g2, const float *g3, const float *g4, float *gx, float *gy,
+                                  void *stream) {
+  return moments_backward("window_moments_backward_n", window, MomentsKernels::Tuned, x, y, P, H, W, {g0, g1, g2, g3, g4},
+                          gx, gy, stream);
 }
 
 // ---- one stage of the A-DISTS head's backward towards y (nqa_adists_backward.hip) ------------------------------------
-// The refusals that depend on sizes alone; quiet for the _bytes query.
-static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, int coff, int out_nhwc, int window = 21) {
+// The refusals that depend on sizes alone; quiet (who null) for the _bytes query.
+static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, int coff, int out_nhwc, int window) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ctot <= 0 || coff < 0 || (long)coff + C > ctot || B > 65535) {
     if (who)
       set_error("%s: bad argument (B %d, C %d, H %d, W %d, ctot %d, coff %d: non-positive size, channels outside q, or "
@@ -1361,7 +1386,7 @@ static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, i
     if (who) set_error("%s: %d x %d: H > 2^20 or more than 2^30 pixels per plane", who, H, W);
     return NQA_E_SHAPE;
   }
-  if (!adists_ts_backward_fits_n(B, C, H, W, window)) {
+  if (!adists_ts_backward_fits(B, C, H, W, window)) {
     if (who) set_error("%s: %d planes of %d x %d need more than 2^31 blocks in one launch (slice the batch)", who, B * C, H, W);
     return NQA_E_SHAPE;
   }
@@ -1372,111 +1397,56 @@ static int ts_bad_sizes(const char *who, int B, int C, int H, int W, int ctot, i
   return 0;
 }
 
-size_t nqa_adists_ts_backward_bytes(int B, int C, int H, int W) {
-  if (ts_bad_sizes(nullptr, B, C, H, W, C, 0, 0)) return 0;
-  return adists_ts_backward_bytes(B, C, H, W);
+static size_t ts_backward_bytes(int window, int B, int C, int H, int W) {
+  if (window < 3 || window > 63 || ts_bad_sizes(nullptr, B, C, H, W, C, 0, 0, window)) return 0;
+  return adists_ts_backward_bytes(B, C, H, W, window);
+}
+
+static int ts_backward(const char *who, int window, MomentsKernels kernels, const float *x, const float *y, int B, int C,
+                       int H, int W, const float *q, const float *wgt, int ctot, int coff, const float *ps, const float *u,
+                       int mask, int out_nhwc, void *workspace, size_t workspace_bytes, float *gy, void *stream) {
+  if (!x || !y || !q || !wgt || !ps || !u || !workspace || !gy) {
+    set_error("%s: bad argument (null pointer)", who);
+    return NQA_E_ARG;
+  }
+  if (int rc = window_check_n(who, window)) return rc;
+  if (int rc = ts_bad_sizes(who, B, C, H, W, ctot, coff, out_nhwc, window)) return rc;
+  // the windowed stage runs the planar window-moments kernels and inherits their rule; ps moves as 16-byte accesses
+  // only where its planes of mh x mw floats are whole 16-byte rows too (always at 21); the workspace holds doubles
+  const bool rows16 = W % 4 == 0 && H >= window && W >= window;
+  const bool ps16 = rows16 && ((long)(H - window + 1) * (W - window + 1)) % 4 == 0;
+  if (((uintptr_t)workspace & 15) || (rows16 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gy) & 15)) ||
+      (ps16 && ((uintptr_t)ps & 15))) {
+    set_error("%s: the workspace, and with W %d a multiple of 4 the maps, must be 16-byte aligned", who, W);
+    return NQA_E_ARG;
+  }
+  const size_t need = adists_ts_backward_bytes(B, C, H, W, window);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    return NQA_E_WORKSPACE;
+  }
+  return adists_ts_backward(x, y, B, C, H, W, window, kernels, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0,
+                            workspace, gy, static_cast<hipStream_t>(stream));
+}
+
+size_t nqa_adists_ts_backward_bytes(int B, int C, int H, int W) { return ts_backward_bytes(21, B, C, H, W); }
+
+size_t nqa_adists_ts_backward_bytes_n(int B, int C, int H, int W, int window) {
+  return ts_backward_bytes(window, B, C, H, W);
 }
 
 int nqa_adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
                            int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *workspace,
                            size_t workspace_bytes, float *gy, void *stream) {
-  if (!x || !y || !q || !wgt || !ps || !u || !workspace || !gy) {
-    set_error("adists_ts_backward: bad argument (null pointer)");
-    return NQA_E_ARG;
-  }
-  if (int rc = ts_bad_sizes("adists_ts_backward", B, C, H, W, ctot, coff, out_nhwc)) return rc;
-  // the windowed stage runs the planar window-moments kernels and inherits their rule; the workspace holds doubles
-  const bool rows16 = W % 4 == 0 && H >= 21 && W >= 21;
-  if (((uintptr_t)workspace & 15) ||
-      (rows16 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ps | (uintptr_t)gy) & 15))) {
-    set_error("adists_ts_backward: the workspace, and with W %d a multiple of 4 the maps, must be 16-byte aligned", W);
-    return NQA_E_ARG;
-  }
-  const size_t need = adists_ts_backward_bytes(B, C, H, W);
-  if (workspace_bytes < need) {
-    set_error("adists_ts_backward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    return NQA_E_WORKSPACE;
-  }
-  return adists_ts_backward(x, y, B, C, H, W, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0, workspace, gy,
-                            static_cast<hipStream_t>(stream));
-}
-
-// ---- the same four for a window of `window` taps, 3 .. 63 (nqa_window_moments_n.hip) ---------------------------------
-static int window_bad_shape_n(const char *who, int P, int H, int W, int window) {
-  if (P <= 0) {
-    set_error("%s: bad argument (P %d <= 0)", who, P);
-    return NQA_E_ARG;
-  }
-  if (int rc = window_check_n(who, window)) return rc;
-  if (H < window || W < window) {
-    set_error("%s: %d x %d is smaller than the %d x %d window", who, H, W, window, window);
-    return NQA_E_SHAPE;
-  }
-  return 0;
-}
-
-int nqa_window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int window, float *out,
-                                 void *stream) {
-  if (!x || !out) {
-    set_error("window_moments_forward_n: bad argument (null pointer)");
-    return NQA_E_ARG;
-  }
-  if (int rc = window_bad_shape_n("window_moments_forward_n", P, H, W, window)) return rc;
-  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15)) {
-    set_error("window_moments_forward_n: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
-    return NQA_E_ARG;
-  }
-  if (int rc = window_too_large("window_moments_forward_n", H, W)) return rc;
-  return window_moments_forward_n(x, y, P, H, W, window, out, static_cast<hipStream_t>(stream));
-}
-
-int nqa_window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int window, const float *g0,
-                                  const float *g1, const float *g2, const float *g3, const float *g4, float *gx, float *gy,
-                                  void *stream) {
-  if (!x || (!gx && !gy) || (!y && (g1 || g3 || g4 || gy))) {
-    set_error("window_moments_backward_n: bad argument (null pointer, no gradient to write, or y's terms given without y)");
-    return NQA_E_ARG;
-  }
-  if (int rc = window_bad_shape_n("window_moments_backward_n", P, H, W, window)) return rc;
-  if (W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)g0 | (uintptr_t)g1 | (uintptr_t)g2 | (uintptr_t)g3 |
-                      (uintptr_t)g4 | (uintptr_t)gx | (uintptr_t)gy) & 15)) {
-    set_error("window_moments_backward_n: with W %d a multiple of 4 the maps must be 16-byte aligned", W);
-    return NQA_E_ARG;
-  }
-  if (int rc = window_too_large("window_moments_backward_n", H, W)) return rc;
-  const float *const g[5] = {g0, g1, g2, g3, g4};
-  return window_moments_backward_n(x, y, P, H, W, window, g, gx, gy, static_cast<hipStream_t>(stream));
-}
-
-size_t nqa_adists_ts_backward_bytes_n(int B, int C, int H, int W, int window) {
-  if (window < 3 || window > 63 || ts_bad_sizes(nullptr, B, C, H, W, C, 0, 0, window)) return 0;
-  return adists_ts_backward_bytes_n(B, C, H, W, window);
+  return ts_backward("adists_ts_backward", 21, MomentsKernels::Taps21, x, y, B, C, H, W, q, wgt, ctot, coff, ps, u, mask,
+                     out_nhwc, workspace, workspace_bytes, gy, stream);
 }
 
 int nqa_adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
                              const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask,
                              int out_nhwc, void *workspace, size_t workspace_bytes, float *gy, void *stream) {
-  if (!x || !y || !q || !wgt || !ps || !u || !workspace || !gy) {
-    set_error("adists_ts_backward_n: bad argument (null pointer)");
-    return NQA_E_ARG;
-  }
-  if (int rc = window_check_n("adists_ts_backward_n", window)) return rc;
-  if (int rc = ts_bad_sizes("adists_ts_backward_n", B, C, H, W, ctot, coff, out_nhwc, window)) return rc;
-  // ps moves as 16-byte accesses only where its planes of mh x mw floats are whole 16-byte rows too (always at 21)
-  const bool rows16 = W % 4 == 0 && H >= window && W >= window;
-  const bool ps16 = rows16 && ((long)(H - window + 1) * (W - window + 1)) % 4 == 0;
-  if (((uintptr_t)workspace & 15) || (rows16 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gy) & 15)) ||
-      (ps16 && ((uintptr_t)ps & 15))) {
-    set_error("adists_ts_backward_n: the workspace, and with W %d a multiple of 4 the maps, must be 16-byte aligned", W);
-    return NQA_E_ARG;
-  }
-  const size_t need = adists_ts_backward_bytes_n(B, C, H, W, window);
-  if (workspace_bytes < need) {
-    set_error("adists_ts_backward_n: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    return NQA_E_WORKSPACE;
-  }
-  return adists_ts_backward_n(x, y, B, C, H, W, window, q, wgt, ctot, coff, ps, u, mask != 0, out_nhwc != 0, workspace, gy,
-                              static_cast<hipStream_t>(stream));
+  return ts_backward("adists_ts_backward_n", window, MomentsKernels::Tuned, x, y, B, C, H, W, q, wgt, ctot, coff, ps, u,
+                     mask, out_nhwc, workspace, workspace_bytes, gy, stream);
 }
 
 }  // extern "C"

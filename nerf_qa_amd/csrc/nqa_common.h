@@ -299,8 +299,8 @@ struct Tuning {
   // edge) where it saves a round of blocks, 1 = plain grids only, 2 = mixed on every such map (tests, at small sizes)
   int edge_grid = 0;
   bool window_generic = false;  // bit 11: a window of 21 runs the generic window kernels (nqa_window_n.h) as well
-  // bit 12: a window of 21 on the _n window-moments / stage-backward entry points runs the generic kernels
-  // (nqa_window_moments_n.hip) as well
+  // bit 12: a window of 21 under MomentsKernels::Tuned (the _n window-moments / stage-backward entry points) runs the
+  // generic kernels (nqa_window_moments_n.hip) as well
   bool moments_generic = false;
   int mixed_launches = 0;  // mixed grids this thread has launched since it last asked (variant 1024)
 };
@@ -357,33 +357,30 @@ int loss_stats_grad_y_add(const float *tx, const float *ty, int B, int HW, int C
                           const float *g_s2, long g_stride, double *coef, float *gy, hipStream_t st);
 int grad_exponent_nblk(long per_image);
 int grad_exponent(const float *g, int n, long per_image, unsigned *ws, int *kexp, int *ktot, hipStream_t st);
-// ---- windowed moments of the A-DISTS head and their backward (nqa_window_moments.hip) ----
-// out: moment m of plane p at (m * P + p) * h * w (five moments with y, two without); g[q] null = zero
-int window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st);
-int window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
-                            float *gy, hipStream_t st);
-// the same for a window of n taps, 3 <= n <= 63 (nqa_window_moments_n.hip): h = H - n + 1, w = W - n + 1.  n == 21 runs
-// the two functions above unless Tuning::moments_generic is set.  window_taps_n: gaussian(n, n / 3), the generic scoring
-// kernels' table (nqa_adists.hip); window_check_n: NQA_E_ARG naming the range for a window outside it.
+// ---- windowed moments of the A-DISTS head and their backward (nqa_window_moments_n.hip, nqa_window_moments.hip) ----
+// Which kernels a window of 21 runs (every other window has the generic ones alone).  Tuned: the 21-tap kernels unless
+// Tuning::moments_generic is set, what the _n entry points pass; Taps21: the 21-tap kernels whatever the tuning state
+// says, what the entry points without a window pass.
+enum class MomentsKernels { Tuned, Taps21 };
+// a window of n taps, 3 <= n <= 63: h = H - n + 1, w = W - n + 1.  out: moment m of plane p at (m * P + p) * h * w (five
+// moments with y, two without); g[q] null = zero
+int window_moments_forward(const float *x, const float *y, int P, int H, int W, int n, MomentsKernels kernels, float *out,
+                           hipStream_t st);
+int window_moments_backward(const float *x, const float *y, int P, int H, int W, int n, MomentsKernels kernels,
+                            const float *const g[5], float *gx, float *gy, hipStream_t st);
+// window_taps_n: gaussian(n, n / 3), the generic scoring kernels' table (nqa_adists.hip); window_check_n: NQA_E_ARG
+// naming the range for a window outside it.
 const float *window_taps_n(int n);
 int window_check_n(const char *who, int window);
-int window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int n, float *out, hipStream_t st);
-int window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int n, const float *const g[5],
-                              float *gx, float *gy, hipStream_t st);
 // ---- one stage of the A-DISTS head's backward towards y (nqa_adists_backward.hip) ----
-// planar float maps (B, C, H, W); q [8][B][ctot] and wgt [B][ctot] with the stage's channels at coff; ps (B, mh, mw);
-// u (B) = dL/dD; gy planar, or NHWC (B, H, W, C) with out_nhwc (C % 32 == 0 on a windowed stage)
-bool adists_ts_backward_fits(int B, int C, int H, int W);
-size_t adists_ts_backward_bytes(int B, int C, int H, int W);
-int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, const float *q, const float *wgt,
-                       int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc, void *ws, float *gy,
-                       hipStream_t st);
-// the same with a window of `window` taps (3 .. 63) in place of 21, on the _n window moments
-bool adists_ts_backward_fits_n(int B, int C, int H, int W, int window);
-size_t adists_ts_backward_bytes_n(int B, int C, int H, int W, int window);
-int adists_ts_backward_n(const float *x, const float *y, int B, int C, int H, int W, int window, const float *q,
-                         const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask, int out_nhwc,
-                         void *ws, float *gy, hipStream_t st);
+// planar float maps (B, C, H, W); a window of `window` taps (3 .. 63) on the window moments above; q [8][B][ctot] and
+// wgt [B][ctot] with the stage's channels at coff; ps (B, mh, mw); u (B) = dL/dD; gy planar, or NHWC (B, H, W, C) with
+// out_nhwc (C % 32 == 0 on a windowed stage)
+bool adists_ts_backward_fits(int B, int C, int H, int W, int window);
+size_t adists_ts_backward_bytes(int B, int C, int H, int W, int window);
+int adists_ts_backward(const float *x, const float *y, int B, int C, int H, int W, int window, MomentsKernels kernels,
+                       const float *q, const float *wgt, int ctot, int coff, const float *ps, const float *u, int mask,
+                       int out_nhwc, void *ws, float *gy, hipStream_t st);
 int conv3x3_split_generic(const void *in, int n, int H, int W, int cin, int cout, const void *blob, size_t bias_off,
                           int relu, void *out, hipStream_t st);
 int l2pool_to_split16(const void *in_f16, int n, int H, int W, int C, void *out_split16, hipStream_t st);

@@ -1,5 +1,7 @@
 // Windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments) for gfx950:
-// the 21 x 21 Gaussian window means E[x], E[y], E[x^2], E[y^2], E[xy] of float NCHW maps, and their backward.
+// the 21 x 21 Gaussian window means E[x], E[y], E[x^2], E[y^2], E[xy] of float NCHW maps, and their backward.  These are
+// the kernels specialised for 21 taps and their two launchers; window_moments_forward / _backward
+// (nqa_window_moments_n.hip) decide when a call runs them.
 //
 //   window_moments_fwd_kernel   one launch reads x (and y) once and writes the two (five) maps of window means; the
 //                               products are formed in registers
@@ -23,7 +25,7 @@
 // (gx or gy null) costs nothing, and the other side's instructions do not depend on it: it is bit-identical.
 #include <math.h>
 
-#include "nqa_common.h"
+#include "nqa_window_moments.h"
 
 namespace nqa {
 
@@ -110,17 +112,6 @@ __device__ inline void horizontal_item(const float *V, int row, int col4, float 
 #pragma unroll
     for (int k = 1; k < kWin; ++k) a = fmaf(kG[k], v[e + k], a);
     out[e] = a;
-  }
-}
-
-// 4 floats of one row: a 16-byte store where the row allows it, else the elements that are inside
-__device__ inline void store4(float *row, int c, int nc, bool vec, const float (&v)[4]) {
-  if (vec) {
-    if (c < nc) *reinterpret_cast<f32x4 *>(row + c) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c + e < nc) row[c + e] = v[e];
   }
 }
 
@@ -266,35 +257,22 @@ static bool window_gauss_ok(const char *who) {
   return !bad;
 }
 
-static constexpr int kMaxGridZ = 65535;
-
-int window_moments_forward(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st) {
+int window_moments_forward_21(const float *x, const float *y, int P, int H, int W, float *out, hipStream_t st) {
   if (!window_gauss_ok("window_moments_forward")) return NQA_E_LAUNCH;
   const int h = H - (kWin - 1), w = W - (kWin - 1);
-  for (int p0 = 0; p0 < P; p0 += kMaxGridZ) {
-    const dim3 grid(cdiv(w, kTW), cdiv(h, kTH), P - p0 < kMaxGridZ ? P - p0 : kMaxGridZ);
-    TimedLaunch t(NQA_K_ADISTS, st);
+  return launch_plane_chunks("window_moments_fwd", P, cdiv(w, kTW), cdiv(h, kTH), st, [&](dim3 grid, int p0) {
     if (y) window_moments_fwd_kernel<true><<<grid, 256, 0, st>>>(x, y, H, W, P, p0, out);
     else window_moments_fwd_kernel<false><<<grid, 256, 0, st>>>(x, nullptr, H, W, P, p0, out);
-    if (int rc = check_launch("window_moments_fwd")) return rc;
-  }
-  return 0;
+  });
 }
 
-int window_moments_backward(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
-                            float *gy, hipStream_t st) {
+int window_moments_backward_21(const float *x, const float *y, int P, int H, int W, const float *const g[5], float *gx,
+                               float *gy, hipStream_t st) {
   if (!window_gauss_ok("window_moments_backward")) return NQA_E_LAUNCH;
-  WindowGrads wg;
-  for (int q = 0; q < 5; ++q) wg.g[q] = g[q];
-  if (!gx) wg.g[0] = wg.g[2] = nullptr;
-  if (!gy) wg.g[1] = wg.g[3] = nullptr;
-  for (int p0 = 0; p0 < P; p0 += kMaxGridZ) {
-    const dim3 grid(cdiv(W, kTW), cdiv(H, kTH), P - p0 < kMaxGridZ ? P - p0 : kMaxGridZ);
-    TimedLaunch t(NQA_K_ADISTS, st);
+  const WindowGrads wg = wanted_grads<WindowGrads>(g, gx, gy);
+  return launch_plane_chunks("window_moments_bwd", P, cdiv(W, kTW), cdiv(H, kTH), st, [&](dim3 grid, int p0) {
     window_moments_bwd_kernel<<<grid, 256, 0, st>>>(x, y, H, W, p0, wg, gx, gy);
-    if (int rc = check_launch("window_moments_bwd")) return rc;
-  }
-  return 0;
+  });
 }
 
 }  // namespace nqa

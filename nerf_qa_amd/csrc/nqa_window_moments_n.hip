@@ -1,5 +1,7 @@
 // Windowed moments of the A-DISTS head and their backward for a RUN-TIME window size n (3 <= n <= 63, odd or even):
-// the generic form of nqa_window_moments.hip's two kernels, with their contract (include/nqa.h).
+// the generic form of nqa_window_moments.hip's two kernels, with their contract (include/nqa.h).  The host side of both
+// families ends here: window_moments_forward / _backward take the window and a MomentsKernels, and runs_generic() below
+// is the one place that sends a call to these kernels or to the 21-tap ones.
 //
 //   window_moments_n_fwd_kernel   the two (five) maps of n x n Gaussian window means of x (and y), h = H - n + 1,
 //                                 w = W - n + 1; the products x^2, y^2, xy are formed in registers on the way into LDS
@@ -30,7 +32,7 @@
 // ones do (W % 4 == 0).
 #include <math.h>
 
-#include "nqa_common.h"
+#include "nqa_window_moments.h"
 
 namespace nqa {
 
@@ -157,16 +159,6 @@ __device__ __forceinline__ void horizontal_item_n(const TapsN &gw, int n, const 
       out);
 }
 
-__device__ inline void store4_n(float *row, int c, int nc, bool vec, const float (&v)[4]) {
-  if (vec) {
-    if (c < nc) *reinterpret_cast<f32x4 *>(row + c) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (c + e < nc) row[c + e] = v[e];
-  }
-}
-
 // grid (cdiv(w, 64), cdiv(h, TH), planes), tile_floats_n(n) floats of dynamic LDS.  out: moment m of plane p at
 // ((m * P + p) * h * w); P: planes of the whole call, p0: the first plane of this launch.  PAIR: five moments of (x, y);
 // else E[x], E[x^2] of x.
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(256) void window_moments_n_fwd_kernel(const float *
       if (it < th * (kNTW / 4) && oy0 + row < h && ox0 + col4 < w) {
         float r[4];
         horizontal_item_n(gw, n, V + row * iws + col4, r);
-        store4_n(o + (size_t)(oy0 + row) * w, ox0 + col4, w, vec_out, r);
+        store4(o + (size_t)(oy0 + row) * w, ox0 + col4, w, vec_out, r);
       }
     }
     // (the next moment's stage writes the tile, which nobody reads any more; its barrier precedes the next write of V)
@@ -282,16 +274,14 @@ __global__ __launch_bounds__(256) void window_moments_n_bwd_kernel(const float *
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     if (!live[u]) continue;
-    if (gx) store4_n(gx + at[u], col[u], W, vec_in, ax[u]);
-    if (gy) store4_n(gy + at[u], col[u], W, vec_in, ay[u]);
+    if (gx) store4(gx + at[u], col[u], W, vec_in, ax[u]);
+    if (gy) store4(gy + at[u], col[u], W, vec_in, ay[u]);
   }
 }
 
 // ---------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------
-static constexpr int kMaxGridZN = 65535;
-
 static TapsN taps_n(int n, bool reversed) {
   TapsN t = {};
   const float *g = window_taps_n(n);
@@ -299,41 +289,35 @@ static TapsN taps_n(int n, bool reversed) {
   return t;
 }
 
-// whether a call of the _n entry points with this window runs the generic kernels (else the 21-tap ones)
-static bool moments_generic(int n) { return n != 21 || tuning().moments_generic; }
+// THE choice between the two kernel families, for both directions and, through them, the stage backward: every window
+// but 21 has the generic kernels alone; 21 runs the 21-tap ones unless the caller leaves it to a tuning state that asks
+// for the generic ones.
+static bool runs_generic(int n, MomentsKernels kernels) {
+  return n != 21 || (kernels == MomentsKernels::Tuned && tuning().moments_generic);
+}
 
-int window_moments_forward_n(const float *x, const float *y, int P, int H, int W, int n, float *out, hipStream_t st) {
-  if (!moments_generic(n)) return window_moments_forward(x, y, P, H, W, out, st);
+int window_moments_forward(const float *x, const float *y, int P, int H, int W, int n, MomentsKernels kernels, float *out,
+                           hipStream_t st) {
+  if (!runs_generic(n, kernels)) return window_moments_forward_21(x, y, P, H, W, out, st);
   const int h = H - (n - 1), w = W - (n - 1), th = tile_rows_n(n);
   const size_t lds = (size_t)tile_floats_n(n) * sizeof(float);
   const TapsN gw = taps_n(n, false);
-  for (int p0 = 0; p0 < P; p0 += kMaxGridZN) {
-    const dim3 grid(cdiv(w, kNTW), cdiv(h, th), P - p0 < kMaxGridZN ? P - p0 : kMaxGridZN);
-    TimedLaunch t(NQA_K_ADISTS, st);
+  return launch_plane_chunks("window_moments_n_fwd", P, cdiv(w, kNTW), cdiv(h, th), st, [&](dim3 grid, int p0) {
     if (y) window_moments_n_fwd_kernel<true><<<grid, 256, lds, st>>>(x, y, H, W, P, p0, gw, n, out);
     else window_moments_n_fwd_kernel<false><<<grid, 256, lds, st>>>(x, nullptr, H, W, P, p0, gw, n, out);
-    if (int rc = check_launch("window_moments_n_fwd")) return rc;
-  }
-  return 0;
+  });
 }
 
-int window_moments_backward_n(const float *x, const float *y, int P, int H, int W, int n, const float *const g[5],
-                              float *gx, float *gy, hipStream_t st) {
-  if (!moments_generic(n)) return window_moments_backward(x, y, P, H, W, g, gx, gy, st);
-  WindowGradsN wg;
-  for (int q = 0; q < 5; ++q) wg.g[q] = g[q];
-  if (!gx) wg.g[0] = wg.g[2] = nullptr;
-  if (!gy) wg.g[1] = wg.g[3] = nullptr;
-  const int th = tile_rows_n(n);
+int window_moments_backward(const float *x, const float *y, int P, int H, int W, int n, MomentsKernels kernels,
+                            const float *const g[5], float *gx, float *gy, hipStream_t st) {
+  if (!runs_generic(n, kernels)) return window_moments_backward_21(x, y, P, H, W, g, gx, gy, st);
+  const WindowGradsN wg = wanted_grads<WindowGradsN>(g, gx, gy);
   const size_t lds = (size_t)tile_floats_n(n) * sizeof(float);
   const TapsN gw = taps_n(n, true);
-  for (int p0 = 0; p0 < P; p0 += kMaxGridZN) {
-    const dim3 grid(cdiv(W, kNTW), cdiv(H, th), P - p0 < kMaxGridZN ? P - p0 : kMaxGridZN);
-    TimedLaunch t(NQA_K_ADISTS, st);
+  const int th = tile_rows_n(n);
+  return launch_plane_chunks("window_moments_n_bwd", P, cdiv(W, kNTW), cdiv(H, th), st, [&](dim3 grid, int p0) {
     window_moments_n_bwd_kernel<<<grid, 256, lds, st>>>(x, y, H, W, p0, wg, gw, n, gx, gy);
-    if (int rc = check_launch("window_moments_n_bwd")) return rc;
-  }
-  return 0;
+  });
 }
 
 }  // namespace nqa

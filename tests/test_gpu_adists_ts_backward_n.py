@@ -183,3 +183,33 @@ def test_window_21_is_the_21_tap_stage_and_bit_4096_stays_inside_the_bound(dev):
         em, er = gr.errors(got, g64)
         print(f"\nstage n=21 {name}: max {em:.3e} rms {er:.3e}; bound max {gr.bound(ym):.3e} rms {gr.bound(yr):.3e}")
         assert em <= gr.bound(ym) and er <= gr.bound(yr)
+
+
+def test_the_old_stage_entry_point_ignores_bit_4096(dev):
+    """nqa_adists_ts_backward (no window argument) keeps the 21-tap window-moments kernels whatever the bit says: equal
+    bits with and without it, and the bits of ops.adists_ts_backward(window=21) without it.  1 x 64 x 30 x 44 is the
+    smallest windowed stage on the 16-byte path (10 x 24 windows)."""
+    import poison
+    from nerf_qa_amd import ops
+    b, c, h, w = 1, 64, 30, 44
+    gen = torch.Generator().manual_seed(79)
+    X, Y = relu_maps((b, c, h, w), gen), relu_maps((b, c, h, w), gen)
+    p, u = torch.rand((b, h - 20, w - 20), generator=gen), torch.tensor([-1.0])
+    wgt = (torch.rand((b, c), generator=gen) + 0.5) / 1475
+    args = [t.to(dev).contiguous() for t in (X, Y, stage_q(X, Y), wgt, p, u)]
+    xd, yd, qd, wd, pd, ud = args
+
+    def old():
+        out = R.Fenced((b, c, h, w), dev)
+        buf = poison.PoisonWorkspace(0xFF).get(ops.lib().nqa_adists_ts_backward_bytes(b, c, h, w), dev)
+        ops._call(dev, ops.lib().nqa_adists_ts_backward, ops.ptr(xd), ops.ptr(yd), b, c, h, w, ops.ptr(qd), ops.ptr(wd), c, 0,
+                  ops.ptr(pd), ops.ptr(ud), 1, 0, ops.ptr(buf), buf.numel(), ops.ptr(out.view), ops.stream_ptr(dev))
+        return out.check("old stage backward").clone()
+    try:
+        ops.set_conv_variant(ops.DEFAULT_CONV_VARIANT | ops.CONV_MOMENTS_GENERIC)
+        with_bit = old()
+    finally:
+        ops.set_conv_variant(ops.DEFAULT_CONV_VARIANT)
+    without = old()
+    assert torch.equal(with_bit, without)
+    assert torch.equal(without, _run(args, dev, (b, c, h, w), False, mask=True, window=21))
