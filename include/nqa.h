@@ -715,6 +715,76 @@ int nqa_dists_stats_nhwc_grad_y_add(const float *tx_nhwc, const float *ty_nhwc, 
                                     const void *partials, size_t partials_bytes, const float *g_s1, const float *g_s2,
                                     long g_stride, void *coef, size_t coef_bytes, float *gy_inout, void *stream);
 
+/* ---- the prepared-target loss step of DISTS as TWO calls (nqa_loss_step.hip; DISTS(target_step="c"),
+ * nerf_qa_amd/autograd.py DistsTargetStep): everything autograd.dists_target_forward and dists_target_backward enqueue
+ * launch by launch -- the single operators and loss-path entry points above, about a hundred of them a step -- driven by
+ * host code in the library on ONE caller-owned state block.  The same launches on the same operands, in the same order
+ * and on the same grids: s1, s2 and gy are that path's bit for bit on both gradient rungs, and every launch keeps its
+ * timing class (the few element-wise kernels that stand where that path has a torch expression count as NQA_K_PREP).
+ * Neither call allocates, synchronises or reads anything back to the host; a caller without Python has the whole loss
+ * with nqa_dists_score and nqa_dists_score_backward around them (INTEGRATION.md section 2 shows the sequence).
+ *
+ *   grad_prec  the rung of the gradient chain: NQA_PREC_F32S (split16 operands, float results, nqa_pack_conv_split
+ *              layers) or NQA_PREC_F16 (half maps, nqa_pack_conv_half layers).  The forward is the same on both; the state
+ *              is sized by the rung, so both calls and nqa_dists_target_step_bytes take the same value.
+ *   x_nchw     dev float32 NCHW (B,3,H,W), the target's frames;  x_taps: host array of five dev pointers, the target's
+ *              float NHWC taps relu1_2 .. relu5_3, tap k + 1 (B, Hk, Wk, Ck) with Hk = ceil(H / 2^k): what the forward
+ *              below leaves as y's taps, or nqa_vgg_pyramid in NQA_PREC_F32S, computed once for a whole optimisation.
+ *   y_nchw     dev float32 NCHW (B,3,H,W), the frames the gradient is taken of.
+ *   packed_w   the NQA_PREC_F32S blob of nqa_pack_vgg_weights, on the device.
+ *   s1, s2     dev float32 (B, 1475), written by the forward;  g_s1, g_s2: dev float32 (B, 1475), dL/dS1 and dL/dS2.
+ *   grad_layers  host array of twelve dev pointers: entry l - 1 is conv layer l's data-gradient layer, W'[ci][co][ky][kx]
+ *              = W[co][ci][2-ky][2-kx] (a 3x3 layer of cout = the layer's cin, cin = the layer's cout), packed by the
+ *              rung's packer.   w0_oihw_dev: conv1_1's float32 OIHW weights (64,3,3,3) on the device.
+ *   gy_nchw    dev float32 NCHW (B,3,H,W): dL/dy.
+ *   state      dev, nqa_dists_target_step_bytes(B, H, W, grad_prec) bytes, 256-byte aligned.  Laid out in regions on
+ *              multiples of 256 bytes, in this order.  KEPT -- written by the forward, only READ by the backward, so a
+ *              second backward on the same state gives the same bits: the thirteen activations of y (layer 0..12, NHWC,
+ *              4 bytes per element; the tapped layers 1, 3, 6, 9, 12 are y's float taps, the others split16), the five
+ *              taps' fp64 partials (nqa_dists_stats_target_bytes each), tap 0's fp64 sums (nqa_stats_scratch_bytes of the
+ *              image beside five one-pixel maps) and those maps' B zero floats.  SCRATCH behind it, one area the two
+ *              calls lay out each in its own way: the forward's four L2-pooled maps and the (B, 8) similarities of tap
+ *              0, dead when it returns; the backward's five tap gradients, tap 0's image term and (B, 8) upstream, the
+ *              fp64 coefficient records, the chain's exponents and their reduction partials, and three chain buffers of
+ *              the largest layer map.  Every byte a call reads it or the forward has written before: no result depends
+ *              on what the state held.  The backward must follow a forward with the same x, x_taps, y, B, H, W and
+ *              grad_prec on the same state (it cannot check that without reading the device), on the same stream or
+ *              ordered behind it; forward and backward may run on different host threads.
+ * nqa_dists_target_step_forward   conv1_1, conv layers 1..12 and the four L2-pools of y in NQA_PREC_F32S, every
+ *              activation kept; per tap 1..5 nqa_dists_stats_target (sums, fold) against x_taps; tap 0 through
+ *              nqa_dists_stats_nchw with the five one-pixel zero maps, its three columns copied into s1 / s2.
+ * nqa_dists_target_step_backward  per tap 1..5 nqa_dists_stats_nhwc_backward_from (coefficients, gradient, y side) from
+ *              the kept partials; tap 0's nqa_dists_stats_nchw_backward from its kept sums; then the chain: the exponent
+ *              of the top tap gradient, and per layer 12..1 mask, data-gradient convolution, the pool seam where the layer
+ *              read an L2-pool, exponent (nqa_grad_exponent / nqa_relu_mask_split16_scaled / nqa_conv3x3_split /
+ *              nqa_l2pool_backward_scaled, or their _half / f16 forms); nqa_conv1_1_backward_scaled with relu1_1's mask
+ *              and 2^-k_total folded in; one float add of tap 0's image term into gy.
+ * All arguments are checked on the host before the first launch, in this order, and a refused call enqueues nothing:
+ *   NQA_E_ARG        a null pointer (each of the five taps and twelve layers included); B, H or W <= 0 or B > 65535; a
+ *                    grad_prec that is neither rung;
+ *   NQA_E_SHAPE      a frame whose map at some layer reaches 2^31 bytes (H * W * 64 floats at stage 1: the layers' 32-bit
+ *                    in-image offsets), or B * H * W * 64 > 2^36 elements (slice the batch);
+ *   NQA_E_ARG        a misaligned buffer: the state on 256 bytes, the five taps, packed_w and the twelve layers on 16,
+ *                    every float array (x, y, s1, s2, g_s1, g_s2, w0, gy) on 4;
+ *   NQA_E_WORKSPACE  a state under nqa_dists_target_step_bytes.
+ * nqa_dists_target_step_bytes returns 0 for what the first two rules refuse.
+ *
+ * nqa_dists_score_backward   the derivative of nqa_dists_score (DISTS_pt.py:123-148) towards S1 and S2: g_s1[b][c] =
+ *              -g_score[b] * alpha[c] / w, g_s2[b][c] = -g_score[b] * beta[c] / w, w = sum(alpha) + sum(beta) summed in
+ *              fp64 as nqa_dists_score sums it and rounded to float; one float quotient, one float product.  alpha, beta
+ *              dev float32 (1475), g_score dev float32 (B), g_s1 / g_s2 dev float32 (B, 1475).  NQA_E_ARG for a null
+ *              pointer, B <= 0 or an array that is not 4-byte aligned.  One launch (NQA_K_PREP). */
+size_t nqa_dists_target_step_bytes(int B, int H, int W, int grad_prec);
+int nqa_dists_target_step_forward(const float *x_nchw, const void *const *x_taps, const float *y_nchw, int B, int H, int W,
+                                  const void *packed_w, int grad_prec, void *state, size_t state_bytes, float *s1, float *s2,
+                                  void *stream);
+int nqa_dists_target_step_backward(const float *x_nchw, const void *const *x_taps, const float *y_nchw, int B, int H, int W,
+                                   const float *g_s1, const float *g_s2, const void *const *grad_layers,
+                                   const float *w0_oihw_dev, int grad_prec, void *state, size_t state_bytes, float *gy_nchw,
+                                   void *stream);
+int nqa_dists_score_backward(const float *alpha, const float *beta, const float *g_score, int B, float *g_s1, float *g_s2,
+                             void *stream);
+
 /* ---- windowed moments of the A-DISTS head under autograd (nerf_qa_amd/ADISTS/head.py, autograd.WindowMoments;
  * nqa_window_moments.hip).  x, y: dev float NCHW maps taken as P = B * C independent planes of H x W; the window is the
  * normalised 21-tap Gaussian of sigma 7 as an outer product, valid correlation: h = H - 20, w = W - 20.

@@ -73,6 +73,21 @@ def resolve_grad_precision(grad_precision=None) -> str:
     if v not in GRAD_PRECISIONS:
         raise ValueError(f"grad_precision must be one of {GRAD_PRECISIONS}, got {v!r}")
     return v
+
+
+# How forward_target(require_grad=True) issues its step: "python" (the default: autograd.DistsTargetSimilarities, about a
+# hundred library calls from nerf_qa_amd/autograd.py) or "c" (autograd.DistsTargetStep: the library's two step calls,
+# nqa_dists_target_step_forward / _backward, on one state tensor -- the same launches, the same bits, less host time).
+DEFAULT_TARGET_STEP = "python"
+TARGET_STEPS = ("python", "c")
+
+
+def resolve_target_step(target_step=None) -> str:
+    """The argument, else $NQA_TARGET_STEP, else "python"; ValueError for anything but "python" / "c"."""
+    v = target_step or os.environ.get("NQA_TARGET_STEP") or DEFAULT_TARGET_STEP
+    if v not in TARGET_STEPS:
+        raise ValueError(f"target_step must be one of {TARGET_STEPS}, got {v!r}")
+    return v
 AUTO_MIN_PIXELS = 128 * 128
 AUTO_F16_BUDGET = 6e-5  # on max |score_mode - score_f32s| over the calibration pairs ...
 AUTO_TAIL = 4.2         # ... and then only if max / rms looks like noise (384 Gaussian samples: 3.2 +- 0.3), not outliers;
@@ -277,9 +292,11 @@ def _build_stages(convs):
 
 
 class DISTS(torch.nn.Module):
-    def __init__(self, load_weights=True, from_feats=False, precision=None, vgg16_path=None, grad_precision=None):
+    def __init__(self, load_weights=True, from_feats=False, precision=None, vgg16_path=None, grad_precision=None,
+                 target_step=None):
         super().__init__()
         self.grad_precision = resolve_grad_precision(grad_precision)  # (refused before anything is loaded)
+        self.target_step = resolve_target_step(target_step)
         convs, self.vgg_source = load_vgg16_convs(vgg16_path)
         self.stage1, self.stage2, self.stage3, self.stage4, self.stage5 = _build_stages(convs)
         for param in self.parameters():
@@ -523,6 +540,7 @@ class DISTS(torch.nn.Module):
         d = self.__dict__
         d.setdefault("precision", os.environ.get("NQA_PRECISION", DEFAULT_PRECISION))
         d.setdefault("grad_precision", DEFAULT_GRAD_PRECISION)  # (a module pickled before the keyword existed)
+        d.setdefault("target_step", DEFAULT_TARGET_STEP)        # (likewise)
         d.setdefault("vgg_source", "unpickled module (Conv2d weights of stage1..5)")
         d["_packed"], d["_ws"], d["_auto"], d["_deltas"], d["_agreed"] = {}, ops.Workspace(), None, {}, {}
         d["_guard_streams"] = {}
@@ -621,13 +639,18 @@ class DISTS(torch.nn.Module):
         chain (autograd.DistsTargetSimilarities) -- nothing of x runs, nothing is computed twice, nothing is read back
         to the host -- and y.grad is forward's own bit for bit.  Otherwise y gives its taps and nothing is kept.  The
         forward always runs in f32s; the backward chain in the module's grad_precision ("f32s", or "f16": half gradient
-        maps, the same values).  alpha / beta get their gradients as in forward.  ValueError for
+        maps, the same values).  alpha / beta get their gradients as in forward.  A module built with target_step="c"
+        runs that step as the library's two step calls on one state tensor (autograd.DistsTargetStep): the same launches
+        and the same bits; the target is used whole, and a state beyond NQA_MAX_WORKSPACE_GB is an NqaError naming
+        target[i:j].  ValueError for
         a target of another module, one prepared before the VGG weights changed, and a shape that does not fit;
         NqaError for tensors off the GPU."""
         from .. import autograd, target as tgt
         tgt.check(self, target, y, "DISTS")
         if require_grad and torch.is_grad_enabled() and y.requires_grad:
-            s1, s2 = autograd.DistsTargetSimilarities.apply(y, target, self)
+            step = (autograd.DistsTargetStep if getattr(self, "target_step", DEFAULT_TARGET_STEP) == "c"
+                    else autograd.DistsTargetSimilarities)
+            s1, s2 = step.apply(y, target, self)
         else:
             s1, s2 = autograd.dists_target_similarities(self, target, y)
         return self._weighted(s1, s2, batch_average)

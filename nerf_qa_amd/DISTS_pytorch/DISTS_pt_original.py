@@ -23,8 +23,9 @@ from .DISTS_pt import prepare_image as _prepare_image
 
 
 class DISTS(_BaseDISTS):
-    def __init__(self, load_weights=True, precision=None, vgg16_path=None, grad_precision=None):
-        super().__init__(load_weights=False, precision=precision, vgg16_path=vgg16_path, grad_precision=grad_precision)
+    def __init__(self, load_weights=True, precision=None, vgg16_path=None, grad_precision=None, target_step=None):
+        super().__init__(load_weights=False, precision=precision, vgg16_path=vgg16_path, grad_precision=grad_precision,
+                         target_step=target_step)
         if load_weights:
             ab = np.load(_DATA)
             alpha = torch.from_numpy(ab["alpha"]).view(1, -1, 1, 1).clone()

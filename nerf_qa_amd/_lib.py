@@ -125,6 +125,11 @@ _SIGNATURES = {
     "nqa_dists_stats_nhwc_backward_from": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp,
                                                 _vp]),
     "nqa_dists_stats_nhwc_grad_y_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp]),
+    "nqa_dists_target_step_bytes": (_sz, [_i, _i, _i, _i]),
+    "nqa_dists_target_step_forward": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "nqa_dists_target_step_backward": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _vp, _vp, C.POINTER(_vp), _vp, _i, _vp,
+                                            _sz, _vp, _vp]),
+    "nqa_dists_score_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "nqa_grad_exponent_bytes": (_sz, [_i, C.c_long]),
     "nqa_grad_exponent": (_i, [_vp, _i, C.c_long, _vp, _sz, _vp, _vp, _vp]),
     "nqa_relu_mask_split16_scaled": (_i, [_vp, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),

@@ -27,6 +27,8 @@ losses run one kept pyramid of y per step and nothing of x: DistsTargetSimilarit
 from its forward and starts the backward from them, AdistsTargetLoss runs adists_backward_y's two halves in its forward
 and its backward.  PairTargetLoss is the two together for a loss that sums both metrics (nerf_qa_amd/pair.py,
 forward_target): one kept pyramid serves both heads, and the sum of their tap gradients goes down one chain.
+DistsTargetStep (DISTS(target_step="c")) is DistsTargetSimilarities with both halves issued by the library: two calls on
+one state tensor (csrc/nqa_loss_step.hip), the same launches in the same order, the same bits.
 
 One walk each way: _pyramid_forward (pyramid_keep keeps all of it, pyramid_taps the five taps) and pyramid_backward_device,
 whose rung of grad_precision is a record of _RUNGS (packer, exponent, mask, data-gradient convolution).  _target_backward
@@ -631,6 +633,51 @@ class DistsTargetSimilarities(torch.autograd.Function):
             return None, None, None
         ctx.saved_tensors  # (y itself is in the state; this is autograd's check that it was not changed in place since)
         return dists_target_backward(ctx.module, ctx.target, ctx.state, g1, g2).to(ctx.dtype), None, None
+
+
+def dists_target_step_state(module, target):
+    """An uninitialised state tensor (uint8) for one step of DistsTargetStep on `target` in the module's gradient rung.  A
+    target is used WHOLE: NqaError where the state would pass NQA_MAX_WORKSPACE_GB or the step does not take the shape."""
+    from ._lib import NqaError
+    b, _, h, w = target.shape
+    rung = _grad_precision(module)
+    nbytes = ops.dists_target_step_bytes(b, h, w, rung)
+    if not nbytes:
+        raise NqaError(f"forward_target (target_step='c'): {b} pairs of {h} x {w} are more than one step takes: "
+                       + ops.lib().nqa_last_error().decode())
+    if ops._max_pairs(lambda k: ops.dists_target_step_bytes(k, h, w, rung), b) < b:
+        raise NqaError(f"forward_target (target_step='c'): {b} pairs of {h} x {w} need a state of {nbytes} bytes, more than "
+                       "NQA_MAX_WORKSPACE_GB allows: pass the target in slices (target[i:j])")
+    return torch.empty(nbytes, dtype=torch.uint8, device=target.device)
+
+
+class DistsTargetStep(torch.autograd.Function):
+    """DistsTargetSimilarities as the library's two step calls (DISTS(target_step="c"); include/nqa.h, "the prepared-target
+    loss step"): forward = nqa_dists_target_step_forward, backward = nqa_dists_target_step_backward, both on ONE state
+    tensor that the Function keeps -- the launches of dists_target_forward / dists_target_backward in their order, issued
+    by the library instead of from here, so (S1, S2) and dL/dy are that Function's bit for bit.  The kept part of the
+    state is only read by the backward: a second backward (retain_graph=True) gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, y, target, module):
+        yf = y.detach().float().contiguous()
+        rung = _grad_precision(module)
+        state = dists_target_step_state(module, target)
+        s1, s2 = ops.dists_target_step_forward(target.x, target.taps, yf, module._packed_weights(yf.device, "f32s"), rung,
+                                               state)
+        ctx.module, ctx.target, ctx.state, ctx.rung, ctx.dtype = module, target, state, rung, y.dtype
+        ctx.save_for_backward(yf)
+        return s1, s2
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (yf,) = ctx.saved_tensors
+        blobs, w0 = _backward_blobs(ctx.module, yf.device, ctx.rung)
+        t = ctx.target
+        gy = ops.dists_target_step_backward(t.x, t.taps, yf, g1, g2, blobs, w0, ctx.rung, ctx.state)
+        return gy.to(ctx.dtype), None, None
 
 
 def pair_target_values(adists_module, target, y):

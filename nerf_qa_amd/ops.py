@@ -1175,6 +1175,68 @@ def dists_stats_nhwc_grad_y_add(tx: torch.Tensor, ty: torch.Tensor, part: torch.
     return gy
 
 
+# ---- the prepared-target loss step as two library calls (include/nqa.h, "the prepared-target loss step"; nqa_loss_step.hip) ----
+GRAD_PREC_ID = {"f32s": _lib.PREC_F32S, "f16": _lib.PREC_F16}  # the rungs of the gradient chain as the step calls name them
+
+
+def dists_target_step_bytes(b: int, h: int, w: int, grad_precision: str = "f32s") -> int:
+    """Bytes of the state block of one step for b pairs of h x w frames on the rung grad_precision; 0 for a shape the
+    step does not take (no device is touched)."""
+    return int(lib().nqa_dists_target_step_bytes(int(b), int(h), int(w), GRAD_PREC_ID[grad_precision]))
+
+
+def _step_args(who: str, x: torch.Tensor, x_taps: Sequence[torch.Tensor], y: torch.Tensor, state: torch.Tensor):
+    dev = _need_cuda(x, y, state, *x_taps)
+    assert len(x_taps) == 5 and all(t.dtype == torch.float32 and t.is_contiguous() for t in x_taps), who
+    assert x.dtype == y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape, who
+    assert state.dtype == torch.uint8 and state.is_contiguous(), who
+    b, _, h, w = x.shape
+    return dev, b, h, w, (C.c_void_p * 5)(*[ptr(t) for t in x_taps])
+
+
+def dists_target_step_forward(x: torch.Tensor, x_taps: Sequence[torch.Tensor], y: torch.Tensor, packed: torch.Tensor,
+                              grad_precision: str, state: torch.Tensor, s1: torch.Tensor | None = None,
+                              s2: torch.Tensor | None = None):
+    """(S1, S2), each float32 (B, 1475), of a prepared target (x, its five float NHWC taps) against y, with everything a
+    gradient needs left in `state` (uint8, at least dists_target_step_bytes): ONE library call.  packed: the f32s blob."""
+    dev, b, h, w, tp = _step_args("dists_target_step_forward", x, x_taps, y, state)
+    _need_cuda(packed)
+    s1 = _out_or_empty(s1, (b, TOTAL_CHNS), torch.float32, dev)
+    s2 = _out_or_empty(s2, (b, TOTAL_CHNS), torch.float32, dev)
+    _call(dev, lib().nqa_dists_target_step_forward, ptr(x), tp, ptr(y), b, h, w, ptr(packed), GRAD_PREC_ID[grad_precision],
+          ptr(state), state.numel(), ptr(s1), ptr(s2), stream_ptr(dev))
+    return s1, s2
+
+
+def dists_target_step_backward(x: torch.Tensor, x_taps: Sequence[torch.Tensor], y: torch.Tensor, g_s1: torch.Tensor,
+                               g_s2: torch.Tensor, blobs, w0: torch.Tensor, grad_precision: str, state: torch.Tensor,
+                               gy: torch.Tensor | None = None) -> torch.Tensor:
+    """dL/dy, float32 (B,3,H,W), given dL/dS1, dL/dS2 (B, 1475) from the state dists_target_step_forward left for the same
+    arguments: ONE library call.  blobs: {layer 1..12: its data-gradient layer packed for the rung}; w0: conv1_1's float
+    OIHW weights on the device."""
+    dev, b, h, w, tp = _step_args("dists_target_step_backward", x, x_taps, y, state)
+    _need_cuda(g_s1, g_s2, w0, *[blobs[l] for l in range(1, 13)])
+    g_s1, g_s2, w0 = _f32c(g_s1), _f32c(g_s2), _f32c(w0)
+    assert tuple(g_s1.shape) == tuple(g_s2.shape) == (b, TOTAL_CHNS) and tuple(w0.shape) == (64, 3, 3, 3)
+    gy = _out_or_empty(gy, (b, 3, h, w), torch.float32, dev)
+    lp = (C.c_void_p * 12)(*[ptr(blobs[l]) for l in range(1, 13)])
+    _call(dev, lib().nqa_dists_target_step_backward, ptr(x), tp, ptr(y), b, h, w, ptr(g_s1), ptr(g_s2), lp, ptr(w0),
+          GRAD_PREC_ID[grad_precision], ptr(state), state.numel(), ptr(gy), stream_ptr(dev))
+    return gy
+
+
+def dists_score_backward(alpha: torch.Tensor, beta: torch.Tensor, g_score: torch.Tensor):
+    """(dL/dS1, dL/dS2), each float32 (B, 1475), of dists_score for dL/dscore = g_score (B,): -g_score[b] * alpha[c] / w and
+    -g_score[b] * beta[c] / w with w = sum(alpha) + sum(beta) (no autograd; the library's kernel)."""
+    dev = _need_cuda(alpha, beta, g_score)
+    a, b_, g = _f32c(alpha.detach().reshape(-1)), _f32c(beta.detach().reshape(-1)), _f32c(g_score.detach().reshape(-1))
+    assert a.numel() == b_.numel() == TOTAL_CHNS
+    g1 = torch.empty((g.numel(), TOTAL_CHNS), dtype=torch.float32, device=dev)
+    g2 = torch.empty_like(g1)
+    _call(dev, lib().nqa_dists_score_backward, ptr(a), ptr(b_), ptr(g), g.numel(), ptr(g1), ptr(g2), stream_ptr(dev))
+    return g1, g2
+
+
 def _exponent_args(who: str, g: torch.Tensor, k: torch.Tensor, k_total: torch.Tensor | None):
     """What grad_exponent and grad_exponent_half check and allocate alike: g contiguous, k and k_total int32 with one
     entry per image g[i] -> (device, images, elements per image, the reduction's scratch, k_total's pointer or None)."""

@@ -17,9 +17,11 @@ pairs in the same process, with the time of prepare_target itself.
 
 --grad-precision f16 (with --target) builds the module with grad_precision="f16": the same steps with the half gradient
 chain, to be set beside a run without it; --shape HxWxB (with --target) runs that one shape, so that every shape can have a
-process of its own.
+process of its own; --step c (with --target) builds the module with target_step="c", whose target step is the library's
+two step calls on one state tensor (autograd.DistsTargetStep) instead of the launches issued from autograd.py: the same
+report, to be set beside a run without it (profiles/target_step_c.txt).
 
-Usage: python tools/gpu_loss_step_bench.py [OUT] [--target [--grad-precision f16] [--shape HxWxB]]  -- prints the report,
+Usage: python tools/gpu_loss_step_bench.py [OUT] [--target [--grad-precision f16] [--shape HxWxB] [--step c]]  -- prints the report,
 and also writes it to OUT when given (profiles/loss_step_bench.txt holds such reports; a --target report is APPENDED to OUT)."""
 import os; os.environ.setdefault("NQA_VGG16_WEIGHTS", "synth:1234")  # dev tool: stand-in weights, asked for explicitly
 import subprocess
@@ -124,15 +126,17 @@ def target_report(model, dev, say, shapes=SHAPES):
 
 def main():
     flags = sys.argv[1:]
-    valued = {flags[i + 1] for i, a in enumerate(flags[:-1]) if a in ("--grad-precision", "--shape")}
+    valued = {flags[i + 1] for i, a in enumerate(flags[:-1]) if a in ("--grad-precision", "--shape", "--step")}
     args = [a for a in flags if not a.startswith("--") and a not in valued]
     with_target = "--target" in flags
     grad_precision = flags[flags.index("--grad-precision") + 1] if "--grad-precision" in flags else None
     shapes = (tuple(int(v) for v in flags[flags.index("--shape") + 1].split("x")),) if "--shape" in flags else SHAPES
+    target_step = flags[flags.index("--step") + 1] if "--step" in flags else None
     dev = torch.device("cuda:0")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        model = DISTS(precision="f32s", **({"grad_precision": grad_precision} if grad_precision else {})).to(dev).eval()
+        model = DISTS(precision="f32s", **({"grad_precision": grad_precision} if grad_precision else {}),
+                      **({"target_step": target_step} if target_step else {})).to(dev).eval()
     lines = [f"# tools/gpu_loss_step_bench.py  ({torch.cuda.get_device_name(dev)}; torch {torch.__version__}; commit {commit()}; "
              f"HIP sources {build.source_hash()})",
              f"# forward + backward of DISTS(x, y, require_grad=True, batch_average=True), precision f32s, stand-in weights;",
@@ -145,7 +149,8 @@ def main():
 
     if with_target:
         lines[1] = ("# --target: DISTS(x, y, require_grad=True, batch_average=True) with x fixed against forward_target on a "
-                    f"prepared target, precision f32s, gradient chain {model.grad_precision}, stand-in weights;")
+                    f"prepared target, precision f32s, gradient chain {model.grad_precision}, target step issued from "
+                    f"{'the library (two calls)' if model.target_step == 'c' else 'Python'}, stand-in weights;")
         target_report(model, dev, say, shapes)
     for h, w, b in () if with_target else SHAPES:
         xn, yn = synth.frame_batch(list(range(100, 100 + b)), h, w)
