@@ -833,7 +833,10 @@ int nqa_window_moments_backward(const float *x, const float *y, int P, int H, in
  * P(r) = (g1 + 2 y(r) g3 + x(r) g4) / (H W).  One writer per element, no atomics: bitwise repeatable; no pair reads
  * another pair's numbers; nothing is read back to the host.  Launches are counted as NQA_K_ADISTS.
  * Workspace: nqa_adists_ts_backward_bytes(B, C, H, W) (0 for sizes that are refused): the five moment maps, P and the
- * fp64 partials; 16-byte aligned.
+ * fp64 partials; 16-byte aligned.  The regions lie in this order, each rounded up to 16 bytes, and all of them are still
+ * there when the call returns: the partials (P * ceil(H W / 4096) doubles, plane-major, P = B * C), s = a_y^2 <P, y> (P
+ * doubles), P (P * H W floats), the five moment maps (moment m of plane p at ((m * P + p) * mh * mw) floats; g1, g3, g4
+ * have replaced moments 1, 3, 4); the global branch keeps nothing in its 16 bytes (tests/ts_backward_refs.py, layout).
  * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, coff < 0 or coff + C > ctot, more
  * than 65535 pairs, a misaligned workspace, or -- on a windowed stage with W % 4 == 0, where rows move as 16-byte
  * accesses -- x, y, ps or gy not 16-byte aligned; NQA_E_SHAPE H > 2^20, more than 2^30 pixels per plane, more than 2^31
