@@ -19,6 +19,9 @@
  *     and the tuning choice of nqa_set_conv_variant) plus idempotent per-device caches (kernel
  *     attributes, CU count), so calls are re-entrant per (thread, stream): one thread's tuning
  *     or timing never changes or observes another thread's launches.
+ *   - the Python shell PARSES this file for its signatures and constants (nerf_qa_amd/_lib.py), so declarations stay
+ *     plain C: int / long / size_t / double / float and pointers, every parameter named, no structs, no function
+ *     pointers, no varargs, no conditional blocks; what the parser does not understand it refuses at import.
  *
  * Layouts
  *   - images enter as the reference's tensors: float32 NCHW, values in [0,1];

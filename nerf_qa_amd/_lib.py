@@ -1,23 +1,132 @@
-"""ctypes binding of libnqa_hip.so (include/nqa.h).
+"""ctypes binding of libnqa_hip.so, read from include/nqa.h.
 
 The library is the product: if it is missing or does not load, importing this module's
 `lib()` raises.  There is no CPU or eager-PyTorch fallback anywhere in nerf_qa_amd.
+
+The header is the only statement of the ABI: `_SIGNATURES` and the constants below are parsed from it when this
+module is imported (`parse_header`), by these rules, and whatever they do not cover is refused with an NqaError that
+names the declaration -- the parser never guesses:
+  - comments go first, then preprocessor lines (a trailing backslash continues one).  `#define NQA_X v` with an integer
+    v is a constant; function-like macros and the includes are skipped; the include guard and the `#ifdef __cplusplus`
+    blocks (dropped whole, this is the C reading) are the only conditionals allowed;
+  - `enum { NQA_X = v, ... };` blocks give constants, every enumerator with its own integer value;
+  - every other statement is a declaration `ret nqa_name(params);`, which may span lines;
+  - a parameter containing `*` or `[` is a pointer: c_void_p, host or device alike (the header cannot tell them apart;
+    c_void_p takes ctypes arrays, pointers, byref(), integers and None);
+  - any other parameter is `[const] type name` with type one of int, long, size_t, double, float;
+  - the return type is one of those five, or `const char *`: c_char_p;
+  - a struct, union or enum type, a function pointer, `...`, an unnamed parameter, any other type: refused.
+tests/test_cpu_abi_from_header.py holds this reading to the compiler's own.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  (loads the HIP runtime the library binds to; must come first)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NQA_LIB") or os.path.join(_HERE, "libnqa_hip.so")  # NQA_LIB: development builds only
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nqa.h"))
 
-PREC_F32, PREC_BF16, PREC_F16, PREC_F32S, PREC_F32M, PREC_F32M2, PREC_F32M4, PREC_F16W = 0, 1, 2, 3, 4, 5, 6, 7
+
+class NqaError(RuntimeError):
+    pass
+
+
+_SCALARS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "double": C.c_double, "float": C.c_float}
+_NOT_A_NAME = set(_SCALARS) | {"unsigned", "signed", "short", "char", "void", "const"}
+
+
+def _int(text: str, what: str) -> int:
+    try:
+        return int(text.strip(), 0)
+    except ValueError:
+        raise NqaError(f"nqa.h: {what}: {text.strip()!r} is not an integer literal") from None
+
+
+def _scalar(words: str, decl: str):
+    """`[const] type [name]` without the name -> ctypes type."""
+    names = [w for w in words.split() if w != "const"]
+    if len(names) != 1 or names[0] not in _SCALARS:
+        raise NqaError(f"nqa.h: type {words.strip()!r} is not one the binding knows, in `{decl}`")
+    return _SCALARS[names[0]]
+
+
+def parse_header(text: str):
+    """The text of nqa.h -> ({name: (restype, [argtypes])}, {NQA_X: value}), by the module docstring's rules."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text).replace("\\\n", " ")
+    consts, code, in_cxx = {}, [], False
+    for line in text.splitlines():
+        if not line.lstrip().startswith("#"):
+            if not in_cxx:
+                code.append(line)
+            continue
+        word = line.replace("#", " ", 1).split() or [""]
+        if word[0] == "endif":  # closes the guard or a __cplusplus block: every other conditional is refused below
+            in_cxx = False
+        elif word[:2] == ["ifdef", "__cplusplus"]:
+            in_cxx = True
+        elif word[0] in ("if", "ifdef", "ifndef", "else", "elif") and word[:2] != ["ifndef", "NQA_H"]:
+            raise NqaError(f"nqa.h: conditional `{line.strip()}`: the binding reads every declaration unconditionally")
+        elif word[0] == "define" and len(word) > 2 and re.fullmatch(r"NQA_\w+", word[1]):
+            consts[word[1]] = _int(" ".join(word[2:]), f"#define {word[1]}")
+    code = " ".join(" ".join(code).split())
+
+    def enum(m):
+        for item in m.group(1).split(","):
+            name, eq, value = item.partition("=")
+            if not eq or not re.fullmatch(r"NQA_\w+", name.strip()):
+                raise NqaError(f"nqa.h: enumerator `{item.strip()}` is not `NQA_X = value`")
+            consts[name.strip()] = _int(value, f"enumerator {name.strip()}")
+        return " "
+    code = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, code)
+
+    sigs = {}
+    for decl in filter(None, (d.strip() for d in code.split(";"))):
+        m = re.fullmatch(r"([\w\s\*]+?)\b(nqa_\w+)\s*\(([^()]*)\)", decl)
+        if not m or re.search(r"\b(struct|union|enum)\b", decl) or "..." in decl:
+            raise NqaError(f"nqa.h: `{decl}` is not a plain C declaration `ret nqa_name(params)` the binding can read")
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if name in sigs:
+            raise NqaError(f"nqa.h: {name} is declared twice")
+        restype = C.c_char_p if ret.split() == ["const", "char", "*"] else _scalar(ret, decl)
+        argtypes = []
+        for p in ([] if params == "void" else params.split(",")):
+            if "*" in p or "[" in p:
+                argtypes.append(C.c_void_p)
+                continue
+            typ, _, pname = p.strip().rpartition(" ")
+            if pname in _NOT_A_NAME or not re.fullmatch(r"[A-Za-z_]\w*", pname):
+                raise NqaError(f"nqa.h: parameter `{p.strip()}` of `{decl}` has no name")
+            argtypes.append(_scalar(typ, decl))
+        sigs[name] = (restype, argtypes)
+    return sigs, consts
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            sigs, consts = parse_header(f.read())
+        if not sigs:
+            raise NqaError("nqa.h: no declaration found")
+    except (OSError, NqaError) as e:
+        raise NqaError(f"{HEADER_PATH}: the C ABI is read from this header and it cannot be: {e}") from None
+    return sigs, consts
+
+
+_SIGNATURES, CONSTANTS = _read_header()
+EXPORTS = tuple(_SIGNATURES)
+
+(PREC_F32, PREC_BF16, PREC_F16, PREC_F32S, PREC_F32M, PREC_F32M2, PREC_F32M4, PREC_F16W) = (
+    CONSTANTS["NQA_PREC_" + n] for n in ("F32", "BF16", "F16", "F32S", "F32M", "F32M2", "F32M4", "F16W"))
 PREC_NAMES = {"f32": PREC_F32, "fp32": PREC_F32, "bf16": PREC_BF16, "f16": PREC_F16, "fp16": PREC_F16,
               "f32s": PREC_F32S, "f32m": PREC_F32M, "f32m2": PREC_F32M2, "f32m4": PREC_F32M4, "f16w": PREC_F16W}
 PREC_DTYPE = {PREC_F32: torch.float32, PREC_BF16: torch.bfloat16, PREC_F16: torch.float16, PREC_F32S: torch.float32}
-# NQA_MIXED_STAGES: the mixed modes run their first pyramid stages as f16 kernels on two-term weights, the rest as f32s
+# NQA_MIXED_STAGES (a function-like macro, restated; the tests hold it to the compiler's): the mixed modes run their
+# first pyramid stages as f16 kernels on two-term weights, the rest as f32s
 MIXED_STAGES = {PREC_F32M: 3, PREC_F32M2: 2, PREC_F32M4: 4, PREC_F16W: 5}
 
 
@@ -26,142 +135,11 @@ def stage_prec(prec: int, stage: int) -> int:
     if prec not in MIXED_STAGES:
         return prec
     return PREC_F16 if stage < MIXED_STAGES[prec] else PREC_F32S
-NUM_CONVS, NUM_TAPS, TOTAL_CHNS = 13, 6, 1475
+NUM_CONVS, NUM_TAPS, TOTAL_CHNS = CONSTANTS["NQA_NUM_CONVS"], CONSTANTS["NQA_NUM_TAPS"], CONSTANTS["NQA_TOTAL_CHNS"]
 K_NAMES = ("conv1_1", "conv_igemm", "l2pool", "stats", "adists", "prep", "pool_seam")
-
-_vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
-_SIGNATURES = {
-    "nqa_version": (_i, []),
-    "nqa_last_error": (C.c_char_p, []),
-    "nqa_packed_weights_bytes": (_sz, [_i]),
-    "nqa_pack_vgg_weights": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, _vp]),
-    "nqa_conv1_1": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "nqa_conv1_fused": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "nqa_conv3x3_relu": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "nqa_l2pool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_l2pool_f16_to_split16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_nhwc_to_nchw_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_split16_encode": (_i, [_vp, C.c_long, _i, _vp, _vp]),
-    "nqa_split16_decode": (_i, [_vp, C.c_long, _i, _vp, _vp]),
-    "nqa_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_vgg_pyramid": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, C.POINTER(_vp), _vp]),
-    "nqa_dists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_dists_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_dists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_dists_group_stats_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "nqa_dists_group_stats": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_dists_group_sums": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "nqa_dists_group_stats_grid": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
-    "nqa_pool_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_stats_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_pool_stats_grid": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
-    "nqa_stats_nhwc_grid": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
-    "nqa_pool_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "nqa_pool_stats_f16_to_split16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "nqa_stats_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "nqa_stats_scratch_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
-    "nqa_dists_stats_nchw": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
-                                  _vp, _sz, _vp, _vp, _vp]),
-    "nqa_stats_backward_bytes": (_sz, [_i, C.POINTER(_i)]),
-    "nqa_dists_stats_nchw_backward": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i),
-                                           C.POINTER(_i), _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp),
-                                           _vp]),
-    "nqa_dists_score": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "nqa_conv_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_dists_fused_taps": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
-    "nqa_conv_pool_stats": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "nqa_conv1_pool_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "nqa_adists_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_adists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp]),
-    "nqa_adists_forward_map": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_adists_dists_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "nqa_adists_group_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_adists_forward_group": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "nqa_adists_window_stage_group": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "nqa_adists_chain_group_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_adists_chain_group": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz,
-                                    C.POINTER(_vp), _vp, _vp]),
-    "nqa_adists_window_stage": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "nqa_adists_window_grid": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
-    "nqa_adists_chain_dims": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
-    "nqa_adists_chain_bytes": (_sz, [_i, _i, _i]),
-    "nqa_adists_chain": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _vp, _sz, C.POINTER(_vp), _vp,
-                              _vp, _vp]),
-    # the same entry points with an explicit window size behind W (3..63; the old names are their window-21 calls)
-    "nqa_adists_workspace_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_adists_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp]),
-    "nqa_adists_forward_map_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_adists_dists_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "nqa_adists_group_workspace_bytes_n": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "nqa_adists_forward_group_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "nqa_adists_window_stage_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "nqa_adists_window_stage_group_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "nqa_adists_chain_dims_n": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
-    "nqa_adists_chain_bytes_n": (_sz, [_i, _i, _i, _i]),
-    "nqa_adists_chain_n": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz, C.POINTER(_vp),
-                                _vp, _vp, _vp]),
-    "nqa_adists_chain_group_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_adists_chain_group_n": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _sz,
-                                      C.POINTER(_vp), _vp, _vp]),
-    "nqa_adists_front_bytes": (_sz, [_i, C.POINTER(_i), C.POINTER(_i), _i]),
-    "nqa_adists_front_grid": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i)]),
-    "nqa_adists_front": (_i, [_vp, _vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_u8hwc_to_f32nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_resize_bilinear_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_u8_resize_bilinear_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_resize_pil_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_resize_pil_bilinear_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "nqa_packed_conv_split_bytes": (_sz, [_i, _i]),
-    "nqa_pack_conv_split": (_i, [_vp, _i, _i, _vp]),
-    "nqa_conv3x3_split": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "nqa_relu_mask_split16": (_i, [_vp, _vp, _i, C.c_long, _i, _vp, _vp]),
-    "nqa_l2pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_conv1_1_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "nqa_dists_stats_nhwc_backward_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_dists_stats_nhwc_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_dists_stats_target_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_dists_stats_target": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, C.c_long, _vp]),
-    "nqa_dists_stats_nhwc_backward_from_bytes": (_sz, [_i, _i]),
-    "nqa_dists_stats_nhwc_backward_from": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp,
-                                                _vp]),
-    "nqa_dists_stats_nhwc_grad_y_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, C.c_long, _vp, _sz, _vp, _vp]),
-    "nqa_dists_target_step_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_dists_target_step_forward": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_dists_target_step_backward": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _vp, _vp, C.POINTER(_vp), _vp, _i, _vp,
-                                            _sz, _vp, _vp]),
-    "nqa_dists_score_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
-    "nqa_grad_exponent_bytes": (_sz, [_i, C.c_long]),
-    "nqa_grad_exponent": (_i, [_vp, _i, C.c_long, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_relu_mask_split16_scaled": (_i, [_vp, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
-    "nqa_l2pool_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_conv1_1_backward_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "nqa_packed_conv_half_bytes": (_sz, [_i, _i]),
-    "nqa_pack_conv_half": (_i, [_vp, _i, _i, _vp]),
-    "nqa_conv3x3_half": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "nqa_relu_mask_f16_scaled": (_i, [_vp, _i, _vp, _i, _i, C.c_long, _i, _vp, _vp, _vp]),
-    "nqa_grad_exponent_half": (_i, [_vp, _i, _i, C.c_long, _vp, _sz, _vp, _vp, _vp]),
-    "nqa_l2pool_backward_scaled_half": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_conv1_1_backward_scaled_half": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "nqa_window_moments_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "nqa_window_moments_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "nqa_adists_ts_backward_bytes": (_sz, [_i, _i, _i, _i]),
-    "nqa_adists_ts_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp]),
-    "nqa_window_moments_forward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "nqa_window_moments_backward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "nqa_adists_ts_backward_bytes_n": (_sz, [_i, _i, _i, _i, _i]),
-    "nqa_adists_ts_backward_n": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _sz, _vp,
-                                      _vp]),
-    "nqa_set_conv_variant": (_i, [_i]),
-    "nqa_timing_enable": (_i, [_i]),
-    "nqa_timing_collect": (_i, [C.POINTER(_i), C.POINTER(C.c_double)]),
-}
-EXPORTS = tuple(_SIGNATURES)
+assert len(K_NAMES) == CONSTANTS["NQA_K_COUNT"], "K_NAMES names every timing class of nqa.h"
 
 _lib = None
-
-
-class NqaError(RuntimeError):
-    pass
 
 
 def lib() -> C.CDLL:
@@ -175,7 +153,7 @@ def lib() -> C.CDLL:
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the ABI is incomplete
             fn.restype, fn.argtypes = res, args
-        if handle.nqa_version() != 1:
+        if handle.nqa_version() != CONSTANTS["NQA_VERSION"]:
             raise NqaError("libnqa_hip.so: ABI version mismatch")
         _lib = handle
     return _lib

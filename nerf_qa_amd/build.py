@@ -91,10 +91,16 @@ FILE_FLAGS = {"nqa_adists.hip": ["-fno-slp-vectorize"], "nqa_conv_pool.hip": ["-
               "nqa_conv1_pool.hip": ["-fno-slp-vectorize"], "nqa_window_moments.hip": ["-fno-slp-vectorize"],
               "nqa_window_moments_n.hip": ["-fno-slp-vectorize"]}
 
+# The link: product library and development variants alike export what include/nqa.h declares (nqa_*) and nothing
+# else; everything is compiled with default visibility, the map makes the rest local.
+EXPORT_MAP = os.path.join(CSRC, "nqa_exports.map")
+LINK_FLAG = "-Wl,--version-script="
+
 
 def source_hash() -> str:
-    """sha256 (16 hex digits) over the HIP sources, headers and compile flags: names the library build that the
-    committed rocprofv3 summaries (profiles/r03_traffic.json) were measured on, independently of the machine."""
+    """sha256 (16 hex digits) over the HIP sources, headers, compile flags, link flag and export map: names the library
+    build that the committed rocprofv3 summaries (profiles/r03_traffic.json) were measured on, independently of the
+    machine."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
@@ -102,6 +108,8 @@ def source_hash() -> str:
         h.update(os.path.basename(path).encode())
         h.update(open(path, "rb").read())
     h.update(" ".join(FLAGS + sorted(f"{k}:{' '.join(v)}" for k, v in FILE_FLAGS.items())).encode())
+    h.update(LINK_FLAG.encode())
+    h.update(open(EXPORT_MAP, "rb").read())
     return h.hexdigest()[:16]
 
 
@@ -161,7 +169,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str |
         for path in [RESOURCES_BUILD] + ([RESOURCES] if emit_resources else []):
             with open(path, "w") as f:
                 json.dump({k: resources[k] for k in sorted(resources)}, f, indent=0)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib]
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", LINK_FLAG + EXPORT_MAP, *objs, "-o", lib]
     subprocess.run(cmd, check=True)
     if variant:  # a development variant's objects are not reused: do not let them pile up
         for o in objs:
