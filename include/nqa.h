@@ -508,6 +508,27 @@ size_t nqa_resize_pil_workspace_bytes(int n, int Hin, int Win, int Hout, int Wou
 int nqa_resize_pil_bilinear_u8(const uint8_t *in, int n, int Hin, int Win, int Hout, int Wout, void *workspace,
                                size_t workspace_bytes, uint8_t *out, void *stream);
 
+/* ---- score-map targets of the no-reference dataset prep (nerf_nr_qa_prep_4.py:71-133) -- */
+
+/* From the K A-DISTS distortion maps of a frame's K renders to the K score-map images and the 2K + 4 logged extrema,
+ * for F frames: v = double(max(map, 1e-10f)) (NaN stays NaN); per pixel mean = (sum_k v) / K, k ascending, and the
+ * unbiased std = sqrt(sum_k (v - mean)^2 / (K - 1)) (K = 1: NaN, as torch.std); min and max per map and of the std and
+ * mean maps, NaN propagating as amin / amax; byte = trunc(255 * (log_max - (-log10 q)) / (log_max - log_min)) where
+ * the spread is > 0, else 0, and 0 for a quotient that is not finite.  The per-pixel -log10 and the one that forms
+ * log_max / log_min are one device function.
+ *   maps  dev float32 (F, K, H, W): frame f's K maps as nqa_adists_forward_map writes them for K pairs.
+ *   rgb   dev uint8 (F, K, H, W, 3): HWC, channels (mean, map k, std).
+ *   logs  dev double (F, 2K + 4): K x log_max_k = -log10(min of map k), K x log_min_k = -log10(max of map k), then
+ *         std_max, std_min, mean_max, mean_min, formed the same way from the std and mean maps.
+ * Three launches (NQA_K_PREP), no atomics, fixed fold order: bitwise repeatable.  The workspace
+ * (nqa_score_maps_workspace_bytes; 0 for sizes the call refuses) holds the fp64 mean and std maps and the per-block
+ * partials; nothing in it is read before it is written.
+ * Refused on the host, before any launch: NQA_E_ARG null pointer, non-positive size, K > 256, F * K > 65535,
+ * F * K * H * W * 3 reaching 2^31; NQA_E_WORKSPACE a short workspace. */
+size_t nqa_score_maps_workspace_bytes(int F, int K, int H, int W);
+int nqa_score_maps(const float *maps, int F, int K, int H, int W, void *workspace, size_t workspace_bytes,
+                   uint8_t *rgb, double *logs, void *stream);
+
 /* ---- tuning hook ------------------------------------------------------------------ */
 
 /* The stage-closing conv of the DISTS path fused with what consumes its tap (nqa_conv_pool.hip; replaces

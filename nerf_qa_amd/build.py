@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnqa_hip.so")
 SOURCES = ["nqa_api.hip", "nqa_weights.hip", "nqa_conv.hip", "nqa_conv_pool.hip", "nqa_conv1_pool.hip", "nqa_pool_stats.hip", "nqa_group_stats.hip", "nqa_adists.hip", "nqa_prep.hip",
            "nqa_backward.hip", "nqa_stats_backward.hip", "nqa_loss_backward.hip", "nqa_loss_step.hip", "nqa_window_moments.hip",
-           "nqa_window_moments_n.hip", "nqa_adists_backward.hip"]
+           "nqa_window_moments_n.hip", "nqa_adists_backward.hip", "nqa_score_maps.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]  # the remarks are parsed below: no hand-scheduled kernel may spill

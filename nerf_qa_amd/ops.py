@@ -991,6 +991,47 @@ def resize_pil_bilinear_u8(frames: torch.Tensor, size, ws: Workspace | None = No
     return out
 
 
+# ---- score-map targets (nerf_nr_qa_prep_4.py:71-133) ---------------------------------------------
+def _score_maps_dims(maps: torch.Tensor):
+    """Every check of score_maps on its input but its device; (F, K, H, W)."""
+    if not torch.is_tensor(maps) or maps.dim() != 4 or maps.numel() == 0:
+        raise ValueError(f"score_maps: maps must be a non-empty (F, K, H, W) tensor, got {tuple(getattr(maps, 'shape', ()))}")
+    if maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError(f"score_maps: maps must be contiguous float32, got {maps.dtype}"
+                         f"{'' if maps.is_contiguous() else ' (not contiguous)'}")
+    return tuple(int(s) for s in maps.shape)
+
+
+def score_maps(maps: torch.Tensor, ws: Workspace | None = None):
+    """The arithmetic the reference's dataset prep runs on the CPU after as_map=True (include/nqa.h, nqa_score_maps):
+    from maps (F, K, H, W) float32 -- frame f's K distortion maps, one per render -- to (rgb (F, K, H, W, 3) uint8 with
+    the channels (mean, map k, std), logs (F, 2K + 4) float64: K x log_max, K x log_min, std_max, std_min, mean_max,
+    mean_min)."""
+    f, k, h, w = _score_maps_dims(maps)
+    dev = _need_cuda(maps)
+    rgb = torch.empty((f, k, h, w, 3), dtype=torch.uint8, device=dev)
+    logs = torch.empty((f, 2 * k + 4), dtype=torch.float64, device=dev)
+    score_maps_into(maps, rgb, logs, ws)
+    return rgb, logs
+
+
+def score_maps_into(maps: torch.Tensor, rgb: torch.Tensor, logs: torch.Tensor, ws: Workspace | None = None) -> None:
+    """score_maps into caller-owned contiguous outputs of the shapes and types it would return (tests place them between
+    guard regions).  Every check of score_maps applies."""
+    f, k, h, w = _score_maps_dims(maps)
+    if not (torch.is_tensor(rgb) and torch.is_tensor(logs)):
+        raise ValueError("score_maps: rgb and logs must be tensors")
+    for name, t, sh, dt in (("rgb", rgb, (f, k, h, w, 3), torch.uint8), ("logs", logs, (f, 2 * k + 4), torch.float64)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"score_maps: {name} must be contiguous {dt} {sh}, got {t.dtype} {tuple(t.shape)}")
+    dev = _need_cuda(maps, rgb, logs)
+    nbytes = lib().nqa_score_maps_workspace_bytes(f, k, h, w)
+    if nbytes == 0:
+        raise _lib.NqaError(f"libnqa_hip: {lib().nqa_last_error().decode()}")
+    buf = (ws or Workspace()).get(nbytes, dev)
+    _call(dev, lib().nqa_score_maps, ptr(maps), f, k, h, w, ptr(buf), buf.numel(), ptr(rgb), ptr(logs), stream_ptr(dev))
+
+
 # ---- split16 (NQA_PREC_F32S activation format between conv layers; tests and tools only) ----------
 def split16_encode(a: torch.Tensor) -> torch.Tensor:
     """float32 NHWC (..., C) -> split16 bytes viewed as float32 of the same shape (4 bytes per element)."""
